@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark: audio-seconds/sec of CPC training (1.28 s windows @16 kHz, 128 negatives).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps of the headline configuration and prints its line.  --full adds what
+else the line has carried: the CPU baseline, the in-situ kernel timings and roofline figures, the stream-placement
+checks and the other configurations (--also).  --dump-outputs DIR writes what the last timed step computed as .npy files.
 
 One "step" = one optimisation step of the reference's trainStep (train.py:95-113) on one batch of
 synthetic windows already resident in HBM: encoder on cat([past, future]) (2b windows), the context
@@ -333,21 +338,42 @@ def hold_the_collector():
     return "frozen after the warm-up steps (gc.freeze)"
 
 
-def measure(args, cfg_name, device, rank, world, use_dist, steps, warmup, cpu_seconds):
+DUMP_PARAM_ELEMENTS = 8 << 20          # at most 32 MB of parameters per dump; larger models: a fixed, seeded sample
+
+
+def dump_outputs(out_dir, arrays, opt):
+    """What a caller of the timed step receives, as <out_dir>/<name>.npy (float32): `arrays` (losses and accuracies of the last
+    step) and `parameters`, the optimizer's flat buffer after the last update (criterion parameters first, then the model's:
+    buildOptimizer's order).  Above DUMP_PARAM_ELEMENTS elements the same seeded sample of positions is written every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    flat = opt.flat.detach()
+    if flat.numel() > DUMP_PARAM_ELEMENTS:
+        pick = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_PARAM_ELEMENTS].sort().values
+        flat = flat[pick.to(flat.device)]
+    arrays = dict(arrays, parameters=flat)
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32))
+    log(f"outputs of the last timed step written to {out_dir}: {', '.join(sorted(arrays))}")
+
+
+def measure(args, cfg_name, device, rank, world, use_dist, steps, warmup, cpu_seconds, dump_dir=None):
     """Build CONFIGS[cfg_name], run `warmup` untimed and `steps` timed steps (barrier + synchronize on both sides, MAX over
-    ranks) and return the result record (rank 0: the dict that is printed; other ranks: None)."""
+    ranks) and return the result record (rank 0: the dict that is printed; other ranks: None).  dump_dir: rank 0 writes what
+    the last timed step computed there (dump_outputs)."""
     from cpc2_amd import _lib
     from cpc2_amd.train import DataParallelContext, cpcStep
     cfg = CONFIGS[cfg_name]
     lib = _lib.load()
     prev_mode = lib.cpc_gemm_set_mode(cfg.get("gemm_mode", 0))
     try:
-        return _measure(args, cfg_name, cfg, lib, device, rank, world, use_dist, steps, warmup, cpu_seconds)
+        return _measure(args, cfg_name, cfg, lib, device, rank, world, use_dist, steps, warmup, cpu_seconds, dump_dir)
     finally:
         lib.cpc_gemm_set_mode(prev_mode)
 
 
-def _measure(args, cfg_name, cfg, lib, device, rank, world, use_dist, steps, warmup, cpu_seconds):
+def _measure(args, cfg_name, cfg, lib, device, rank, world, use_dist, steps, warmup, cpu_seconds, dump_dir):
     from cpc2_amd import _lib
     from cpc2_amd.train import DataParallelContext, backward, cpcStep
     model, crit, opt = build(cfg, device)
@@ -367,15 +393,15 @@ def _measure(args, cfg_name, cfg, lib, device, rank, world, use_dist, steps, war
     label = torch.zeros(args.batch, dtype=torch.long, device=device)
 
     def step():
-        tot, losses, _acc = cpcStep(x, x, label, model, crit, dedup=dedup, dp=dp, strict=strict)
+        tot, losses, acc = cpcStep(x, x, label, model, crit, dedup=dedup, dp=dp, strict=strict)
         backward(tot)                                       # (train.py:109; cpc2_amd.train.backward seeds it with a cached 1.0)
         dp.reduce_and_step()
         opt.zero_grad()
-        return losses
+        return losses, acc
 
     log(f"rank {rank}: {cfg_name}: model built, starting {warmup} warm-up steps")
     for i in range(warmup):
-        losses = step()
+        losses, acc = step()
         if i == 0:
             torch.cuda.synchronize()
             log("first step done")
@@ -384,7 +410,7 @@ def _measure(args, cfg_name, cfg, lib, device, rank, world, use_dist, steps, war
     gc_note = hold_the_collector()
     if use_dist:
         dist.barrier()
-    prof = not args.no_prof
+    prof = args.full and not args.no_prof
     roof = "gemm_planes_nt" if cfg["hidden"] % 256 == 0 else "gemm_nt"
     if prof:
         lib.cpc_prof_enable(2 if roof == "gemm_planes_nt" else 3)   # the roofline kernel only inside the timed region
@@ -400,7 +426,7 @@ def _measure(args, cfg_name, cfg, lib, device, rank, world, use_dist, steps, war
     t0 = time.perf_counter()
     for i in range(steps):
         ta = time.perf_counter()
-        losses = step()
+        losses, acc = step()
         enqueue_s += time.perf_counter() - ta
         marks[i + 1].record()
     t_enqueued = time.perf_counter() - t0
@@ -443,6 +469,9 @@ def _measure(args, cfg_name, cfg, lib, device, rank, world, use_dist, steps, war
         rank_ms = [1e3 * float(-tmax[2].item()) / steps, 1e3 * float(tmax[1].item()) / steps]     # min, max over the ranks
         exposed_ms = float(tmax[3].item()) if exposed_ms is not None else None
     final_loss = [round(float(v), 4) for v in losses.detach().cpu().view(-1)]
+    if dump_dir and rank == 0:
+        # (before the extra profiling steps of --full below: they would move the parameters on)
+        dump_outputs(dump_dir, {"losses": losses, "accuracies": acc}, opt)
 
     kernels = {}
 
@@ -473,7 +502,7 @@ def _measure(args, cfg_name, cfg, lib, device, rank, world, use_dist, steps, war
         read_classes(tuple(c for c in ("gemm_planes_nt", "gemm_planes_tn", "gemm_nt", "gemm_tn", "infonce_fwd", "infonce_bwd",
                                        "gru_fwd", "gru_bwd", "conv0_fwd", "conv0_bwd") if c != roof), extra)
     cur = _lib.stream_ptr(device)
-    if use_dist and dp.active:
+    if args.full and use_dist and dp.active:
         # RCCL's own stream is torch's to pick: does it share the training stream's hardware queue?  A 2 ms spin kernel on the
         # training stream, a one-element all-reduce issued from an idle third stream (so that the collective does not wait for the
         # spin by its own ordering rule): finished while the spin still runs = on another queue.  After the clock has stopped.
@@ -560,18 +589,19 @@ def _measure(args, cfg_name, cfg, lib, device, rank, world, use_dist, steps, war
         # the ten timed classes against the step (caller's stream and the library's side stream together; the small kernels
         # between them are not timed): what is left is launch gaps + untimed kernels, or -- when it jumps -- a stream that idled
         host_rec["timed_kernel_classes_ms_per_step"] = round(sum(k["ms_per_step"] for k in kernels.values()), 3)
-    # the library's side stream (deferred backward work) and the training stream on different hardware queues?  Tested, not assumed
-    # (cpc2_hip.h, cpc_stream_create_apart; 200 us, after the clock has stopped)
-    side = ctypes.c_void_p()
-    cur = _lib.stream_ptr(device)
-    if lib.cpc_side_stream(cur, ctypes.byref(side)) == 0:
-        host_rec["side_stream_runs_beside_training_stream"] = lib.cpc_streams_overlap(cur, side) == 1
-    wst = ctypes.c_void_p()
-    if lib.cpc_negidx_stream(crit.sampler._h, ctypes.byref(wst)) == 0 and wst.value:
-        host_rec["sampler_stream_runs_beside_training_stream"] = lib.cpc_streams_overlap(cur, wst) == 1
-    if getattr(dp, "_helper", None) is not None:
-        host_rec["exchange_helper_stream_runs_beside_training_stream"] = lib.cpc_streams_overlap(cur, ctypes.c_void_p(dp._helper.cuda_stream)) == 1
-    host_rec["streams_handed_out_untested"] = int(lib.cpc_stream_apart_failures())
+    if args.full:
+        # the library's side stream (deferred backward work) and the training stream on different hardware queues?  Tested, not
+        # assumed (cpc2_hip.h, cpc_stream_create_apart; 200 us, after the clock has stopped)
+        side = ctypes.c_void_p()
+        cur = _lib.stream_ptr(device)
+        if lib.cpc_side_stream(cur, ctypes.byref(side)) == 0:
+            host_rec["side_stream_runs_beside_training_stream"] = lib.cpc_streams_overlap(cur, side) == 1
+        wst = ctypes.c_void_p()
+        if lib.cpc_negidx_stream(crit.sampler._h, ctypes.byref(wst)) == 0 and wst.value:
+            host_rec["sampler_stream_runs_beside_training_stream"] = lib.cpc_streams_overlap(cur, wst) == 1
+        if getattr(dp, "_helper", None) is not None:
+            host_rec["exchange_helper_stream_runs_beside_training_stream"] = lib.cpc_streams_overlap(cur, ctypes.c_void_p(dp._helper.cuda_stream)) == 1
+        host_rec["streams_handed_out_untested"] = int(lib.cpc_stream_apart_failures())
     out["host"] = host_rec
     out["_gradient_bytes"] = 4 * opt.flat_grad.numel()
     out["_comm"] = {"early_bytes": 4 * sum(hi - lo for lo, hi in dp.early), "late_bytes": 4 * sum(hi - lo for lo, hi in dp.late)
@@ -602,8 +632,9 @@ def write_synthetic_corpus(root, n_windows, n_speakers=16, files_per_speaker=8, 
     return n_files * per_file
 
 
-def measure_feeder(args, cfg_name, device, rank, world, use_dist, resident_rate):
-    """One epoch of cpc2_amd.train.trainStep fed by the window feeder from files on disk; returns the record (rank 0) or None."""
+def measure_feeder(args, cfg_name, device, rank, world, use_dist, resident_rate, dump_dir=None):
+    """One epoch of cpc2_amd.train.trainStep fed by the window feeder from files on disk; returns the record (rank 0) or None.
+    dump_dir: what trainStep returned for the timed epoch (its mean losses and accuracies) and the parameters after it."""
     import random
     import shutil
     import tempfile
@@ -692,6 +723,8 @@ def measure_feeder(args, cfg_name, device, rank, world, use_dist, resident_rate)
             dist.all_reduce(wsum)
             windows = int(wsum[0].item())
         _lib.check(lib.cpc_async_error_check(_lib.stream_ptr(device)), "async error check")
+        if dump_dir and rank == 0:
+            dump_outputs(dump_dir, {"losses": logs["locLoss_train"], "accuracies": logs["locAcc_train"]}, opt)
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
     if rank != 0:
@@ -772,17 +805,25 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=64, help="windows per GPU")
     ap.add_argument("--config", default="small", choices=sorted(CONFIGS))
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the CPU baseline leg (0 = skip)")
-    ap.add_argument("--no-prof", action="store_true", help="skip the in-situ kernel timing")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the CPU baseline, in-situ kernel "
+                         "timings and roofline figures, stream placement, the other configurations (--also)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (losses, accuracies, parameters after the update) as "
+                         "DIR/<name>.npy, float32")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="--full: budget of the CPU baseline leg (0 = skip)")
+    ap.add_argument("--no-prof", action="store_true", help="--full: skip the in-situ kernel timing")
     ap.add_argument("--dedup", action="store_true",
                     help="one encoder/AR pass when past is future (identical results; NOT the reference's 2b-window step)")
     ap.add_argument("--also", default=None,
-                    help="comma-separated configs measured AFTER the headline's timed region and reported inside the same JSON "
-                         "line under \"other_configs\" (default at one GPU with the small config: large,transformer = BASELINE "
-                         "configs[4] per GPU and configs[3]; '' = none)")
+                    help="--full: comma-separated configs measured AFTER the headline's timed region and reported inside the same "
+                         "JSON line under \"other_configs\" (default at one GPU with the small config: large,transformer = "
+                         "BASELINE configs[4] per GPU and configs[3]; '' = none)")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="start the ranks, all-reduce one CPU number over gloo, print it and exit (launcher self-test)")
     args = ap.parse_args()
+    if args.also and not args.full:
+        ap.error("--also measures other configurations: it needs --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` by itself: become the launcher (no GPU call has been made in this process) and run
@@ -818,16 +859,16 @@ def main():
             os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(free_port()))
         dist.init_process_group(backend=backend, init_method="env://", world_size=world, rank=rank)
 
-    # The CPU leg FIRST (rank 0 of a one-GPU run): ~20 s of host work on the oracle's step.  The GPU legs then start on a box that has
-    # paged its libraries in and finished starting up -- the first process on a fresh box has been seen at 23 ms per step with the host
-    # descheduled for 17 of them (tests/test_bench_gpu.py) -- and the timed region never shares the host with the CPU leg.
+    # --full: the CPU leg FIRST (rank 0 of a one-GPU run): ~20 s of host work on the oracle's step.  The GPU legs then start on a box
+    # that has paged its libraries in and finished starting up -- the first process on a fresh box has been seen at 23 ms per step
+    # with the host descheduled for 17 of them (tests/test_bench_gpu.py) -- and the timed region never shares the host with the CPU leg.
     cpu_rec = None
-    if args.cpu_seconds > 0 and world == 1 and not CONFIGS[args.config].get("feeder"):
+    if args.full and args.cpu_seconds > 0 and world == 1 and not CONFIGS[args.config].get("feeder"):
         cpu_rec = cpu_baseline(CONFIGS[args.config], args.cpu_seconds)
     if CONFIGS[args.config].get("feeder"):
-        out = measure_feeder(args, args.config, device, rank, world, use_dist, None)
+        out = measure_feeder(args, args.config, device, rank, world, use_dist, None, args.dump_outputs)
     else:
-        out = measure(args, args.config, device, rank, world, use_dist, args.steps, args.warmup, args.cpu_seconds)
+        out = measure(args, args.config, device, rank, world, use_dist, args.steps, args.warmup, args.cpu_seconds, args.dump_outputs)
     if out is not None and cpu_rec is not None:
         out["cpu_baseline"] = cpu_rec
     if out is not None:
@@ -845,12 +886,12 @@ def main():
             use_dist and not os.environ.get("CPC_BENCH_NO_OVERLAP")) else "one blocking all-reduce" if use_dist else None
         out["comm"] = comm
     also = args.also
-    if also is None:
+    if also is None and args.full:
         # (N > 1: the line still carries BASELINE configs[4] -- CPC-large is DEFINED as the 8-GPU data-parallel config)
         also = ("large,transformer,small_strict,small_feeder,recipe,small_3term,small_dedup" if world == 1 else "large") \
             if (args.config == "small" and not args.no_prof) else ""
     others = []
-    for name in [n for n in also.split(",") if n]:
+    for name in [n for n in (also or "").split(",") if n]:
         # (an extra configuration must never cost the headline its line: a failure is recorded in its place.  Every rank runs the
         #  same code on the same shapes, so an exception is raised on every rank alike and no collective is left half-entered)
         try:

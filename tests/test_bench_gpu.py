@@ -16,8 +16,8 @@ def _bench(env_extra):
     env = dict(os.environ, PYTHONPATH=ROOT, HSA_ENABLE_IPC_MODE_LEGACY="0", **env_extra)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "16", "--warmup", "6", "--cpu-seconds", "0",
-                        "--also", ""], env=env, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "16", "--warmup", "6", "--full",
+                        "--cpu-seconds", "0", "--also", ""], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = r.stdout.strip().splitlines()[-1]
     # every line this module measures is kept where gpurun merges it back from: a failure is then read from the record, not re-run
@@ -129,7 +129,7 @@ def test_the_drivers_launch_of_two_ranks_prints_one_line():
         env.pop(k, None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-                        "--also", "large"], env=env, capture_output=True, text=True, timeout=420)
+                        "--full", "--also", "large"], env=env, capture_output=True, text=True, timeout=420)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -140,3 +140,35 @@ def test_the_drivers_launch_of_two_ranks_prints_one_line():
     assert rec["comm"]["early_bytes"] + rec["comm"]["late_bytes"] == rec["comm"]["gradient_bytes"]
     assert "rccl_stream_runs_beside_training_stream" in rec["host"]
     assert [o["config"]["workload"][:9] for o in rec["other_configs"]] == ["CPC-large"] and "error" not in rec["other_configs"][0]
+
+
+def test_a_plain_run_times_the_headline_alone_and_dumps_its_last_step(tmp_path):
+    """`bench.py --gpus 1 --steps N --warmup W` times N steps of the headline configuration and nothing else (no CPU baseline,
+    kernel timings or other configurations: those are --full's), and --dump-outputs writes what the last timed step computed.
+    Two runs with the same arguments see the same inputs: their outputs are equal bit for bit (the step has no fp32 atomics:
+    tests/test_gpu_parity.py::test_training_steps_are_reproducible_bit_for_bit)."""
+    import numpy as np
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    runs = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                            "--dump-outputs", str(out)], env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        runs.append((json.loads(lines[0]), {p.stem: np.load(p) for p in sorted(out.glob("*.npy"))}))
+    rec, arrays = runs[0]
+    assert rec["steps"] == 3 and rec["warmup"] == 2 and rec["n_gpus"] == 1 and rec["dtype"] == "f32"
+    assert rec["value"] > 0 and abs(rec["value"] - 64 * 1.28 / (rec["ms_per_step"] * 1e-3)) < 0.01 * rec["value"]
+    assert not {"cpu_baseline", "other_configs", "roofline", "roofline_similarity"} & set(rec) and rec["kernels"] == {}
+    assert sorted(arrays) == ["accuracies", "losses", "parameters"]
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert arrays["losses"].size == 12 and arrays["accuracies"].size == 12
+    # (the line's final_losses are the same step's losses, rounded)
+    assert np.allclose(arrays["losses"].reshape(-1), rec["config"]["final_losses"], atol=1e-4)
+    for name, a in arrays.items():
+        assert np.array_equal(a, runs[1][1][name]), f"{name}: two runs with the same arguments differ"

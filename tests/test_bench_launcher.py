@@ -70,3 +70,9 @@ def test_no_collective_behind_a_rank_zero_only_return():
                     and isinstance(node.func.value, ast.Name) and node.func.value.id == "dist" and node.lineno > first:
                 found.append((fn.name, node.lineno, node.func.attr))
     assert not found, f"collectives behind a rank-dependent return: {found}"
+
+
+def test_other_configurations_need_full():
+    # a plain run measures the headline alone: asking for more without --full is an error, not a silently longer run
+    res = _run("--gpus", "1", "--also", "large")
+    assert res.returncode != 0 and "--full" in res.stderr

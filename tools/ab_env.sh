@@ -7,7 +7,7 @@ args=${@:---steps 16 --warmup 6 --cpu-seconds 0 --also=}
 for rep in $(seq 1 $reps); do
   for arm in A B; do
     envs=$a; [ $arm = B ] && envs=$b
-    env $envs python3 bench.py $args > $out/${arm}_$rep.json 2> $out/${arm}_$rep.err || { echo "$arm $rep failed"; tail -5 $out/${arm}_$rep.err; exit 1; }
+    env $envs python3 bench.py --full $args > $out/${arm}_$rep.json 2> $out/${arm}_$rep.err || { echo "$arm $rep failed"; tail -5 $out/${arm}_$rep.err; exit 1; }
     python3 - $out/${arm}_$rep.json "$arm[$envs] rep $rep" <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -9,7 +9,7 @@ mkdir -p $out
 for rep in $(seq 1 $reps); do
   i=0
   for envs in "${arms[@]}"; do
-    env $envs python3 bench.py $args > $out/arm${i}_$rep.json 2> $out/arm${i}_$rep.err || { echo "arm $i rep $rep failed"; tail -5 $out/arm${i}_$rep.err; exit 1; }
+    env $envs python3 bench.py --full $args > $out/arm${i}_$rep.json 2> $out/arm${i}_$rep.err || { echo "arm $i rep $rep failed"; tail -5 $out/arm${i}_$rep.err; exit 1; }
     python3 - $out/arm${i}_$rep.json "[$envs] rep $rep" <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

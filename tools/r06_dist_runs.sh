@@ -5,7 +5,7 @@ n=${1:-10}; q=${2:-8}
 out=gpurun_out/r06_dist_runs
 mkdir -p $out
 for rep in $(seq 1 $n); do
-  env RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=$((29800 + rep)) CPC_BENCH_FORCE_DIST=1 GPU_MAX_HW_QUEUES=$q python3 bench.py --steps 16 --warmup 6 --cpu-seconds 0 --also= > $out/run_$rep.json 2> $out/run_$rep.err || { echo "run $rep failed"; tail -3 $out/run_$rep.err; exit 1; }
+  env RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=$((29800 + rep)) CPC_BENCH_FORCE_DIST=1 GPU_MAX_HW_QUEUES=$q python3 bench.py --full --steps 16 --warmup 6 --cpu-seconds 0 --also= > $out/run_$rep.json 2> $out/run_$rep.err || { echo "run $rep failed"; tail -3 $out/run_$rep.err; exit 1; }
   python3 - $out/run_$rep.json $rep <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); h=d["host"]; k=d["kernels"]

@@ -5,7 +5,7 @@ set -o pipefail
 export TMPDIR=/tmp
 out=gpurun_out/r06_pg
 mkdir -p $out
-common="--steps 16 --warmup 6 --cpu-seconds 0 --also= "
+common="--full --steps 16 --warmup 6 --cpu-seconds 0 --also= "
 dist_env="RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 CPC_BENCH_FORCE_DIST=1"
 for rep in 1 2; do
   python3 bench.py $common > $out/plain_$rep.json 2> $out/plain_$rep.err || exit 1

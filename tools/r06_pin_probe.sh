@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 out=gpurun_out/r06_pin
 mkdir -p $out
-common="--steps 16 --warmup 6 --cpu-seconds 0 --also="
+common="--full --steps 16 --warmup 6 --cpu-seconds 0 --also="
 for rep in 1 2 3; do
   env RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=2960$rep CPC_BENCH_FORCE_DIST=1 CPC_BENCH_PIN_CORES=2 python3 bench.py $common > $out/dist_pin2_$rep.json 2> $out/dist_pin2_$rep.err || exit 1
   env RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=2961$rep CPC_BENCH_FORCE_DIST=1 python3 bench.py $common > $out/dist_free_$rep.json 2> $out/dist_free_$rep.err || exit 1

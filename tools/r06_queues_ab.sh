@@ -2,7 +2,7 @@
 # One-rank process-group step with the runtime's four hardware queues per priority against eight, alternating, 6 runs each.
 out=gpurun_out/r06_q48
 mkdir -p $out
-common="--steps 16 --warmup 6 --cpu-seconds 0 --also="
+common="--full --steps 16 --warmup 6 --cpu-seconds 0 --also="
 for rep in 1 2 3 4 5 6; do
   for q in 4 8; do
     env RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=297$q$rep CPC_BENCH_FORCE_DIST=1 GPU_MAX_HW_QUEUES=$q python3 bench.py $common > $out/q${q}_$rep.json 2> $out/q${q}_$rep.err || exit 1

@@ -1,5 +1,6 @@
 #!/bin/bash
-OUT=gpurun_out/ab_pair_step.txt
+mkdir -p bench_out
+OUT=bench_out/ab_pair_step.txt
 : > $OUT
 for v in pair nopair; do
   if [ $v = nopair ]; then export CPC_PLANES_NO_PAIR=1; else unset CPC_PLANES_NO_PAIR; fi
@@ -18,10 +19,10 @@ unset PROBE_TAPS PROBE_STRIDE PROBE_COLS PROBE_L
 for rep in 1 2 3; do
   for v in pair nopair; do
     if [ $v = nopair ]; then export CPC_PLANES_NO_PAIR=1; else unset CPC_PLANES_NO_PAIR; fi
-    timeout -k 10 200 python bench.py --cpu-seconds 0 --also "" --steps 40 --warmup 10 > gpurun_out/ab_ps_$v.json 2>gpurun_out/ab_ps_$v.err || tail -5 gpurun_out/ab_ps_$v.err >> $OUT
+    timeout -k 10 200 python bench.py --full --cpu-seconds 0 --also "" --steps 40 --warmup 10 > bench_out/ab_ps_$v.json 2>bench_out/ab_ps_$v.err || tail -5 bench_out/ab_ps_$v.err >> $OUT
     python - >> $OUT <<PY
 import json
-d=json.loads(open("gpurun_out/ab_ps_$v.json").read().strip().splitlines()[-1])
+d=json.loads(open("bench_out/ab_ps_$v.json").read().strip().splitlines()[-1])
 k=d["kernels"]
 print("step $v rep $rep: %.3f ms/step  planes_nt %.3f  planes_tn %.3f  frac %.3f" % (d["ms_per_step"], k["gemm_planes_nt"]["ms_per_step"], k["gemm_planes_tn"]["ms_per_step"], d["roofline"]["frac"]))
 PY

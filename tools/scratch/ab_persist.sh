@@ -1,6 +1,7 @@
 #!/bin/bash
 # the persistent pair kernel (next item's first double stage requested under the epilogue) against one workgroup per tile
-OUT=gpurun_out/ab_persist.txt
+mkdir -p bench_out
+OUT=bench_out/ab_persist.txt
 : > $OUT
 for rep in 1 2; do
   for v in persist tile; do
@@ -20,10 +21,10 @@ unset PROBE_TAPS PROBE_STRIDE PROBE_COLS PROBE_L
 for rep in 1 2 3; do
   for v in persist tile; do
     if [ $v = tile ]; then export CPC_PLANES_NO_PERSIST=1; else unset CPC_PLANES_NO_PERSIST; fi
-    timeout -k 10 200 python bench.py --cpu-seconds 0 --also "" --steps 40 --warmup 10 > gpurun_out/ab_pp_$v.json 2>gpurun_out/ab_pp_$v.err || tail -5 gpurun_out/ab_pp_$v.err >> $OUT
+    timeout -k 10 200 python bench.py --full --cpu-seconds 0 --also "" --steps 40 --warmup 10 > bench_out/ab_pp_$v.json 2>bench_out/ab_pp_$v.err || tail -5 bench_out/ab_pp_$v.err >> $OUT
     python - >> $OUT <<PY
 import json
-d=json.loads(open("gpurun_out/ab_pp_$v.json").read().strip().splitlines()[-1])
+d=json.loads(open("bench_out/ab_pp_$v.json").read().strip().splitlines()[-1])
 k=d["kernels"]
 print("step $v rep $rep: %.3f ms/step  planes_nt %.3f  frac %.3f" % (d["ms_per_step"], k["gemm_planes_nt"]["ms_per_step"], d["roofline"]["frac"]))
 PY

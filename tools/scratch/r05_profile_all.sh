@@ -2,7 +2,8 @@
 # round-5 evidence run: the bench line, kernel stats + PMC passes (small, large, transformer), step timeline, per-shape stamps
 set -u
 TAG=${1:-r05a}
-timeout -k 10 600 python3 bench.py --steps 20 --warmup 5 > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err || { echo "bench failed"; tail -5 gpurun_out/${TAG}_bench.err; exit 1; }
+mkdir -p bench_out
+timeout -k 10 600 python3 bench.py --full --steps 20 --warmup 5 > bench_out/${TAG}_bench.json 2> bench_out/${TAG}_bench.err || { echo "bench failed"; tail -5 bench_out/${TAG}_bench.err; exit 1; }
 bash tools/gpu_profile.sh $TAG small > gpurun_out/prof_$TAG.log 2>&1 || { echo "profile small failed"; tail -5 gpurun_out/prof_$TAG.log; exit 1; }
 bash tools/gpu_profile.sh ${TAG}_large large > gpurun_out/prof_${TAG}_large.log 2>&1 || { echo "profile large failed"; exit 1; }
 bash tools/trace_step.sh $TAG --also "" || exit 1
