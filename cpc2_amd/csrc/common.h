@@ -149,6 +149,9 @@ size_t gemm_tn_scratch_bytes(int M, int N, long R);
 // conv_cin > 0: C is a Conv1d weight [M][conv_cin][conv_k] and column j*conv_cin+ci goes to [ci][j]
 int gemm_tn(const float *A, long lda, const float *B, long ldb, float *C, long ldc, int M, int N, long R,
             void *scratch, size_t scratch_bytes, int conv_cin, int conv_k, hipStream_t st);
+// C = the sum of S slabs [M][N], in slab order (bitwise reproducible); conv_cin > 0: the re-layout of gemm_tn.  The split-K
+// reduce of every GEMM family (gemm_f32.hip, gemm_planes.hip)
+__global__ void gemm_tn_reduce_kernel(const float *slab, int S, int M, int N, float *C, long ldc, int conv_cin, int conv_k);
 
 // out[c] = sum_r part[r*ld + c]
 int colsum(const float *part, long rows, long ld, int width, float *out, hipStream_t st);

@@ -53,7 +53,6 @@ struct GemmNTArgs {
     float *slabs;      // K split with ordered reduction: partial product of blockIdx.y goes to slabs + blockIdx.y * M * N
     int xcd_remap;     // split kernels: column panels of a row tile on one XCD (row tile count % 8 == 0, several panels)
     int vec_out;       // x6 kernels: dense output in 16-byte pieces through LDS (no row map, no atomics; N, ldc % 4 == 0)
-    int dbg;           // -DX6_PROBE builds only: 1 no epilogue, 2 no split arithmetic, 4 no MFMAs, 8 no loads after the first K step
 };
 
 // acc[i][j][e] is C[m][n], m = m0 + wm*32*MI + i*32 + (e&3) + 8*(e>>2) + 4h, n = n0 + wn*64 + j*32 + r32
@@ -351,22 +350,12 @@ __device__ __forceinline__ void split8_store(const float4 &u, const float4 &v, c
     *reinterpret_cast<uint4 *>(plane0 + 2 * plane_bytes + off) = w2;
 }
 
-// (-DX6_PROBE, dbg & 2: the same stores without the split's arithmetic)
-__device__ __forceinline__ void raw8_store(const float4 &u, const float4 &v, char *plane0, int plane_bytes, int off)
-{
-    uint4 w0 = make_uint4(__float_as_uint(u.x), __float_as_uint(u.y), __float_as_uint(v.x), __float_as_uint(v.y));
-    uint4 w1 = make_uint4(__float_as_uint(u.z), __float_as_uint(u.w), __float_as_uint(v.z), __float_as_uint(v.w));
-    *reinterpret_cast<uint4 *>(plane0 + off) = w0;
-    *reinterpret_cast<uint4 *>(plane0 + plane_bytes + off) = w1;
-    *reinterpret_cast<uint4 *>(plane0 + 2 * plane_bytes + off) = w0;
-}
-
 __device__ __forceinline__ int x6_off(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 2) & 3)) << 4); }
 
 // MI x NJ 32x32 MFMA tiles per wave, waves 2 x 2: block tile (64 MI) x (64 NJ).  (2, 2): 128 x 128, three workgroups
 // per CU; (2, 4): 128 x 256 -- for N = 256 the A panel is then read, split and staged once -- two per CU; (1, 2)
 // for small problems.
-template <int MI, int NJ, int DBG = 0> __global__ __launch_bounds__(256, NJ == 4 ? 2 : 3) void gemm_nt_x6_kernel(GemmNTArgs p)
+template <int MI, int NJ> __global__ __launch_bounds__(256, NJ == 4 ? 2 : 3) void gemm_nt_x6_kernel(GemmNTArgs p)
 {
     constexpr int BM = 64 * MI, BNX = 64 * NJ;
     constexpr int PA = BM * 64, PB = BNX * 64;             // bytes per plane
@@ -439,22 +428,14 @@ template <int MI, int NJ, int DBG = 0> __global__ __launch_bounds__(256, NJ == 4
             for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
     const int nk = (kend - kbeg + BK - 1) / BK;
-    constexpr int dbg = DBG;
     load_tiles(0);
     for (int kt = 0; kt < nk; ++kt) {
-        if constexpr ((dbg & 2) != 0) {
-#pragma unroll
-            for (int q = 0; q < MI; ++q) raw8_store(ra[q][0], ra[q][1], As, PA, x6_off(lrow + 64 * q, lchunk));
-#pragma unroll
-            for (int q = 0; q < NJ; ++q) raw8_store(rb[q][0], rb[q][1], Bs, PB, x6_off(lrow + 64 * q, lchunk));
-        } else {
 #pragma unroll
         for (int q = 0; q < MI; ++q) split8_store(ra[q][0], ra[q][1], As, PA, x6_off(lrow + 64 * q, lchunk));
 #pragma unroll
         for (int q = 0; q < NJ; ++q) split8_store(rb[q][0], rb[q][1], Bs, PB, x6_off(lrow + 64 * q, lchunk));
-        }
         __syncthreads();
-        if (kt + 1 < nk && !(dbg & 8)) load_tiles(kt + 1);
+        if (kt + 1 < nk) load_tiles(kt + 1);
 
 #pragma unroll
         for (int kk = 0; kk < BK / 16; ++kk) {
@@ -478,7 +459,6 @@ template <int MI, int NJ, int DBG = 0> __global__ __launch_bounds__(256, NJ == 4
 #pragma unroll
                     for (int j = 0; j < 2; ++j) {
                         f32x16 &c = acc[i][jp + j];
-                        if constexpr ((dbg & 4) != 0) { c[0] += (float)fa[i][0][0] + (float)fb[j][1][0] + (float)fa[i][2][1] + (float)fb[j][2][0] + (float)fa[i][1][0] + (float)fb[j][0][0]; continue; }
                         // smallest terms first
                         c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][2], fb[j][0], c, 0, 0, 0);
                         c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[j][2], c, 0, 0, 0);
@@ -491,7 +471,6 @@ template <int MI, int NJ, int DBG = 0> __global__ __launch_bounds__(256, NJ == 4
         }
         __syncthreads();
     }
-    if constexpr ((dbg & 1) != 0) { if (acc[0][0][0] == 123.456f) p.C[0] = acc[MI - 1][NJ - 1][3]; return; }
     static_assert(4 * 32 * (32 * NJ + 4) * 4 <= 3 * (PA + PB), "the staged epilogue lives in the operand tiles");
     if (p.vec_out) nt_epilogue_staged<MI, NJ>(p, acc, lds, m0, m_end, n0, wave, wm, wn, lane);      // (behind the loop's last barrier)
     else nt_epilogue<MI, NJ>(p, acc, m0, m_end, n0, wm, wn, r32, h);
@@ -506,26 +485,11 @@ template <int MI, int NJ, int DBG = 0> __global__ __launch_bounds__(256, NJ == 4
 template <int ROWS> __device__ __forceinline__ int x6p_off(int row, int half) { return half * (ROWS * 16 + 128) + row * 16; }
 template <int ROWS> constexpr int x6p_plane() { return 2 * ROWS * 16 + 128; }
 
-
-__global__ void gemm_tn_reduce_kernel(const float *slab, int S, int M, int N, float *C, long ldc, int conv_cin, int conv_k);
-
-// A/B switch: CPC_GEMM_X6_OLD=1 selects the two-barrier TN kernel and the K-split rule of rounds 1-5
-static bool x6_pipelined()
-{
-    static const bool old_kernels = getenv("CPC_GEMM_X6_OLD") != nullptr;
-    return !old_kernels;
-}
-
 // few tiles but a long K (e.g. dC = dP . W, K = 12 H): K is split over blockIdx.y
-// (Round 6, tools/x6_sweep.py: below K = 2048 a split costs more than the idle CUs it fills -- 7424 x 256 x 768: 34 us whole
-//  against 44 in four parts; 8192 x 256 x 256: 13.5 against 27 in two; 7424 x 512 x 1536: 83 against 88 -- above it the parts stay
-//  >= 512 k long.  CPC_GEMM_X6_OLD=1 keeps the rule of rounds 1-5 for A/B runs.)
+// (Round 6: below K = 2048 a split costs more than the idle CUs it fills -- 7424 x 256 x 768: 34 us whole against 44 in four
+//  parts; 8192 x 256 x 256: 13.5 against 27 in two; 7424 x 512 x 1536: 83 against 88 -- above it the parts stay >= 512 k long.)
 static int nt_splits(long blocks, int K)
 {
-    if (!x6_pipelined()) {
-        if (blocks >= 2 * 256 || K < 8 * BK) return 1;
-        return (int)std::max<long>(1, std::min<long>(cdiv(3 * 256, blocks), K / (4 * BK)));
-    }
     if (blocks >= 2 * 256 || K < 2048) return 1;
     return (int)std::max<long>(1, std::min<long>(cdiv(3 * 256, blocks), K / 512));
 }
@@ -557,10 +521,6 @@ int gemm_nt(const float *A, long lda, const float *B, long ldb, float *C, long l
     a.M = M; a.N = N; a.K = K; a.map = map;
     a.aligned = (K % 4 == 0) && (K >= 4) && (lda % 4 == 0) && (ldb % 4 == 0) &&
                 ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) % 16 == 0);
-    a.dbg = 0;
-#ifdef X6_PROBE
-    if (getenv("X6_DBG")) a.dbg = atoi(getenv("X6_DBG"));
-#endif
     const bool native = g_gemm_mode.load() == 1;
     const bool split_kernels = a.aligned && !native;
     // segmented row tiling (split kernels): never multiply the junk rows at the end of a sample
@@ -577,24 +537,17 @@ int gemm_nt(const float *A, long lda, const float *B, long ldb, float *C, long l
         // 165 (128 x 256) against 150 (128 x 128) TFLOP/s; with ONE column panel the wide tile also reads A once.
         auto fill = [](long blocks, long places) { return (double)blocks / (double)(cdiv(blocks, places) * places); };
         const double wide = 165.0 * fill(m_tiles(128) * (N / 256), 2 * 256), narrow = 150.0 * fill(m_tiles(128) * (N / 128), 3 * 256);
-        static const bool wide_always = getenv("CPC_GEMM_WIDE_ALWAYS") != nullptr;        // A/B switch
-        nj = (N == 256 || wide >= narrow || wide_always) ? 4 : 2;
+        nj = (N == 256 || wide >= narrow) ? 4 : 2;
     } else if (a.aligned && m_tiles(128) * cdiv(N, BN) < 2 * 256) mi = 1;
-    // (tile / split sweeps of tools/x6_sweep.py: CPC_GEMM_TILE="mi,nj", CPC_GEMM_SPLITS=n)
-    static const char *tile_env = getenv("CPC_GEMM_TILE"), *splits_env = getenv("CPC_GEMM_SPLITS");
-    if (tile_env != nullptr && split_kernels) {
-        if (sscanf(tile_env, "%d,%d", &mi, &nj) != 2 || !((mi == 1 && nj == 2) || (mi == 2 && (nj == 2 || nj == 4)))) { mi = 2; nj = 2; }
-    }
     const long blocks = m_tiles(64 * mi) * cdiv(N, 64 * nj);
     CPC_REQUIRE(blocks <= 2147483647L, "gemm_nt: grid too large (%ld blocks)", blocks);
     // few tiles but a long K (e.g. dC = dP . W, K = 12 H): split K over blockIdx.y, partial products are
     // atomically added into a zeroed C (dense, unmapped outputs only)
     int splits = 1;
-    if (a.aligned && !map.enabled && ldc == N && map.epi == EPI_NONE) splits = splits_env != nullptr ? std::max(1, atoi(splits_env)) : nt_splits(blocks, K);
+    if (a.aligned && !map.enabled && ldc == N && map.epi == EPI_NONE) splits = nt_splits(blocks, K);
     a.kchunk = (int)(cdiv(cdiv(K, splits), BK) * BK);
     splits = (int)cdiv(K, a.kchunk);
-    static const bool no_remap = getenv("CPC_GEMM_NO_XCD") != nullptr;
-    a.xcd_remap = (split_kernels && !no_remap && cdiv(N, 64 * nj) > 1 && m_tiles(64 * mi) % 8 == 0) ? 1 : 0;
+    a.xcd_remap = (split_kernels && cdiv(N, 64 * nj) > 1 && m_tiles(64 * mi) % 8 == 0) ? 1 : 0;
     // the partial products go to slabs summed in a fixed order when the caller lent the room, else straight into a zeroed
     // C with atomics
     a.slabs = nullptr;
@@ -611,19 +564,10 @@ int gemm_nt(const float *A, long lda, const float *B, long ldb, float *C, long l
                 "gemm_nt: a fused elementwise epilogue needs a dense output (M=%ld N=%d K=%d ldc=%ld)", M, N, K, ldc);
     const bool epi_pass = map.epi != EPI_NONE && !(a.vec_out != 0 && split_kernels);     // (only the staged store does it in place)
     dim3 grid((unsigned)blocks, (unsigned)splits);
-    static const bool log_shapes = getenv("CPC_GEMM_LOG") != nullptr;        // tools/x6_shapes.py: one line per launch
-    if (log_shapes) fprintf(stderr, "cpc_gemm nt M=%ld N=%d K=%d lda=%ld ldb=%ld ldc=%ld tile=%dx%d grid=%ld splits=%d map=%d epi=%d kernel=%s\n", M, N, K, lda,
-                            ldb, ldc, 64 * mi, 64 * nj, blocks, splits, map.enabled, map.epi, split_kernels ? "x6" : "f32");
     ProfScope prof(PROF_GEMM_NT, st);
     if (!a.aligned) hipLaunchKernelGGL((gemm_nt_kernel<false, 2>), grid, dim3(256), 0, st, a);
     else if (native && mi == 1) hipLaunchKernelGGL((gemm_nt_kernel<true, 1>), grid, dim3(256), 0, st, a);
     else if (native) hipLaunchKernelGGL((gemm_nt_kernel<true, 2>), grid, dim3(256), 0, st, a);
-#ifdef X6_PROBE
-#define X6_CASE(D) else if (a.dbg == D && nj == 4) hipLaunchKernelGGL((gemm_nt_x6_kernel<2, 4, D>), grid, dim3(256), 0, st, a); \
-    else if (a.dbg == D && mi == 1) hipLaunchKernelGGL((gemm_nt_x6_kernel<1, 2, D>), grid, dim3(256), 0, st, a); \
-    else if (a.dbg == D) hipLaunchKernelGGL((gemm_nt_x6_kernel<2, 2, D>), grid, dim3(256), 0, st, a);
-    X6_CASE(1) X6_CASE(2) X6_CASE(4) X6_CASE(8) X6_CASE(3) X6_CASE(6) X6_CASE(14) X6_CASE(15)
-#endif
     else if (nj == 4) hipLaunchKernelGGL((gemm_nt_x6_kernel<2, 4>), grid, dim3(256), 0, st, a);
     else if (mi == 1) hipLaunchKernelGGL((gemm_nt_x6_kernel<1, 2>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((gemm_nt_x6_kernel<2, 2>), grid, dim3(256), 0, st, a);
@@ -760,138 +704,13 @@ template <bool ALIGNED> __global__ __launch_bounds__(256) void gemm_tn_kernel(Ge
         }
 }
 
-// TN product on the bf16 pipe (same three-term split as gemm_nt_x6_kernel).  The reduction index r is the ROW
-// of both operands, so the loader transposes while it splits: a thread takes an 8(r) x 4(column) micro tile
-// (8 row loads of 16 bytes), and writes, for each of its 4 columns, the 8 consecutive r as one 16-byte chunk per
-// plane -> the LDS image is [column][32 r] bf16, the layout (and swizzle) the NT kernel reads its fragments from.
-__global__ __launch_bounds__(256, 3) void gemm_tn_x6_kernel(GemmTNArgs p)
-{
-    constexpr int PL = BM * 64;                            // bytes per plane (BM == BN)
-    __shared__ __attribute__((aligned(16))) char lds[6 * PL];
-    char *As = lds;                   // [3][BM][64 B]
-    char *Bs = lds + 3 * PL;          // [3][BN][64 B]
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int r32 = lane & 31, h = lane >> 5;
-
-    int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-    if (p.xcd_remap) {
-        // workgroups go to the 8 XCDs round robin in dispatch order (x fastest): give ALL tiles of one row slab to one XCD,
-        // so that the slab's A and B rows are fetched into one L2 instead of into eight
-        const unsigned b = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-        const unsigned tiles = gridDim.x * gridDim.y, j = b >> 3, tile = j % tiles;
-        bz = (int)((j / tiles) * 8 + (b & 7));
-        by = (int)(tile / gridDim.x);
-        bx = (int)(tile % gridDim.x);
-    }
-    const int i0 = by * BM;
-    const int j0 = bx * BN;
-    const long rbeg = (long)bz * p.chunk;
-    long rend = rbeg + p.chunk;
-    if (rend > p.R) rend = p.R;
-
-    // waves 0,1 stage A, waves 2,3 stage B: micro tile u -> rows 8*(u&3) .. +7, columns 4*(u>>2) .. +3
-    const bool isA = tid < 128;                                // wave uniform
-    const int u = tid & 127;
-    const int rg = u & 3, cg = u >> 2;
-    const float *src = isA ? p.A : p.B;
-    const long ld = isA ? p.lda : p.ldb;
-    const int ncols = isA ? p.M : p.N;
-    const int col = min((isA ? i0 : j0) + 4 * cg, ncols - 4);  // clamped columns only feed outputs never stored
-    char *dst = isA ? As : Bs;
-    float4 rv[8];
-    auto load_tiles = [&](long r0) {
-        const bool full = r0 + BK <= rend;              // uniform
-#pragma unroll
-        for (int d = 0; d < 8; ++d) {
-            const long r = r0 + 8 * rg + d;
-            const long rc = (full || r < rend) ? r : rend - 1;
-            rv[d] = *reinterpret_cast<const float4 *>(src + rc * ld + col);
-        }
-        return full;
-    };
-
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-    if (rbeg < rend) {
-        bool full = load_tiles(rbeg);
-        for (long r0 = rbeg; r0 < rend; r0 += BK) {
-            if (!full) {
-#pragma unroll
-                for (int d = 0; d < 8; ++d)
-                    if (r0 + 8 * rg + d >= rend) rv[d] = make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-            split8_store(make_float4(rv[0].x, rv[1].x, rv[2].x, rv[3].x), make_float4(rv[4].x, rv[5].x, rv[6].x, rv[7].x),
-                         dst, PL, x6_off(4 * cg + 0, rg));
-            split8_store(make_float4(rv[0].y, rv[1].y, rv[2].y, rv[3].y), make_float4(rv[4].y, rv[5].y, rv[6].y, rv[7].y),
-                         dst, PL, x6_off(4 * cg + 1, rg));
-            split8_store(make_float4(rv[0].z, rv[1].z, rv[2].z, rv[3].z), make_float4(rv[4].z, rv[5].z, rv[6].z, rv[7].z),
-                         dst, PL, x6_off(4 * cg + 2, rg));
-            split8_store(make_float4(rv[0].w, rv[1].w, rv[2].w, rv[3].w), make_float4(rv[4].w, rv[5].w, rv[6].w, rv[7].w),
-                         dst, PL, x6_off(4 * cg + 3, rg));
-            __syncthreads();
-            if (r0 + BK < rend) full = load_tiles(r0 + BK);
-#pragma unroll
-            for (int kk = 0; kk < BK / 16; ++kk) {
-                bf16x8_t fa[2][3], fb[2][3];
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int t = 0; t < 3; ++t)
-                        fa[i][t] = *reinterpret_cast<const bf16x8_t *>(As + t * PL + x6_off(wm * 64 + i * 32 + r32, 2 * kk + h));
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int t = 0; t < 3; ++t)
-                        fb[j][t] = *reinterpret_cast<const bf16x8_t *>(Bs + t * PL + x6_off(wn * 64 + j * 32 + r32, 2 * kk + h));
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][2], fb[j][0], acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[j][2], acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][1], fb[j][1], acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][1], fb[j][0], acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[j][1], acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[j][0], acc[i][j], 0, 0, 0);
-                    }
-            }
-            __syncthreads();
-        }
-    }
-
-    // slab[z][i][j]: i = i0 + wm*64 + it*32 + (e&3) + 8*(e>>2) + 4h ; j = j0 + wn*64 + jt*32 + r32
-    float *slab = p.slab + (long)bz * p.M * p.N;
-    // (16-byte pieces through LDS as in the NT kernel were measured here too: no difference -- tools/scratch/ab_tn_out.sh)
-#pragma unroll
-    for (int it = 0; it < 2; ++it)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int i = i0 + wm * 64 + it * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-            if (i >= p.M) continue;
-#pragma unroll
-            for (int jt = 0; jt < 2; ++jt) {
-                const int j = j0 + wn * 64 + jt * 32 + r32;
-                if (j < p.N) slab[(long)i * p.N + j] = acc[it][jt][e];
-            }
-        }
-}
-
-// The TN product as a SOFTWARE PIPELINE (round 6).  gemm_tn_x6_kernel stores a step of 32 rows into LDS, waits at a barrier,
-// multiplies, waits again.  Here a stage is 16 reduction rows (one MFMA's depth), LDS holds TWO stages and every wave splits and
-// stores stage s + 1 while the matrix pipe works through the MFMAs it has issued for stage s (sched_group_barrier interleaves
-// them: no branch inside a stage, clamped stage numbers instead); raw operands arrive two stages ahead in two register sets; ONE
-// barrier per stage.  5-9 % faster than the two-barrier kernel on the large weight-gradient products (predictor 3072 x 256 over
-// 7424 rows: 83 against 91 us; CPC-large 6144 x 512: 287 against 305), equal on the small ones (profiles/r06_x6_sweep.md).
+// TN product on the bf16 pipe (same three-term split as gemm_nt_x6_kernel), as a SOFTWARE PIPELINE (round 6).  A stage is 16
+// reduction rows (one MFMA's depth), LDS holds TWO stages and every wave splits and stores stage s + 1 while the matrix pipe works
+// through the MFMAs it has issued for stage s (sched_group_barrier interleaves them: no branch inside a stage, clamped stage numbers
+// instead); raw operands arrive two stages ahead in two register sets; ONE barrier per stage.  5-9 % faster than the two-barrier
+// kernel of rounds 1-5 (32 rows per step, a barrier before and after the MFMAs) on the large weight-gradient products (predictor
+// 3072 x 256 over 7424 rows: 83 against 91 us; CPC-large 6144 x 512: 287 against 305), equal on the small ones
+// (profiles/r06_x6_sweep.md).
 // The loader transposes while it splits: waves 0, 1 stage A, waves 2, 3 stage B; a thread takes an 8 (r) x 2 (columns) micro tile
 // (eight 8-byte loads; a wave's load covers 256 contiguous bytes of two rows) and writes, per column, its 8 consecutive r as one
 // 16-byte chunk per plane.
@@ -1032,6 +851,7 @@ __global__ __launch_bounds__(256, 3) void gemm_tn_x6p_kernel(GemmTNArgs p)
 }
 
 // out = sum over slabs; optional Conv1d weight re-layout (column jj*cin+ci -> [ci][jj])
+// (the slabs are a few tens of MB that the producing kernel has just written: a latency-bound pass, not a bandwidth-bound one)
 __global__ void gemm_tn_reduce_kernel(const float *slab, int S, int M, int N, float *C, long ldc, int conv_cin, int conv_k)
 {
     const long total = (long)M * N;
@@ -1084,8 +904,6 @@ static int tn_splits(int M, int N, long R, long *chunk_out)
 {
     const long tiles = cdiv(M, BM) * cdiv(N, BN);
     long S = 768 / tiles;                     // one full wave of 3 workgroups per CU (256 CUs)
-    static const char *splits_env = getenv("CPC_GEMM_TN_SPLITS");     // (tools/x6_sweep.py)
-    if (splits_env != nullptr) S = std::max(1, atoi(splits_env));
     const long max_s = cdiv(R, 4 * BK);      // at least 128 rows per split
     if (S > max_s) S = max_s;
     if (S < 1) S = 1;
@@ -1122,15 +940,10 @@ int gemm_tn(const float *A, long lda, const float *B, long ldb, float *C, long l
     a.aligned = (M % 4 == 0) && (N % 4 == 0) && (M >= 4) && (N >= 4) && (lda % 4 == 0) && (ldb % 4 == 0) &&
                 ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) % 16 == 0);
     dim3 grid((unsigned)cdiv(N, BN), (unsigned)cdiv(M, BM), (unsigned)S);
-    static const bool no_remap = getenv("CPC_GEMM_NO_XCD") != nullptr;
-    a.xcd_remap = (!no_remap && S % 8 == 0 && grid.x * grid.y > 1) ? 1 : 0;
-    static const bool log_shapes = getenv("CPC_GEMM_LOG") != nullptr;
-    if (log_shapes) fprintf(stderr, "cpc_gemm tn M=%d N=%d R=%ld lda=%ld ldb=%ld ldc=%ld tile=128x128 grid=%ld splits=%d chunk=%ld kernel=%s\n", M, N, R, lda, ldb,
-                            ldc, cdiv(N, BN) * cdiv(M, BM), S, chunk, a.aligned ? "x6" : "f32");
+    a.xcd_remap = (S % 8 == 0 && grid.x * grid.y > 1) ? 1 : 0;
     ProfScope prof(PROF_GEMM_TN, st);
     const bool native = g_gemm_mode.load() == 1;
-    if (a.aligned && !native && x6_pipelined()) hipLaunchKernelGGL(gemm_tn_x6p_kernel, grid, dim3(256), 0, st, a);
-    else if (a.aligned && !native) hipLaunchKernelGGL(gemm_tn_x6_kernel, grid, dim3(256), 0, st, a);
+    if (a.aligned && !native) hipLaunchKernelGGL(gemm_tn_x6p_kernel, grid, dim3(256), 0, st, a);
     else if (a.aligned) hipLaunchKernelGGL(gemm_tn_kernel<true>, grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL(gemm_tn_kernel<false>, grid, dim3(256), 0, st, a);
     CPC_CHECK_LAUNCH("gemm_tn_kernel");

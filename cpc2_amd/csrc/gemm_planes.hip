@@ -76,8 +76,6 @@ struct PlanesNTArgs {
     float *slabs;                                 // K split: partial product of blockIdx.y -> slabs + blockIdx.y * slab_rows * N
     long slab_rows;                               // output rows (after the row map)
     PlanesNormOut norm;                           // NORM kernels only (N == 256, no K split)
-    int dbg;                                      // probes: 1 no loads after the prologue, 2 no MFMAs, 8 clock stamps, 16 half the A requests, 32 a third fewer fragment reads
-    unsigned long long *stamps;                   // dbg & 8: [workgroup][8] = memtime, memrealtime at loop start and end, ...
 };
 
 // chunk index of K step ks, row q = 0
@@ -139,12 +137,8 @@ template <int Q> __device__ __forceinline__ void mma2(f32x16 &c0, f32x16 &c1, co
 // TERMS = 6: the exact product.  TERMS = 3 (cpc_gemm_set_mode(2), opt-in): a0 b0 + a0 b1 + a1 b0 only -- 16 bits of product
 // mantissa instead of 24 (TF32, what the reference's convolutions get on its own GPUs by default, keeps 10); the planes are moved
 // as before, the three small products are not multiplied.
-template <int TERMS> __device__ __forceinline__ void mma6(f32x16 &c0, f32x16 &c1, const frag_t (&a)[3], const frag_t (&b)[2][3], bool skip)
+template <int TERMS> __device__ __forceinline__ void mma6(f32x16 &c0, f32x16 &c1, const frag_t (&a)[3], const frag_t (&b)[2][3])
 {
-    if (skip) {
-        asm volatile("" ::"v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(b[0][0]), "v"(b[0][1]), "v"(b[0][2]), "v"(b[1][0]), "v"(b[1][1]), "v"(b[1][2]));
-        return;
-    }
     if constexpr (TERMS == 6) { mma2<0>(c0, c1, a, b); mma2<1>(c0, c1, a, b); mma2<2>(c0, c1, a, b); }
     else asm volatile("" ::"v"(a[2]), "v"(b[0][2]), "v"(b[1][2]));
     mma2<3>(c0, c1, a, b); mma2<4>(c0, c1, a, b); mma2<5>(c0, c1, a, b);
@@ -186,11 +180,12 @@ template <int BLK> __device__ __forceinline__ void read_a_pair(frag_t (&a)[3], u
     a[2] = lds_frag<false, (18 + BLK) * PT_PIECE>(fa);
 }
 
-template <int DBG, bool TN, int TERMS = 6, bool NORM = false, bool PAIR = false> __global__ __launch_bounds__(512, 2) void gemm_planes_kernel(PlanesNTArgs p)
+// The leading template argument is always 0 and does nothing: it keeps the kernel's profiled name gemm_planes_kernel<0, ...>, by
+// which bench.py's roofline record and profiles/pmc_traffic.json know it.
+template <int, bool TN, int TERMS = 6, bool NORM = false, bool PAIR = false> __global__ __launch_bounds__(512, 2) void gemm_planes_kernel(PlanesNTArgs p)
 {
     static_assert(!(PAIR && TN), "the pair form is an NT form");
     extern __shared__ __attribute__((aligned(1024))) char lds[];
-    const unsigned long long rentry = (p.dbg & 8) ? __builtin_amdgcn_s_memrealtime() : 0;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 2, wc = wave & 3;
@@ -252,11 +247,6 @@ template <int DBG, bool TN, int TERMS = 6, bool NORM = false, bool PAIR = false>
         b_vo = vo(p.TB, n0);
     }
     const unsigned lds0 = (unsigned)(unsigned long long)lds;
-    constexpr bool noload = (DBG & 1) != 0, nomma = (DBG & 2) != 0;     // probes only
-    // probes with wrong numbers and valid timing: what a lever could win AT MOST, before building it.  DBG & 4: the A pieces of the
-    // odd stages are not requested (the L2 -> LDS traffic of a kernel that stages the A operand of a k = 2s convolution once per
-    // tap pair); DBG & 8: a third of the fragment reads is skipped (the LDS read traffic of 128 x 128 wave tiles)
-    constexpr bool half_a = (DBG & 4) != 0, fewer_reads = (DBG & 8) != 0;
     // stage t -> ring slot at byte offset `slot`: six pieces per wave, piece i of the stage requested by issue1<i>
     struct Src { unsigned dst; const char *ab, *bb; };
     auto stage_src = [&](int t, unsigned slot) {
@@ -279,8 +269,7 @@ template <int DBG, bool TN, int TERMS = 6, bool NORM = false, bool PAIR = false>
     auto issue = [&](int t, unsigned slot) {
         const Src q = stage_src(t, slot);
 #pragma unroll
-        for (int i = 0; i < 6; ++i)
-            if (!(half_a && (t & 1) && i < 3)) issue1(q, i);
+        for (int i = 0; i < 6; ++i) issue1(q, i);
     };
 
     f32x16 acc[4][2];
@@ -346,23 +335,23 @@ template <int DBG, bool TN, int TERMS = 6, bool NORM = false, bool PAIR = false>
         // the MFMAs of this row block 3, the B pieces two at a time behind row blocks 0, 1, 2 of the next half (d + 1's first one).
         auto half = [&](int d, unsigned fa, unsigned fan, unsigned fbn, frag_t (&bc)[2][3], frag_t (&bn)[2][3], const bool last) {
             // first half of double stage d >= 1: the B pieces of double stage d + 1 (its A pieces went out in front of this half)
-            const bool breq = !last && d >= 1 && d + 1 < nds && !noload;
+            const bool breq = !last && d >= 1 && d + 1 < nds;
             const SrcP qb = src_pair(breq ? d + 1 : 0, slot == 0 ? PP_DS : 0);
             read_a_pair<1>(ay, fa);
             PT_SB;
-            mma6<TERMS>(acc[0][0], acc[0][1], ax, bc, nomma);
+            mma6<TERMS>(acc[0][0], acc[0][1], ax, bc);
             PT_SB;
             if (breq) { issue_p(qb, 3); issue_p(qb, 4); } PT_SB;
             lds_wait3(ay);
             read_a_pair<2>(ax, fa);
             PT_SB;
-            mma6<TERMS>(acc[1][0], acc[1][1], ay, bc, nomma);
+            mma6<TERMS>(acc[1][0], acc[1][1], ay, bc);
             PT_SB;
             if (breq) { issue_p(qb, 5); issue_p(qb, 6); } PT_SB;
             lds_wait3(ax);
             read_a_pair<3>(ay, fa);
             PT_SB;
-            mma6<TERMS>(acc[2][0], acc[2][1], ax, bc, nomma);
+            mma6<TERMS>(acc[2][0], acc[2][1], ax, bc);
             PT_SB;
             if (breq) { issue_p(qb, 7); issue_p(qb, 8); } PT_SB;
             lds_wait3(ay);
@@ -371,36 +360,29 @@ template <int DBG, bool TN, int TERMS = 6, bool NORM = false, bool PAIR = false>
             if (last) {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's pieces of double stage d + 1 (all it has in flight)
                 __builtin_amdgcn_s_barrier();                         // d + 1 has landed for everyone; everyone has read all of d
-                req = d + 2 < nds && !noload;
+                req = d + 2 < nds;
                 if (req) q = src_pair(d + 2, slot);
             }
-            if (!nomma && TERMS == 6) { mma2<0>(acc[3][0], acc[3][1], ay, bc); } PT_SB;
+            if (TERMS == 6) { mma2<0>(acc[3][0], acc[3][1], ay, bc); } PT_SB;
             bn[0][0] = lds_frag<false, 0>(fbn); bn[0][1] = lds_frag<false, 8 * PT_PIECE>(fbn); bn[0][2] = lds_frag<false, 16 * PT_PIECE>(fbn); PT_SB;
-            if (!nomma && TERMS == 6) { mma2<1>(acc[3][0], acc[3][1], ay, bc); } PT_SB;
+            if (TERMS == 6) { mma2<1>(acc[3][0], acc[3][1], ay, bc); } PT_SB;
             bn[1][0] = lds_frag<false, PT_PIECE>(fbn); bn[1][1] = lds_frag<false, 9 * PT_PIECE>(fbn); bn[1][2] = lds_frag<false, 17 * PT_PIECE>(fbn); PT_SB;
-            if (!nomma && TERMS == 6) { mma2<2>(acc[3][0], acc[3][1], ay, bc); } PT_SB;
+            if (TERMS == 6) { mma2<2>(acc[3][0], acc[3][1], ay, bc); } PT_SB;
             read_a_pair<0>(ax, fan); PT_SB;
             if (req) { issue_p(q, 0); issue_p(q, 9); } PT_SB;
-            if (!nomma) { mma2<3>(acc[3][0], acc[3][1], ay, bc); } PT_SB;
+            mma2<3>(acc[3][0], acc[3][1], ay, bc); PT_SB;
             if (req) { issue_p(q, 1); } PT_SB;
-            if (!nomma) { mma2<4>(acc[3][0], acc[3][1], ay, bc); } PT_SB;
+            mma2<4>(acc[3][0], acc[3][1], ay, bc); PT_SB;
             if (req) { issue_p(q, 2); } PT_SB;
-            if (!nomma) { mma2<5>(acc[3][0], acc[3][1], ay, bc); } PT_SB;
+            mma2<5>(acc[3][0], acc[3][1], ay, bc); PT_SB;
             lds_wait9(ax, bn);
         };
 #undef PT_SB
-        unsigned long long c0 = 0, r0 = 0;
-        if (p.dbg & 8) { c0 = __builtin_amdgcn_s_memtime(); r0 = __builtin_amdgcn_s_memrealtime(); }
         for (int d = 0; d < nds; ++d) {
             const unsigned nslot = slot == 0 ? PP_DS : 0;
             half(d, fa_b + slot, fs_b + slot, fj_b + slot + 24 * PT_PIECE, b0, b1, false);
             half(d, fs_b + slot, fa_b + nslot, fj_b + nslot, b1, b0, true);
             slot = nslot;
-        }
-        if ((p.dbg & 8) && tid == 0) {
-            p.stamps[blockIdx.x * 8 + 0] = c0; p.stamps[blockIdx.x * 8 + 1] = r0;
-            p.stamps[blockIdx.x * 8 + 2] = __builtin_amdgcn_s_memtime(); p.stamps[blockIdx.x * 8 + 3] = __builtin_amdgcn_s_memrealtime();
-            p.stamps[blockIdx.x * 8 + 4] = rentry;
         }
     } else {
     // fragment addresses inside a stage: A piece (plane, block wr * 4 + i), B piece 24 + (plane, block wc * 2 + j)
@@ -413,11 +395,9 @@ template <int DBG, bool TN, int TERMS = 6, bool NORM = false, bool PAIR = false>
     issue(1, PT_STAGE);
     if (nst > 2) {
         issue(2, 2 * PT_STAGE);
-        if constexpr (half_a) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+        asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
     } else {
-        if constexpr (half_a) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
     }
     __builtin_amdgcn_s_barrier();
     frag_t b0[2][3], b1[2][3], ax[3], ay[3];
@@ -432,63 +412,53 @@ template <int DBG, bool TN, int TERMS = 6, bool NORM = false, bool PAIR = false>
     //  costs the SIMD's matrix pipe ~60 cycles whichever wave issues it.)
     unsigned slot = 0;                                                   // ring slot of stage t (byte offset)
 #define PT_SB __builtin_amdgcn_sched_barrier(0)
-    auto stage = [&](int t, frag_t (&bc)[2][3], frag_t (&bn)[2][3], const bool odd) {
+    auto stage = [&](int t, frag_t (&bc)[2][3], frag_t (&bn)[2][3]) {
         const unsigned fa = fa0 + slot;
         const unsigned nslot = slot == (PT_RING - 1) * PT_STAGE ? 0 : slot + PT_STAGE;
         read_a<TN, 1>(ay, fa);
         PT_SB;
-        mma6<TERMS>(acc[0][0], acc[0][1], ax, bc, nomma);
+        mma6<TERMS>(acc[0][0], acc[0][1], ax, bc);
         PT_SB;
         lds_wait3(ay);
         read_a<TN, 2>(ax, fa);
         PT_SB;
-        mma6<TERMS>(acc[1][0], acc[1][1], ay, bc, nomma);
+        mma6<TERMS>(acc[1][0], acc[1][1], ay, bc);
         PT_SB;
         lds_wait3(ax);
-        if constexpr (!fewer_reads) read_a<TN, 3>(ay, fa);
+        read_a<TN, 3>(ay, fa);
         PT_SB;
-        mma6<TERMS>(acc[2][0], acc[2][1], ax, bc, nomma);
+        mma6<TERMS>(acc[2][0], acc[2][1], ax, bc);
         PT_SB;
         lds_wait3(ay);                          // every LDS read of stage t by this wave is done
         // (no branch may enclose an asm LDS read: hipcc would copy its destination registers at the join, before the wait)
-        if (t + 2 < nst && !noload) {
-            if (half_a && odd) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");       // (stage t + 2 stays in flight: odd like t, three pieces)
-            else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        } else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (t + 2 < nst) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();          // stage t + 1 has landed for everyone; everyone has read all of stage t
         // row block 3, with the requests for stage t + 3 and the reads of stage t + 1's first fragments BETWEEN its MFMAs:
         // the eight waves leave the barrier together, and an LDS-DMA piece holds a wave's issue for ~100 cycles
-        const bool req = t + 3 < nst && !noload;
+        const bool req = t + 3 < nst;
         const Src q = stage_src(req ? t + 3 : t, slot);
         const unsigned fbn = fb0 + nslot, fan = fa0 + nslot;
-        if (!nomma && TERMS == 6) { mma2<0>(acc[3][0], acc[3][1], ay, bc); } PT_SB;
+        if (TERMS == 6) { mma2<0>(acc[3][0], acc[3][1], ay, bc); } PT_SB;
         bn[0][0] = lds_frag<TN, 0>(fbn); bn[0][1] = lds_frag<TN, 8 * PT_PIECE>(fbn); bn[0][2] = lds_frag<TN, 16 * PT_PIECE>(fbn); PT_SB;
-        if (!nomma && TERMS == 6) { mma2<1>(acc[3][0], acc[3][1], ay, bc); } PT_SB;
-        if constexpr (!fewer_reads) { bn[1][0] = lds_frag<TN, PT_PIECE>(fbn); bn[1][1] = lds_frag<TN, 9 * PT_PIECE>(fbn); bn[1][2] = lds_frag<TN, 17 * PT_PIECE>(fbn); } PT_SB;
-        if (!nomma && TERMS == 6) { mma2<2>(acc[3][0], acc[3][1], ay, bc); } PT_SB;
+        if (TERMS == 6) { mma2<1>(acc[3][0], acc[3][1], ay, bc); } PT_SB;
+        bn[1][0] = lds_frag<TN, PT_PIECE>(fbn); bn[1][1] = lds_frag<TN, 9 * PT_PIECE>(fbn); bn[1][2] = lds_frag<TN, 17 * PT_PIECE>(fbn); PT_SB;
+        if (TERMS == 6) { mma2<2>(acc[3][0], acc[3][1], ay, bc); } PT_SB;
         read_a<TN, 0>(ax, fan); PT_SB;
-        if (req && !(half_a && !odd)) { issue1(q, 0); issue1(q, 1); } PT_SB;      // (stage t + 3 is odd when t is even)
-        if (!nomma) { mma2<3>(acc[3][0], acc[3][1], ay, bc); } PT_SB;
-        if (req) { if (!(half_a && !odd)) issue1(q, 2); issue1(q, 3); } PT_SB;
-        if (!nomma) { mma2<4>(acc[3][0], acc[3][1], ay, bc); } PT_SB;
+        if (req) { issue1(q, 0); issue1(q, 1); } PT_SB;
+        mma2<3>(acc[3][0], acc[3][1], ay, bc); PT_SB;
+        if (req) { issue1(q, 2); issue1(q, 3); } PT_SB;
+        mma2<4>(acc[3][0], acc[3][1], ay, bc); PT_SB;
         if (req) { issue1(q, 4); issue1(q, 5); } PT_SB;
-        if (!nomma) { mma2<5>(acc[3][0], acc[3][1], ay, bc); } PT_SB;
+        mma2<5>(acc[3][0], acc[3][1], ay, bc); PT_SB;
         lds_wait9(ax, bn);
         slot = nslot;
     };
 #undef PT_SB
-    unsigned long long c0 = 0, r0 = 0;
-    if (p.dbg & 8) { c0 = __builtin_amdgcn_s_memtime(); r0 = __builtin_amdgcn_s_memrealtime(); }
     for (int t = 0; t < nst; t += 2) {
-        stage(t, b0, b1, false);
-        stage(t + 1, b1, b0, true);
+        stage(t, b0, b1);
+        stage(t + 1, b1, b0);
     }
-    if ((p.dbg & 8) && tid == 0) {
-        p.stamps[blockIdx.x * 8 + 0] = c0; p.stamps[blockIdx.x * 8 + 1] = r0;
-        p.stamps[blockIdx.x * 8 + 2] = __builtin_amdgcn_s_memtime(); p.stamps[blockIdx.x * 8 + 3] = __builtin_amdgcn_s_memrealtime();
-        p.stamps[blockIdx.x * 8 + 4] = rentry;
-    }
-
     }
 
     // ---- epilogue: acc[i][j][e] is C[m][n], m = m0 + wr*128 + i*32 + (e&3) + 8*(e>>2) + 4h, n = n0 + wc*64 + j*32 + r32.
@@ -588,7 +558,7 @@ template <int DBG, bool TN, int TERMS = 6, bool NORM = false, bool PAIR = false>
                 const long gf = mf / rv, tf = mf - gf * rv;
                 const long R = gf * p.norm.rows_next + p.norm.halo + tf;
                 const long rowchunk = (R & smask) * p.norm.rts + (R >> sh);
-                if (mf < p.M && !(p.dbg & 64)) {
+                if (mf < p.M) {
 #pragma unroll
                     for (int k = 0; k < 12; ++k) {
                         const int pl = k >> 2, pch = k & 3;
@@ -615,10 +585,6 @@ template <int DBG, bool TN, int TERMS = 6, bool NORM = false, bool PAIR = false>
             t += 4;
             while (t >= rv) { t -= rv; ++g; }
         }
-    }
-    if (p.dbg & 8) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (tid == 0) p.stamps[blockIdx.x * 8 + 5] = __builtin_amdgcn_s_memrealtime();
     }
 }
 
@@ -689,8 +655,6 @@ int split_planes(const float *x, long ld, long rows, int cols, bf16_t *planes, l
     return CPC_OK;
 }
 
-__global__ void planes_tn_reduce_kernel(const float *slab, int S, int M, int N, float *C, long ldc, int conv_cin, int conv_k);
-
 bool gemm_nt_planes_ok(long M, int N, int K)
 {
     return N % PT_BN == 0 && K % (2 * PT_BK) == 0 && K >= 4 * PT_BK && M >= 1;
@@ -729,20 +693,20 @@ bool gemm_nt_planes_norm_ok(long M, int N, int K)
 }
 
 // one instantiation: dynamic LDS attribute (once), launch
-template <int DBG, bool TN, int TERMS, bool NORM, bool PAIR> static int launch_planes(dim3 grid, const PlanesNTArgs &a, hipStream_t st,
+template <bool TN, int TERMS, bool NORM, bool PAIR> static int launch_planes(dim3 grid, const PlanesNTArgs &a, hipStream_t st,
                                                                                        hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr)
 {
     constexpr int bytes = PAIR ? PP_LDS : PT_LDS;
     static bool attr_set = false;
     if (!attr_set) {
-        CPC_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_planes_kernel<DBG, TN, TERMS, NORM, PAIR>),
+        CPC_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_planes_kernel<0, TN, TERMS, NORM, PAIR>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
         attr_set = true;
     }
     if (ev_start != nullptr)       // (in-situ timing: the events of the dispatch itself, no barrier packets on the stream)
-        hipExtLaunchKernelGGL((gemm_planes_kernel<DBG, TN, TERMS, NORM, PAIR>), grid, dim3(512), bytes, st, ev_start, ev_stop, 0, a);
+        hipExtLaunchKernelGGL((gemm_planes_kernel<0, TN, TERMS, NORM, PAIR>), grid, dim3(512), bytes, st, ev_start, ev_stop, 0, a);
     else
-        hipLaunchKernelGGL((gemm_planes_kernel<DBG, TN, TERMS, NORM, PAIR>), grid, dim3(512), bytes, st, a);
+        hipLaunchKernelGGL((gemm_planes_kernel<0, TN, TERMS, NORM, PAIR>), grid, dim3(512), bytes, st, a);
     return CPC_OK;
 }
 
@@ -762,8 +726,7 @@ int gemm_nt_planes(const PlanesOperand &A, const PlanesOperand &B, float *C, lon
     a.C = C; a.ldc = ldc; a.bias = bias; a.M = M; a.N = N; a.K = K; a.map = map;
     if (norm != nullptr) a.norm = *norm;
     a.tiles_m = (int)cdiv(M, PT_BM); a.tiles_n = N / PT_BN;
-    static const bool no_remap = getenv("CPC_GEMM_NO_XCD") != nullptr;
-    a.xcd_remap = (!no_remap && a.tiles_n > 1 && a.tiles_m % 8 == 0) ? 1 : 0;
+    a.xcd_remap = (a.tiles_n > 1 && a.tiles_m % 8 == 0) ? 1 : 0;
     a.kchunk = K; a.slabs = nullptr; a.slab_rows = 0;
     // few tiles and a K long enough: split K over blockIdx.y (one workgroup per CU), partial products to slabs that a
     // second kernel adds in a fixed order -- when the caller lent the room (RowMap::splitk_scratch)
@@ -779,13 +742,6 @@ int gemm_nt_planes(const PlanesOperand &A, const PlanesOperand &B, float *C, lon
             a.slab_rows = out_rows;
         }
     }
-    static const int dbg_env = getenv("CPC_PLANES_DBG") ? atoi(getenv("CPC_PLANES_DBG")) : 0;
-    a.dbg = dbg_env;
-    static unsigned long long *stamps = nullptr;
-    if (a.dbg & 8) {
-        if (stamps == nullptr) CPC_CHECK_HIP(hipMalloc(&stamps, 65536 * 8 * sizeof(unsigned long long)));
-        a.stamps = stamps;
-    }
     const long blocks = (long)a.tiles_m * a.tiles_n;
     // the pair form (A staged once per tap pair): an operand with tap pairs whose tiles do not straddle samples
     static const bool no_pair = getenv("CPC_PLANES_NO_PAIR") != nullptr;
@@ -795,22 +751,14 @@ int gemm_nt_planes(const PlanesOperand &A, const PlanesOperand &B, float *C, lon
     const hipEvent_t e0 = prof.start(), e1 = prof.stop();
     int rc = CPC_OK;
     const int mode3 = gemm_mode() == 2;
-    const int sel = (a.dbg & 48) ? ((a.dbg & 48) >> 2) : (a.dbg & 3);                 // DBG template value of the probes
     if (pair) {
-        if (sel == 1) rc = launch_planes<1, false, 6, false, true>(grid, a, st, e0, e1);
-        else if (sel == 2) rc = launch_planes<2, false, 6, false, true>(grid, a, st, e0, e1);
-        else if (norm != nullptr) rc = launch_planes<0, false, 6, true, true>(grid, a, st, e0, e1);
-        else if (mode3) rc = launch_planes<0, false, 3, false, true>(grid, a, st, e0, e1);
-        else rc = launch_planes<0, false, 6, false, true>(grid, a, st, e0, e1);
+        if (norm != nullptr) rc = launch_planes<false, 6, true, true>(grid, a, st, e0, e1);
+        else if (mode3) rc = launch_planes<false, 3, false, true>(grid, a, st, e0, e1);
+        else rc = launch_planes<false, 6, false, true>(grid, a, st, e0, e1);
     } else {
-        if (sel == 4) rc = launch_planes<4, false, 6, false, false>(grid, a, st, e0, e1);
-        else if (sel == 8) rc = launch_planes<8, false, 6, false, false>(grid, a, st, e0, e1);
-        else if (sel == 12) rc = launch_planes<12, false, 6, false, false>(grid, a, st, e0, e1);
-        else if (sel == 1) rc = launch_planes<1, false, 6, false, false>(grid, a, st, e0, e1);
-        else if (sel == 2) rc = launch_planes<2, false, 6, false, false>(grid, a, st, e0, e1);
-        else if (norm != nullptr) rc = launch_planes<0, false, 6, true, false>(grid, a, st, e0, e1);
-        else if (mode3) rc = launch_planes<0, false, 3, false, false>(grid, a, st, e0, e1);
-        else rc = launch_planes<0, false, 6, false, false>(grid, a, st, e0, e1);
+        if (norm != nullptr) rc = launch_planes<false, 6, true, false>(grid, a, st, e0, e1);
+        else if (mode3) rc = launch_planes<false, 3, false, false>(grid, a, st, e0, e1);
+        else rc = launch_planes<false, 6, false, false>(grid, a, st, e0, e1);
     }
     if (rc != CPC_OK) { prof.cancel(); return rc; }
     CPC_CHECK_LAUNCH("gemm_planes_kernel (nt)");
@@ -818,84 +766,25 @@ int gemm_nt_planes(const PlanesOperand &A, const PlanesOperand &B, float *C, lon
         *left_slabs = splits;
     } else if (splits > 1) {
         const long total = a.slab_rows * N;
-        hipLaunchKernelGGL(planes_tn_reduce_kernel, dim3((unsigned)std::min<long>(cdiv(total / 4, 256), 4096)), dim3(256), 0, st, a.slabs, splits,
+        hipLaunchKernelGGL(gemm_tn_reduce_kernel, dim3((unsigned)std::min<long>(cdiv(total / 4, 256), 4096)), dim3(256), 0, st, a.slabs, splits,
                            (int)a.slab_rows, N, C, ldc, 0, 0);
         CPC_CHECK_LAUNCH("planes split-K reduce");
     }
-    if (a.dbg & 8) {
-        static unsigned long long host[65536 * 8];
-        CPC_CHECK_HIP(hipStreamSynchronize(st));
-        const long nb = std::min<long>(blocks, 65536);
-        CPC_CHECK_HIP(hipMemcpy(host, stamps, nb * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        double cyc = 0, real = 0, pro = 0, epi = 0;
-        unsigned long long first = ~0ull, last = 0;
-        for (long i = 0; i < nb; ++i) {
-            cyc += (double)(host[i * 8 + 2] - host[i * 8]); real += (double)(host[i * 8 + 3] - host[i * 8 + 1]);
-            pro += (double)(host[i * 8 + 1] - host[i * 8 + 4]); epi += (double)(host[i * 8 + 5] - host[i * 8 + 3]);
-            first = std::min(first, host[i * 8 + 4]); last = std::max(last, host[i * 8 + 5]);
-        }
-        fprintf(stderr, "planes stamps: %ld tiles, loop %.0f cycles = %.2f us per tile, clock %.3f GHz; prologue %.2f us, epilogue %.2f us, kernel span %.1f us\n",
-                nb, cyc / nb, real / nb * 0.01, cyc / real * 0.1, pro / nb * 0.01, epi / nb * 0.01, (double)(last - first) * 0.01);
-    }
     return CPC_OK;
-}
-
-// out = sum over slabs, in slab order (bitwise reproducible); optional Conv1d weight re-layout (column jj*cin+ci -> [ci][jj])
-// (four output elements per thread, 16-byte loads, four slabs in flight: the slabs are a few tens of MB that the producing
-//  kernel has just written -- this is a latency-bound pass, not a bandwidth-bound one)
-__global__ void planes_tn_reduce_kernel(const float *slab, int S, int M, int N, float *C, long ldc, int conv_cin, int conv_k)
-{
-    const long total4 = (long)M * N / 4;                       // N % 256 == 0
-    const float4 *s4 = reinterpret_cast<const float4 *>(slab);
-    for (long i4 = (long)blockIdx.x * blockDim.x + threadIdx.x; i4 < total4; i4 += (long)gridDim.x * blockDim.x) {
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-        int z = 0;
-        for (; z + 4 <= S; z += 4) {                            // fixed order: slab 0, 1, 2, ... (bitwise reproducible)
-            const float4 v0 = s4[(long)z * total4 + i4], v1 = s4[(long)(z + 1) * total4 + i4];
-            const float4 v2 = s4[(long)(z + 2) * total4 + i4], v3 = s4[(long)(z + 3) * total4 + i4];
-            acc.x += v0.x; acc.y += v0.y; acc.z += v0.z; acc.w += v0.w;
-            acc.x += v1.x; acc.y += v1.y; acc.z += v1.z; acc.w += v1.w;
-            acc.x += v2.x; acc.y += v2.y; acc.z += v2.z; acc.w += v2.w;
-            acc.x += v3.x; acc.y += v3.y; acc.z += v3.z; acc.w += v3.w;
-        }
-        for (; z < S; ++z) {
-            const float4 v = s4[(long)z * total4 + i4];
-            acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-        }
-        const long idx = i4 * 4;
-        const int i = (int)(idx / N), j = (int)(idx - (long)i * N);
-        if (conv_cin > 0) {                                     // conv_cin % 4 == 0: the four elements share the tap
-            const int jj = j / conv_cin, ci = j - jj * conv_cin;
-            float *dst = C + (long)i * conv_cin * conv_k + (long)ci * conv_k + jj;
-            dst[0] = acc.x; dst[conv_k] = acc.y; dst[2 * conv_k] = acc.z; dst[3 * conv_k] = acc.w;
-        } else {
-            float *dst = C + (long)i * ldc + j;
-            dst[0] = acc.x; dst[1] = acc.y; dst[2] = acc.z; dst[3] = acc.w;
-        }
-    }
 }
 
 // slabs of `chunk` reduction rows: as many as give every CU one workgroup in ONE round.  *slots_out = the grid's z: the slab count
 // padded to a multiple of 8, so that all tiles of a slab share an XCD (gemm_planes_kernel, xcd_remap) whatever the count -- the
 // padding slots' workgroups leave at once.  (Rounds 2-5 looked for a chunk whose slab count WAS a multiple of 8: conv3's weight
 // gradient then ran as 4 x 40 = 160 workgroups of 52 stages on 256 CUs, conv4's as 192 of 22, conv2's as 224 of 74; now 244 of
-// 34, 232 of 18, 252 of 66.  CPC_PLANES_TN_OLD_SPLITS=1 keeps the old rule for A/B runs.)
+// 34, 232 of 18, 252 of 66.)
 static int tn_planes_splits(int M, int N, long R, long *chunk_out, int *slots_out = nullptr)
 {
     const long tiles = (long)(M / PT_BM) * (N / PT_BN);
     const long Rp = cdiv(R, 32) * 32;
     long S = std::max<long>(1, (256 + tiles / 2) / tiles);            // one workgroup per CU, one round
     S = std::min(S, std::max<long>(1, Rp / 128));
-    long chunk = cdiv(cdiv(Rp, S), 32) * 32;
-    static const bool old_rule = getenv("CPC_PLANES_TN_OLD_SPLITS") != nullptr;
-    if (old_rule) {
-        if (S >= 8 && tiles > 1)
-            for (long c = chunk; c <= chunk + 32 * 16; c += 32)
-                if (cdiv(Rp, c) % 8 == 0) { chunk = c; break; }
-        *chunk_out = chunk;
-        if (slots_out != nullptr) *slots_out = (int)cdiv(Rp, chunk);
-        return (int)cdiv(Rp, chunk);
-    }
+    const long chunk = cdiv(cdiv(Rp, S), 32) * 32;
     const long slabs = cdiv(Rp, chunk);
     *chunk_out = chunk;
     if (slots_out != nullptr) *slots_out = (int)((slabs >= 8 && tiles > 1) ? cdiv(slabs, 8) * 8 : slabs);
@@ -934,13 +823,11 @@ int gemm_tn_planes(const PlanesTNOperand &A, const PlanesTNOperand &B, float *C,
     a.R = cdiv(R, 32) * 32;            // rows R .. of A are zero (caller), of B finite
     a.rchunk = chunk;
     a.M = M; a.N = N; a.K = 0; a.slabs = static_cast<float *>(scratch);
-    a.dbg = 0;
-    static const bool no_remap = getenv("CPC_GEMM_NO_XCD") != nullptr;
-    a.xcd_remap = (!no_remap && slots % 8 == 0 && (M / PT_BM) * (N / PT_BN) > 1) ? 1 : 0;
+    a.xcd_remap = (slots % 8 == 0 && (M / PT_BM) * (N / PT_BN) > 1) ? 1 : 0;
     {
         ProfScope prof(PROF_PLANES_TN, st);
         const dim3 grid((unsigned)(N / PT_BN), (unsigned)(M / PT_BM), (unsigned)slots);
-        const int rc = gemm_mode() == 2 ? launch_planes<0, true, 3, false, false>(grid, a, st) : launch_planes<0, true, 6, false, false>(grid, a, st);
+        const int rc = gemm_mode() == 2 ? launch_planes<true, 3, false, false>(grid, a, st) : launch_planes<true, 6, false, false>(grid, a, st);
         if (rc != CPC_OK) return rc;
     }
     CPC_CHECK_LAUNCH("gemm_planes_kernel (tn)");
@@ -954,9 +841,9 @@ int gemm_tn_planes(const PlanesTNOperand &A, const PlanesTNOperand &B, float *C,
 int planes_tn_reduce(const float *slabs, int S, int M, int N, float *C, long ldc, int conv_cin, int conv_k, hipStream_t st)
 {
     const long total = (long)M * N;
-    hipLaunchKernelGGL(planes_tn_reduce_kernel, dim3((unsigned)std::min<long>(cdiv(total / 4, 256), 2048)), dim3(256), 0, st, slabs, S, M, N, C,
+    hipLaunchKernelGGL(gemm_tn_reduce_kernel, dim3((unsigned)std::min<long>(cdiv(total / 4, 256), 2048)), dim3(256), 0, st, slabs, S, M, N, C,
                        ldc, conv_cin, conv_k);
-    CPC_CHECK_LAUNCH("planes_tn_reduce_kernel");
+    CPC_CHECK_LAUNCH("planes_tn_reduce");
     return CPC_OK;
 }
 

@@ -14,13 +14,6 @@
 #include <algorithm>
 #include <cstdlib>
 
-#ifndef GRU_ABL_F
-#define GRU_ABL_F 8      // probes: K quarters of the slice actually multiplied (forward), of 8
-#endif
-#ifndef GRU_ABL_B
-#define GRU_ABL_B 24     // probes: row quarters multiplied (backward), of 24
-#endif
-
 namespace cpc {
 
 // W_hh [3H][H] -> wf[(k4*3 + g)*H + j] = W[g*H + j][4*k4 .. 4*k4+3]   (forward: thread j, all k)
@@ -217,13 +210,7 @@ struct GruCoopArgs {
     int groups, xcd_map;
     int *err;              // host-visible error word (coop.h), or nullptr
     int fault;             // tests: member 0 of group 0 withholds its publish of step 1
-    unsigned long long *stamps;   // -DGRU_STAMPS builds (probes): [workgroup][8] ticks of 10 ns summed over the steps, per phase
 };
-#ifdef GRU_STAMPS
-#define GRU_STAMP(i) do { const unsigned long long now_ = __builtin_amdgcn_s_memrealtime(); ph[i] += now_ - last_; last_ = now_; } while (0)
-#else
-#define GRU_STAMP(i) do { } while (0)
-#endif
 
 template <int H, int NB> __global__ __launch_bounds__(512) void gru_fwd_coop_kernel(GruCoopArgs ca)
 {
@@ -268,9 +255,6 @@ template <int H, int NB> __global__ __launch_bounds__(512) void gru_fwd_coop_ker
         gin0 = gp[j]; gin1 = gp[H + j]; gin2 = gp[2 * H + j];
     }
     bool dead = false;
-#ifdef GRU_STAMPS
-    unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, last_ = __builtin_amdgcn_s_memrealtime();
-#endif
     for (int t = 0; t < T; ++t) {
         const int cur = t & 1, nxt = cur ^ 1;
         // this lane finishes sample q (if q < NB); its input projections were requested one step ago, the next
@@ -286,7 +270,7 @@ template <int H, int NB> __global__ __launch_bounds__(512) void gru_fwd_coop_ker
         for (int s = 0; s < NB; ++s) {
             f32x2 a2[3] = {f32x2{0.f, 0.f}, f32x2{0.f, 0.f}, f32x2{0.f, 0.f}};    // even / odd columns of the slice
 #pragma unroll
-            for (int i4 = 0; i4 < GRU_ABL_F; ++i4) {
+            for (int i4 = 0; i4 < 8; ++i4) {
                 const float4 h4 = *reinterpret_cast<const float4 *>(&hs[cur][s][q * 36 + 4 * i4]);
 #pragma unroll
                 for (int g = 0; g < 3; ++g)
@@ -295,7 +279,6 @@ template <int H, int NB> __global__ __launch_bounds__(512) void gru_fwd_coop_ker
 #pragma unroll
             for (int g = 0; g < 3; ++g) acc[s][g] = coop_group_sum<QS>(a2[g].x + a2[g].y);
         }
-        GRU_STAMP(0);
         if (q < NB) {
             float g0 = 0.f, g1 = 0.f, g2 = 0.f;
 #pragma unroll
@@ -323,7 +306,6 @@ template <int H, int NB> __global__ __launch_bounds__(512) void gru_fwd_coop_ker
                 a.hall[((long)ns * (T + 1) + t + 1) * H + j] = hv;
             }
         }
-        GRU_STAMP(1);
         // gather the whole new h (all members) into the other LDS buffer; a thread's KP granules are polled together
         // (one L2 round trip per attempt, not KP in a row)
         if (t + 1 < T) {
@@ -346,10 +328,6 @@ template <int H, int NB> __global__ __launch_bounds__(512) void gru_fwd_coop_ker
                     if (++spins > (1u << 22)) { dead = true; coop_report(ca.err, COOP_ERR_FWD_WAIT); break; }
                     __builtin_amdgcn_s_sleep(1);
                 }
-#ifdef GRU_STAMPS
-                ph[4] += spins;
-#endif
-                GRU_STAMP(2);
 #pragma unroll
                 for (int i = 0; i < KP; ++i) {
                     const int idx = tid + 512 * i;
@@ -359,13 +337,8 @@ template <int H, int NB> __global__ __launch_bounds__(512) void gru_fwd_coop_ker
                 }
             }
             coop_lds_barrier();            // `dead` stays with the thread that timed out: what it gathered is poisoned above
-            GRU_STAMP(3);
         }
     }
-#ifdef GRU_STAMPS
-    if (ca.stamps != nullptr && (tid == 0 || tid == 511))
-        for (int i = 0; i < 5; ++i) ca.stamps[(blockIdx.x * 2 + (tid != 0)) * 8 + i] = ph[i];
-#endif
     if (a.hlast != nullptr && q < NB && n0 + q < a.N)
         a.hlast[(long)(n0 + q) * H + j] = a.hall[((long)(n0 + q) * (T + 1) + T) * H + j];
 }
@@ -488,9 +461,6 @@ template <int H, int NB> __global__ __launch_bounds__(512) void gru_fwd_mfma_ker
 #pragma unroll
     for (int g = 0; g < 3; ++g) { ptile[g] = (g * U + u) / 16; pcol[g] = (g * U + u) % 16; }
     bool dead = false;
-#ifdef GRU_STAMPS
-    unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, last_ = __builtin_amdgcn_s_memrealtime();
-#endif
     for (int t = 0; t < T; ++t) {
         const int cur = t & 1, nxt = cur ^ 1;
         const float gi0 = gin0, gi1 = gin1, gi2 = gin2;
@@ -523,7 +493,6 @@ template <int H, int NB> __global__ __launch_bounds__(512) void gru_fwd_mfma_ker
 #pragma unroll
         for (int i = 0; i < 3; ++i)
             *reinterpret_cast<f32x4_t *>(&part[(tile0 + i) * M::KS + kpart][lane & 15][4 * (lane >> 4)]) = acc[i];
-        GRU_STAMP(0);
         coop_lds_barrier();
         if (q < NB) {
             float gs[3];
@@ -557,7 +526,6 @@ template <int H, int NB> __global__ __launch_bounds__(512) void gru_fwd_mfma_ker
                 a.hall[((long)ns * (T + 1) + t + 1) * H + j] = hv;
             }
         }
-        GRU_STAMP(1);
         if (t + 1 < T) {
             COOP_GLOBAL gu64_t *slot[KP];
 #pragma unroll
@@ -576,10 +544,6 @@ template <int H, int NB> __global__ __launch_bounds__(512) void gru_fwd_mfma_ker
                     if (++spins > (1u << 22)) { dead = true; coop_report(ca.err, COOP_ERR_FWD_WAIT); break; }
                     __builtin_amdgcn_s_sleep(1);
                 }
-#ifdef GRU_STAMPS
-                ph[4] += spins;
-#endif
-                GRU_STAMP(2);
 #pragma unroll
                 for (int i = 0; i < KP; ++i) {
                     int gw, gk;
@@ -591,13 +555,8 @@ template <int H, int NB> __global__ __launch_bounds__(512) void gru_fwd_mfma_ker
                 }
             }
             coop_lds_barrier();
-            GRU_STAMP(3);
         }
     }
-#ifdef GRU_STAMPS
-    if (ca.stamps != nullptr && (tid == 0 || tid == 511))
-        for (int i = 0; i < 5; ++i) ca.stamps[(blockIdx.x * 2 + (tid != 0)) * 8 + i] = ph[i];
-#endif
     if (a.hlast != nullptr && q < NB && n0 + q < a.N) a.hlast[(long)(n0 + q) * H + j] = hprev;
 }
 
@@ -651,9 +610,6 @@ template <int H, int NB> __global__ __launch_bounds__(512) void gru_bwd_coop_ker
     if (emine) request(T - 1);
     coop_weights_ready(w);
     bool dead = false;
-#ifdef GRU_STAMPS
-    unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, last_ = __builtin_amdgcn_s_memrealtime();
-#endif
     for (int t = T - 1; t >= 0; --t) {
         const int par = t & 1;
         const unsigned epoch = ca.epoch0 + (unsigned)(T - t);              // 1, 2, ...
@@ -683,13 +639,12 @@ template <int H, int NB> __global__ __launch_bounds__(512) void gru_bwd_coop_ker
             if (emine && t > 0) request(t - 1);
         }
         coop_lds_barrier();
-        GRU_STAMP(0);
         // partial[jc] over this thread's 96 rows, all NB windows
         f32x2 acc[NB];                                         // even / odd rows
 #pragma unroll
         for (int s = 0; s < NB; ++s) acc[s] = f32x2{0.f, 0.f};
 #pragma unroll
-        for (int i4 = 0; i4 < GRU_ABL_B; ++i4) {
+        for (int i4 = 0; i4 < 24; ++i4) {
 #pragma unroll
             for (int s = 0; s < NB; ++s) {
                 const float4 d4 = *reinterpret_cast<const float4 *>(&dgs[s][half * 96 + 4 * i4]);
@@ -699,7 +654,6 @@ template <int H, int NB> __global__ __launch_bounds__(512) void gru_bwd_coop_ker
 #pragma unroll
         for (int s = 0; s < NB; ++s) part[half][s][jc] = acc[s].x + acc[s].y;
         coop_lds_barrier();
-        GRU_STAMP(1);
         auto column = [&](int s, int k) {
             float v = part[0][s][k];
 #pragma unroll
@@ -717,7 +671,6 @@ template <int H, int NB> __global__ __launch_bounds__(512) void gru_bwd_coop_ker
                 __hip_atomic_store(slot, ((gu64_t)epoch << 32) | (gu64_t)__float_as_uint(dead ? NAN : v), __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT);
             }
-            GRU_STAMP(2);
             if (ew) {
                 float sum = keep + column(es, ej);
                 // the partners' pieces are polled together: one L2 round trip per attempt, not G - 1 in a row
@@ -742,19 +695,11 @@ template <int H, int NB> __global__ __launch_bounds__(512) void gru_bwd_coop_ker
 #pragma unroll
                 for (int d = 0; d < G - 1; ++d) sum += __uint_as_float((unsigned)x[d]);
                 carry = dead ? NAN : sum;
-#ifdef GRU_STAMPS
-                ph[4] += spins;
-#endif
             }
-            GRU_STAMP(3);
             // no barrier here: dgs is rewritten before the next step's first barrier, part after it, and every thread has
             // finished reading both when it gets there; `dead` stays with the thread that timed out (its carry is poisoned)
         }
     }
-#ifdef GRU_STAMPS
-    if (ca.stamps != nullptr && (tid == 0 || tid == 511))
-        for (int i = 0; i < 5; ++i) ca.stamps[(blockIdx.x * 2 + (tid != 0)) * 8 + i] = ph[i];
-#endif
 }
 
 template <int H, int NB> __global__ __launch_bounds__(512) void gru_bwd_mfma_kernel(GruCoopArgs ca)
@@ -828,9 +773,6 @@ template <int H, int NB> __global__ __launch_bounds__(512) void gru_bwd_mfma_ker
     };
     if (emine) request(T - 1);
     bool dead = false;
-#ifdef GRU_STAMPS
-    unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, last_ = __builtin_amdgcn_s_memrealtime();
-#endif
     for (int t = T - 1; t >= 0; --t) {
         const int par = t & 1;
         const unsigned epoch = ca.epoch0 + (unsigned)(T - t);              // 1, 2, ...
@@ -865,7 +807,6 @@ template <int H, int NB> __global__ __launch_bounds__(512) void gru_bwd_mfma_ker
             if (emine && t > 0) request(t - 1);
         }
         coop_lds_barrier();
-        GRU_STAMP(0);
         // out[window][column] = sum over the member's rows: four products per K step (see gru_fwd_mfma_kernel), four column
         // tiles per wave sharing the A fragments
         {
@@ -894,7 +835,6 @@ template <int H, int NB> __global__ __launch_bounds__(512) void gru_bwd_mfma_ker
             }
         }
         coop_lds_barrier();
-        GRU_STAMP(1);
         auto column = [&](int s, int k) { return part[0][s][k] + part[1][s][k]; };
         // publish the columns other members own (this member's own columns stay in LDS)
         if (t > 0) {
@@ -907,7 +847,6 @@ template <int H, int NB> __global__ __launch_bounds__(512) void gru_bwd_mfma_ker
                 __hip_atomic_store(slot, ((gu64_t)epoch << 32) | (gu64_t)__float_as_uint(dead ? NAN : v), __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT);
             }
-            GRU_STAMP(2);
             if (ew) {
                 float sum = keep + column(es, ej);
                 // the partners' pieces are polled together: one L2 round trip per attempt, not G - 1 in a row
@@ -932,43 +871,13 @@ template <int H, int NB> __global__ __launch_bounds__(512) void gru_bwd_mfma_ker
 #pragma unroll
                 for (int d = 0; d < G - 1; ++d) sum += __uint_as_float((unsigned)x[d]);
                 carry = dead ? NAN : sum;
-#ifdef GRU_STAMPS
-                ph[4] += spins;
-#endif
             }
-            GRU_STAMP(3);
             // no barrier here: dgs is rewritten before the next step's first barrier, part after it, and every thread has
             // finished reading both when it gets there; `dead` stays with the thread that timed out (its carry is poisoned)
         }
     }
-#ifdef GRU_STAMPS
-    if (ca.stamps != nullptr && (tid == 0 || tid == 511))
-        for (int i = 0; i < 5; ++i) ca.stamps[(blockIdx.x * 2 + (tid != 0)) * 8 + i] = ph[i];
-#endif
 }
 
-#ifdef GRU_STAMPS
-static int gru_print_stamps(const char *what, const unsigned long long *stamps, int nblk, int H, int nb, int T, hipStream_t st)
-{
-    static unsigned long long host[512 * 8];
-    static int calls = 0;
-    CPC_CHECK_HIP(hipStreamSynchronize(st));
-    CPC_CHECK_HIP(hipMemcpy(host, stamps, sizeof(host), hipMemcpyDeviceToHost));
-    if (++calls % 7 != 0) return CPC_OK;
-    for (int who = 0; who < 2; ++who) {
-        double sum[5] = {0, 0, 0, 0, 0}, mx[5] = {0, 0, 0, 0, 0};
-        for (int b = 0; b < nblk; ++b)
-            for (int i = 0; i < 5; ++i) {
-                const double v = (double)host[(b * 2 + who) * 8 + i];
-                sum[i] += v; mx[i] = std::max(mx[i], v);
-            }
-        fprintf(stderr, "gru stamps H=%d nb=%d thread %3d, us per step (mean, slowest workgroup) %s: %.2f (%.2f) | %.2f (%.2f) | %.2f (%.2f) | %.2f (%.2f); "
-                "failed polls per step %.2f (%.2f)\n", H, nb, who ? 511 : 0, what, sum[0] / nblk / T * 0.01, mx[0] / T * 0.01, sum[1] / nblk / T * 0.01,
-                mx[1] / T * 0.01, sum[2] / nblk / T * 0.01, mx[2] / T * 0.01, sum[3] / nblk / T * 0.01, mx[3] / T * 0.01, sum[4] / nblk / T, mx[4] / T);
-    }
-    return CPC_OK;
-}
-#endif
 
 // The matrix-pipe form of the step.  Measured (profiles/r03_gru_stamps.txt): H = 512 with 8 windows per group -- forward 1.47 ->
 // 1.23 ms, backward 2.03 -> 1.37 ms per CPC-large step; H = 256 with 2 windows per group (CPC-small: a 16-row tile is 3/4
@@ -1101,11 +1010,10 @@ static int gru_forward(const float *x, const float *const *prm, const float *h0,
         a.hall = g.hall[l]; a.gates = g.gates[l]; a.hn = g.hn[l];
         a.hlast = h_last ? h_last + (size_t)l * N * H : nullptr;
         a.N = N; a.T = T; a.H = H; a.hp = hp; a.kq = kq; a.whh = w_hh;
-        static const bool coop_off = getenv("CPC_GRU_STREAM") != nullptr;
         static const int n_cus = coop_cu_count();
         // the cooperative kernel needs every workgroup resident at once (1 per CU)
         int G = 0;
-        int nb = (coop_off || !coop_allowed()) ? 0 : coop_windows_per_group(H, N, n_cus, &G);
+        int nb = coop_allowed() ? coop_windows_per_group(H, N, n_cus, &G) : 0;
         if (nb != 0 && !(H == 256 ? coop_fwd_fits<256>(nb, (unsigned)(cdiv(N, nb) * G), n_cus) : coop_fwd_fits<512>(nb, (unsigned)(cdiv(N, nb) * G), n_cus)))
             nb = 0;                             // not resident all at once: the streaming kernel has no such requirement
         if (nb != 0) {
@@ -1114,20 +1022,12 @@ static int gru_forward(const float *x, const float *const *prm, const float *h0,
             ca.xcd_map = (ca.groups % 8 == 0) ? 1 : 0;
             ca.err = coop_error_word(); ca.fault = coop_fault_injection();
             CPC_TRY(coop_comm_acquire(sizeof(gu64_t) * (size_t)ca.groups * 2 * nb * H, T, st, &ca.comm, &ca.epoch0));
-#ifdef GRU_STAMPS
-            static unsigned long long *stamps = nullptr;
-            if (stamps == nullptr) CPC_CHECK_HIP(hipMalloc(&stamps, 512 * 8 * sizeof(unsigned long long)));
-            ca.stamps = stamps;
-#endif
             {
                 ProfScope prof(PROF_GRU_FWD, st);
                 const dim3 grid((unsigned)(ca.groups * G));
                 if (H == 256) launch_coop_fwd<256>(nb, grid, st, ca);
                 else launch_coop_fwd<512>(nb, grid, st, ca);
             }
-#ifdef GRU_STAMPS
-            CPC_TRY(gru_print_stamps("fwd: math | (barrier+) gates+publish | wait | lds+barrier", stamps, ca.groups * G, H, nb, T, st));
-#endif
         } else {
             hipLaunchKernelGGL(gru_pack_fwd_kernel, dim3(256), dim3(256), 0, st, w_hh, g.wpack, H);      // (the streaming kernel's weight layout only)
             CPC_CHECK_LAUNCH("gru_pack_fwd_kernel");
@@ -1170,10 +1070,9 @@ static int gru_backward(const float *x, const float *const *prm, const float *do
         float *const dgi = defer_tail ? g.dgi_l[l] : g.dgi, *const dgh = defer_tail ? g.dgh_l[l] : g.dgh;
         a.dout = dcur; a.dgi = dgi; a.dgh = dgh;
         CPC_TRY(infonce_deferred_mark(st));       // (see infonce_deferred_start below)
-        static const bool coop_off = getenv("CPC_GRU_STREAM") != nullptr;
         static const int n_cus = coop_cu_count();
         int G = 0;
-        int nb = (coop_off || !coop_allowed()) ? 0 : coop_windows_per_group(H, N, n_cus, &G);
+        int nb = coop_allowed() ? coop_windows_per_group(H, N, n_cus, &G) : 0;
         if (nb != 0 && !(H == 256 ? coop_bwd_fits<256>(nb, (unsigned)(cdiv(N, nb) * G), n_cus) : coop_bwd_fits<512>(nb, (unsigned)(cdiv(N, nb) * G), n_cus)))
             nb = 0;
         if (nb != 0) {
@@ -1182,20 +1081,12 @@ static int gru_backward(const float *x, const float *const *prm, const float *do
             ca.xcd_map = (ca.groups % 8 == 0) ? 1 : 0;
             ca.err = coop_error_word(); ca.fault = coop_fault_injection();
             CPC_TRY(coop_comm_acquire(sizeof(gu64_t) * (size_t)ca.groups * 2 * G * nb * H, T, st, &ca.comm, &ca.epoch0));
-#ifdef GRU_STAMPS
-            static unsigned long long *stamps = nullptr;
-            if (stamps == nullptr) CPC_CHECK_HIP(hipMalloc(&stamps, 512 * 8 * sizeof(unsigned long long)));
-            ca.stamps = stamps;
-#endif
             {
                 ProfScope prof(PROF_GRU_BWD, st);
                 const dim3 grid((unsigned)(ca.groups * G));
                 if (H == 256) launch_coop_bwd<256>(nb, grid, st, ca);
                 else launch_coop_bwd<512>(nb, grid, st, ca);
             }
-#ifdef GRU_STAMPS
-            CPC_TRY(gru_print_stamps("bwd: gates | math | publish | wait", stamps, ca.groups * G, H, nb, T, st));
-#endif
         } else {
             hipLaunchKernelGGL(gru_pack_bwd_kernel, dim3(256), dim3(256), 0, st, w_hh, g.wpack, H);
             CPC_CHECK_LAUNCH("gru_pack_bwd_kernel");

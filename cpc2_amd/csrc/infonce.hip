@@ -22,7 +22,6 @@
 #include <cstdlib>
 #include <map>
 #include <mutex>
-#include <vector>
 
 namespace cpc {
 
@@ -55,11 +54,9 @@ struct NceArgs {
     int lw;                // LDS dS row length (floats), multiple of 4
     // backward
     const float *dloss;    // [K]
-    float *dz;             // [b*T][H]  (atomics; unused when vbuf is set)
-    float *vbuf;           // [b*W][K + Nneg][H] or null: every candidate's dz contribution stored once (see below)
+    float *vbuf;           // [b*W][K + Nneg][H]: every candidate's dz contribution stored once (see below)
     float *ds_buf;         // [b*W][17][lw]: dS and the candidate rows, handed from infonce_bwd_kernel to the dz kernels
     float inv_count;       // 1 / (b*W)
-    unsigned long long *stamps;   // diagnostic build (CPC_NCE_STAMP=1): per wave, s_memtime at five points of the forward kernel
 };
 
 // The gather table z (b*T rows) is larger than one XCD's L2 (8.4 MB against 4 MB at the benchmark shape), and a (b,t)'s
@@ -98,9 +95,6 @@ __global__ __launch_bounds__(64) void nce_block_sort_kernel(const int32_t *ext, 
 // z row of candidate g of (bb, t): g < 16 -> positive tile (row t+1+g, only g < K), else negative g-16
 __device__ __forceinline__ long nce_row(const NceArgs &a, int bb, int t, int g)
 {
-#if defined(NCE_DBG) && (NCE_DBG & 1)
-    return (g < NCE_POS || g - NCE_POS < a.Nneg) ? (long)(g & 15) : -1;       // probe: every candidate from 16 hot rows
-#endif
     if (g < NCE_POS) return (g < a.K && t + 1 + g < a.T) ? (long)bb * a.T + t + 1 + g : -1;
     const int j = g - NCE_POS;
     return j < a.Nneg ? (long)a.ext[((long)bb * a.W + t) * a.Nneg + j] : -1;
@@ -120,8 +114,6 @@ template <int H> __global__ __launch_bounds__(64) void infonce_fwd_kernel(NceArg
     const int lane = threadIdx.x, r = lane & 15, q = lane >> 4;
     const float inv_h = 1.f / H;
 
-    unsigned long long st0 = 0, st1 = 0, st2 = 0, st3 = 0;
-    if (a.stamps) st0 = __builtin_amdgcn_s_memtime();
     float4 areg[KK];
     {
         const float *prow = a.Pk[r < a.K ? r : 0] + ((long)bb * a.p_rows + t) * a.p_stride + 4 * q;
@@ -141,22 +133,17 @@ template <int H> __global__ __launch_bounds__(64) void infonce_fwd_kernel(NceArg
     for (int j = lane; j < a.Nneg; j += 64) lrow[j] = a.ext[(long)bt * a.Nneg + j];
     __syncthreads();                           // one wave
     auto cand_row = [&](int g) -> long {       // z row of candidate g: the positive tile, then the negatives
-#if defined(NCE_DBG) && (NCE_DBG & 1)
-        return (g < NCE_POS || g - NCE_POS < a.Nneg) ? (long)(g & 15) : -1;
-#endif
         if (g < NCE_POS) return (g < a.K && t + 1 + g < a.T) ? (long)bb * a.T + t + 1 + g : -1;
         return g - NCE_POS < a.Nneg ? (long)lrow[g - NCE_POS] : -1;
     };
 
     // (rows of padding candidates are clamped to row 0, not zeroed: their columns are never used, and an unconditional
     // load keeps the loop free of branches -- hipcc then waits for the CURRENT tile's loads only, not for the prefetch)
-    if (a.stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); st1 = __builtin_amdgcn_s_memtime(); }
     long row = max(cand_row(r), 0L);
     float4 bcur[KK];
 #pragma unroll
     for (int kk = 0; kk < KK; ++kk) bcur[kk] = *reinterpret_cast<const float4 *>(a.z + row * H + 4 * q + 16 * kk);
 
-    if (a.stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); st2 = __builtin_amdgcn_s_memtime(); }
     for (int tile = 0; tile < ntiles; ++tile) {
         // prefetch the next tile's rows while this one is multiplied
         float4 bnext[KK];
@@ -165,10 +152,6 @@ template <int H> __global__ __launch_bounds__(64) void infonce_fwd_kernel(NceArg
         for (int kk = 0; kk < KK; ++kk) bnext[kk] = *reinterpret_cast<const float4 *>(a.z + nrow * H + 4 * q + 16 * kk);
 
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#if defined(NCE_DBG) && (NCE_DBG & 2)
-#pragma unroll
-        for (int kk = 0; kk < KK; ++kk) acc[kk & 3] += bcur[kk].x + bcur[kk].y + bcur[kk].z + bcur[kk].w;   // probe: no MFMA
-#else
 #pragma unroll
         for (int kk = 0; kk < KK; ++kk) {
             acc = __builtin_amdgcn_mfma_f32_16x16x4f32(areg[kk].x, bcur[kk].x, acc, 0, 0, 0);
@@ -176,7 +159,6 @@ template <int H> __global__ __launch_bounds__(64) void infonce_fwd_kernel(NceArg
             acc = __builtin_amdgcn_mfma_f32_16x16x4f32(areg[kk].z, bcur[kk].z, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_16x16x4f32(areg[kk].w, bcur[kk].w, acc, 0, 0, 0);
         }
-#endif
         // the prefetched rows are taken over HERE, before this tile's logits are stored: vmcnt counts stores too, and a
         // wait for the rows placed behind the stores would sit out a store round trip per tile
 #pragma unroll
@@ -202,7 +184,6 @@ template <int H> __global__ __launch_bounds__(64) void infonce_fwd_kernel(NceArg
         }
     }
 
-    if (a.stamps) st3 = __builtin_amdgcn_s_memtime();
     // merge (m, s) over the 16 lanes of the row group; lanes that saw no candidate carry (-inf, 0)
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -232,11 +213,6 @@ template <int H> __global__ __launch_bounds__(64) void infonce_fwd_kernel(NceArg
             }
         }
     }
-    if (a.stamps && lane == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        unsigned long long *o = a.stamps + (long)bt * 8;
-        o[0] = st0; o[1] = st1; o[2] = st2; o[3] = st3; o[4] = __builtin_amdgcn_s_memtime(); o[5] = __builtin_amdgcn_s_memrealtime();
-    }
 }
 
 // The same forward pass for H = 256 / 512 as a STREAM through LDS.  Lanes that each pull 16-byte pieces of "their" row (the
@@ -265,7 +241,7 @@ template <int H> __global__ __launch_bounds__(64, 2) void infonce_fwd_dma_kernel
     const float inv_h = 1.f / H, sc2 = 1.4426950408889634f / H;
     extern __shared__ __attribute__((aligned(1024))) char dma_lds[];
     // the two index lists first, then the two slots: a slot's address minus the largest K-slice offset (glds16x8: M0 = address
-    // - offset) must not go below zero -- the hardware drops an LDS-DMA whose M0 is negative (tools/scratch/ldsdma_offset_probe.hip)
+    // - offset) must not go below zero -- the hardware drops an LDS-DMA whose M0 is negative (ldsdma.h)
     static_assert(2 * NCE_LIST >= (HS - 1) * NCE_KC * 4, "slot addresses stay above the K-slice offsets");
     const char *lists = dma_lds;                                               // [2][NCE_LIST]
     const unsigned lds0 = lds_addr(dma_lds) + 2 * NCE_LIST;
@@ -285,19 +261,10 @@ template <int H> __global__ __launch_bounds__(64, 2) void infonce_fwd_dma_kernel
     };
     auto rows_to_offsets = [&](const u32x2_t (&pr)[NCE_PP / 2], unsigned (&vr)[NCE_PP]) {   // after the reads' wait
 #pragma unroll
-#if defined(NCE_DBG) && (NCE_DBG & 8)
-        for (int i = 0; i < NCE_PP; ++i) vr[i] = (min(pr[i >> 1][i & 1], zmax) & 2047u) * (unsigned)(H * 4) + vcol;   // probe: a 2 MiB table (L2-resident)
-#elif defined(NCE_DBG) && (NCE_DBG & 16)
-        for (int i = 0; i < NCE_PP; ++i) vr[i] = (min(pr[i >> 1][i & 1], zmax) & 15u) * (unsigned)(H * 4) + vcol;     // probe: 16 hot rows
-#else
         for (int i = 0; i < NCE_PP; ++i) vr[i] = min(pr[i >> 1][i & 1], zmax) * (unsigned)(H * 4) + vcol;   // (slots past Nneg: any valid row)
-#endif
     };
     auto req_rows = [&](const unsigned (&vr)[NCE_PP], int half) {
         const unsigned dst = lds0 + wslot;
-#if defined(NCE_ABL) && (NCE_ABL & 8)
-        half = 0;                                           // probe: every K slice re-reads slice 0 (a gather table of half the size)
-#endif
         if (half == 0) glds16x8<NCE_PIECE, 0>(dst, vr, a.z);
         else if (half == 1) glds16x8<NCE_PIECE, NCE_KC * 4>(dst, vr, a.z);
         else if (half == 2) glds16x8<NCE_PIECE, 2 * NCE_KC * 4>(dst, vr, a.z);
@@ -310,25 +277,16 @@ template <int H> __global__ __launch_bounds__(64, 2) void infonce_fwd_dma_kernel
         const unsigned dst = lds0 + wslot;
         if (a.p_packed) {
             // one tensor [b * p_rows][K * H]: row k of (b, t) is K-row number (bb p_rows + t) K + k of it
-#if defined(NCE_DBG) && (NCE_DBG & 32)
-            const unsigned r0 = (unsigned)(((bb * a.p_rows + t) & 63) * a.K);            // probe: the predictions of 64 (b,t) only (no P traffic)
-#else
             const unsigned r0 = (unsigned)((bb * a.p_rows + t) * a.K);
-#endif
             unsigned vp[NCE_PP];
 #pragma unroll
             for (int i = 0; i < NCE_PP; ++i) vp[i] = (r0 + (2 * i + up < a.K ? 2 * i + up : 0)) * (unsigned)(H * 4) + vcol;
-            // Non-temporal loads here (-DNCE_P_NT) take the kernel ALONE from 118 to 113 us -- the read-once rows no longer push z
-            // out of L2 -- but the backward pass re-reads P, finds it gone from the caches and loses 0.03 ms: net loss in the step.
-#ifdef NCE_P_NT
-            constexpr bool PNT = true;
-#else
-            constexpr bool PNT = false;
-#endif
-            if (half == 0) glds16x8<NCE_PIECE, 0, PNT>(dst, vp, a.Pk[0]);
-            else if (half == 1) glds16x8<NCE_PIECE, NCE_KC * 4, PNT>(dst, vp, a.Pk[0]);
-            else if (half == 2) glds16x8<NCE_PIECE, 2 * NCE_KC * 4, PNT>(dst, vp, a.Pk[0]);
-            else glds16x8<NCE_PIECE, 3 * NCE_KC * 4, PNT>(dst, vp, a.Pk[0]);
+            // (not non-temporal: such loads take the kernel ALONE from 118 to 113 us -- the read-once rows no longer push z out of
+            // L2 -- but the backward pass re-reads P, finds it gone from the caches and loses 0.03 ms: net loss in the step)
+            if (half == 0) glds16x8<NCE_PIECE, 0>(dst, vp, a.Pk[0]);
+            else if (half == 1) glds16x8<NCE_PIECE, NCE_KC * 4>(dst, vp, a.Pk[0]);
+            else if (half == 2) glds16x8<NCE_PIECE, 2 * NCE_KC * 4>(dst, vp, a.Pk[0]);
+            else glds16x8<NCE_PIECE, 3 * NCE_KC * 4>(dst, vp, a.Pk[0]);
         } else {
             const long off = ((long)bb * a.p_rows + t) * a.p_stride + half * NCE_KC;
 #pragma unroll
@@ -381,14 +339,6 @@ template <int H> __global__ __launch_bounds__(64, 2) void infonce_fwd_dma_kernel
     f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
     int bt = blockIdx.x, par = 0;
     if (bt >= n_bt) return;
-#if defined(NCE_STAGGER)
-    {
-        // probe: the second wave of a SIMD (odd wave slot: HW_ID bits 3:0) starts NCE_STAGGER x 64 cycles late, so that one wave of
-        // the pair requests while the other multiplies from the first element on
-        const unsigned hwid = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));
-        if (hwid & 1u) __builtin_amdgcn_s_sleep(NCE_STAGGER);
-    }
-#endif
     req_p(bt, 0);
     req_list(bt, 0);
     for (; bt < n_bt; bt += gridDim.x, par ^= 1) {
@@ -443,10 +393,6 @@ template <int H> __global__ __launch_bounds__(64, 2) void infonce_fwd_dma_kernel
                 else read_frags(bf);
 #pragma unroll
                 for (int kk = 0; kk < FR; kk += 2) {
-#if defined(NCE_ABL) && (NCE_ABL & 4)
-                    acc0[0] += __builtin_bit_cast(f32x4, bf[kk])[0]; acc1[1] += __builtin_bit_cast(f32x4, bf[kk + 1])[1];
-                    continue;
-#endif
                     const float4 p0 = areg[half * FR + kk], p1 = areg[half * FR + kk + 1];
                     const f32x4 b0 = __builtin_bit_cast(f32x4, bf[kk]), b1 = __builtin_bit_cast(f32x4, bf[kk + 1]);
                     acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(p0.x, b0[0], acc0, 0, 0, 0);
@@ -472,25 +418,16 @@ template <int H> __global__ __launch_bounds__(64, 2) void infonce_fwd_dma_kernel
                 if (j < a.Nneg) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-#if !(defined(NCE_ABL) && (NCE_ABL & 1))
                         // slot order: the 16 lanes of a row group write 64 consecutive bytes (in the caller's order these were
                         // 64 scattered dwords per instruction -- 206 MB of write traffic for 46 MB of logits, and every store had
-                        // to retire before the next element's wait could pass: 17 % of the kernel)
-#ifdef NCE_LOGITS_NT                                        /* (as NCE_P_NT: the backward pass reads the logits back) */
-                        if (4 * q + e < a.K) __builtin_nontemporal_store(acc[e] * inv_h, lrow0 + e * lstep + j);
-#else
+                        // to retire before the next element's wait could pass: 17 % of the kernel).  Not non-temporal, as the P
+                        // loads above: the backward pass reads the logits back.
                         if (4 * q + e < a.K) lrow0[e * lstep + j] = acc[e] * inv_h;
-#endif
-#endif
-#if defined(NCE_ABL) && (NCE_ABL & 2)
-                        m[e] = fmaxf(m[e], acc[e]);
-#else
                         const float x2 = acc[e] * sc2;
                         const float mn = fmaxf(m[e], x2);
                         sm[e] = sm[e] * __builtin_amdgcn_exp2f(m[e] - mn) + __builtin_amdgcn_exp2f(x2 - mn);   // m = -inf: 0 * 0 + ..
                         m[e] = mn;
                         macc[e] = fmaxf(macc[e], acc[e]);
-#endif
                     }
                 }
             }
@@ -560,15 +497,14 @@ __global__ void infonce_reduce_kernel(const float *lossp, const float *hit, long
 // holds dS[16][lw] = d loss / d <P_k, cand_g> and the candidates' z-row indices.
 //   dP^T[d][k] += sum_g cand_g[d] * dS[k][g]    16x16x4, A = candidate rows streamed from L2 as float4s: lane
 //                 (i, q) reads cand_{4s+q}[64T + 4i ..+3] and feeds the 4 row-interleaved tiles d = 64T + 4i + e
-//   dz[row_g][d] += sum_k dS[k][g] * P_k[d]     32x32x2.  The b*W*(K + Nneg) contribution rows are either added to dz
-//                 with fp32 atomics (128-byte segments; the atomic units' rate then IS the kernel's time) or, when
-//                 a.vbuf is set, stored once to vbuf[(b,t)][candidate][H] and summed per target row by
+//   dz[row_g][d] += sum_k dS[k][g] * P_k[d]     32x32x2.  The b*W*(K + Nneg) contribution rows are stored once to
+//                 vbuf[(b,t)][candidate][H] (by infonce_dz_store_kernel) and summed per target row by
 //                 infonce_dz_gather_kernel from counting-sorted reference lists: plain streaming traffic, and a
-//                 summation order that does not change from run to run.
+//                 summation order that does not change from run to run (with fp32 atomics into dz instead, the atomic
+//                 units' rate was the kernel's time).
 template <int H> __global__ __launch_bounds__(64) void infonce_bwd_kernel(NceArgs a)
 {
     constexpr int DG = (H + 63) / 64;          // groups of 4 interleaved 16-row d tiles (H = 32: half a group)
-    constexpr int DT32 = H / 32;               // 32-wide d tiles of the dz product
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *dS = smem;                                              // [16][lw]
     int *rowidx = reinterpret_cast<int *>(dS + NCE_ROWS * a.lw);   // [lw]
@@ -660,44 +596,14 @@ template <int H> __global__ __launch_bounds__(64) void infonce_bwd_kernel(NceArg
                         make_float4(dp[T4][0][reg], dp[T4][1][reg], dp[T4][2][reg], dp[T4][3][reg]);
     }
 
-    // ---- dz ------------------------------------------------------------------------------------
-    const int r32 = lane & 31, h = lane >> 5;
-    const long prow_off = ((long)bb * a.p_rows + t) * a.p_stride;
-    if (a.vbuf != nullptr) {
-        // the contribution rows are formed and stored by infonce_dz_store_kernel (its own launch: this kernel's register
-        // budget allows two waves per SIMD, too few to overlap the row gather above with 1 GB of stores)
-        float *dsg = a.ds_buf + bt * (long)(NCE_ROWS + 1) * a.lw;
-        for (int i = lane; i < NCE_ROWS * a.lw; i += 64) dsg[i] = dS[i];
-        for (int g = lane; g < a.lw; g += 64) reinterpret_cast<int *>(dsg)[NCE_ROWS * a.lw + g] = rowidx[g];
-        return;
-    }
-    for (int dt = 0; dt < DT32; ++dt) {
-        float bvals[NCE_ROWS / 2];
-#pragma unroll
-        for (int kp = 0; kp < NCE_ROWS / 2; ++kp) {
-            const int k = 2 * kp + h;
-            bvals[kp] = k < a.K ? a.Pk[k][prow_off + dt * 32 + r32] : 0.f;
-        }
-        for (int ct = 0; ct < npad / 32; ++ct) {
-            f32x16 acc;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-#pragma unroll
-            for (int kp = 0; kp < NCE_ROWS / 2; ++kp) {
-                const float av = dS[(2 * kp + h) * a.lw + ct * 32 + r32];
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bvals[kp], acc, 0, 0, 0);
-            }
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int ci = ct * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-                const int row = rowidx[ci];
-                if (row >= 0) atomicAdd(a.dz + (long)row * H + dt * 32 + r32, acc[e]);
-            }
-        }
-    }
+    // ---- dz: the contribution rows are formed and stored by infonce_dz_store_kernel (its own launch: this kernel's register
+    // budget allows two waves per SIMD, too few to overlap the row gather above with 1 GB of stores)
+    float *dsg = a.ds_buf + bt * (long)(NCE_ROWS + 1) * a.lw;
+    for (int i = lane; i < NCE_ROWS * a.lw; i += 64) dsg[i] = dS[i];
+    for (int g = lane; g < a.lw; g += 64) reinterpret_cast<int *>(dsg)[NCE_ROWS * a.lw + g] = rowidx[g];
 }
 
-// Second half of the backward pass when the dz contributions are stored (a.vbuf): one wave per (b,t) reloads its
+// Second half of the one-wave backward pass: one wave per (b,t) reloads its
 // dS[16][lw] and candidate rows (written by infonce_bwd_kernel) and forms  V[cand][d] = sum_k dS[k][cand] * P_k[d]
 // with the 32x32x2 MFMA, candidate tiles outermost so that the H/32 128-byte pieces of a row are stored back to back.
 template <int H> __global__ __launch_bounds__(64) void infonce_dz_store_kernel(NceArgs a)
@@ -786,8 +692,6 @@ template <int H, int NKK> __global__ __launch_bounds__(H / 2) void infonce_bwd_f
     const int npad = a.lw - 4;                                     // multiple of 32 >= ncand
     const float inv_h = 1.f / H;
     const float wgt = (a.weights != nullptr ? a.weights[bt] : 1.f) * a.inv_count;
-    unsigned long long *stamp = a.stamps != nullptr && threadIdx.x == 0 ? a.stamps + bt * 8 : nullptr;
-    if (stamp) stamp[0] = __builtin_amdgcn_s_memtime();
 
     // ---- phase 0 -------------------------------------------------------------------------------
     // (loads are unconditional, from clamped addresses, and selected afterwards: a load under a lane condition becomes a
@@ -839,7 +743,6 @@ template <int H, int NKK> __global__ __launch_bounds__(H / 2) void infonce_bwd_f
         }
     }
     __syncthreads();
-    if (stamp) stamp[1] = __builtin_amdgcn_s_memtime();
 
     // ---- phases 1 and 2, one loop over groups of 16 candidates: the rows of group i + 1 are requested, the contribution rows
     // of group i are formed and stored (no gathered row needed), THEN the gathered rows of group i are multiplied into dP --
@@ -939,8 +842,6 @@ template <int H, int NKK> __global__ __launch_bounds__(H / 2) void infonce_bwd_f
         }
     }
 #undef NCE_ROWS_GROUP
-    if (stamp) stamp[2] = __builtin_amdgcn_s_memtime();
-    if (stamp) { stamp[3] = __builtin_amdgcn_s_memtime(); stamp[4] = __builtin_amdgcn_s_memrealtime(); }
 }
 
 // ---- reference lists: which (b, t, negative) triples point at z row r (counting sort of ext by value) -------------
@@ -1010,12 +911,9 @@ __device__ __forceinline__ float4 nt_load4(const float4 *p)
 
 // dz[r][:] = sum of the stored contributions that point at z row r = (bb, t'): the positives of steps k = 0..K-1
 // come from (bb, t' - 1 - k), the negatives from the row's reference list.  One wave per row, 16 bytes per lane.
-#ifdef NCE_GATHER_WIDE                       /* (A/B build: the 68-register kernel of rounds 1-3, which cannot sit beside the matrix-pipe GRU backward) */
-#define NCE_GATHER_BOUNDS __launch_bounds__(256)
-#else
-#define NCE_GATHER_BOUNDS __launch_bounds__(256, 8)
-#endif
-template <int H> __global__ NCE_GATHER_BOUNDS void infonce_dz_gather_kernel(const float *vbuf, const int *offsets,
+// (at most 64 registers -- __launch_bounds__(256, 8): the 68-register kernel of rounds 1-3 could not sit beside the matrix-pipe
+//  GRU backward)
+template <int H> __global__ __launch_bounds__(256, 8) void infonce_dz_gather_kernel(const float *vbuf, const int *offsets,
                                                                                    const int *entries, float *dz, int b, int T,
                                                                                    int W, int K, int Nneg, int pos_rows)
 {
@@ -1127,10 +1025,9 @@ static int nce_layout(NceLayout &l, int b, int T, int K, int Har, int Henc, int 
     l.lse = sv.take<float>((size_t)b * l.W * K);
     l.ext_sorted = sv.take<int32_t>((size_t)b * l.W * Nneg);
     l.perm = sv.take<unsigned short>((size_t)b * l.W * Nneg + 1024);     // (+ slack: the streaming kernel reads whole KiB pieces)
-    // blocks of about 2 MB of z rows (an XCD's L2 holds 4 MB); CPC_NCE_NOSORT=1: one block = the drawn order
-    static const bool nosort = getenv("CPC_NCE_NOSORT") != nullptr;
+    // blocks of about 2 MB of z rows (an XCD's L2 holds 4 MB)
     const size_t zbytes = sizeof(float) * (size_t)b * T * Henc;
-    l.nblk = nosort ? 1 : (int)std::min<size_t>(16, std::max<size_t>(1, (zbytes + (1u << 21) - 1) >> 21));
+    l.nblk = (int)std::min<size_t>(16, std::max<size_t>(1, (zbytes + (1u << 21) - 1) >> 21));
     l.rows_per_block = (int)cdiv((long)b * T, l.nblk);
     l.saved_bytes = sv.used();
     Carver sc(scratch);
@@ -1189,17 +1086,9 @@ static int nce_sort_negatives(const NceLayout &l, const int32_t *ext, hipStream_
 
 static int nce_launch_fwd(NceArgs &a, const NceLayout &l, float *losses, float *acc, hipStream_t st)
 {
-    static const bool stamp = getenv("CPC_NCE_STAMP") != nullptr;
-    static unsigned long long *stamps = nullptr;
-    const long nw = (long)l.b * l.W;
-    if (stamp && nw <= 65536) {
-        if (stamps == nullptr) CPC_CHECK_HIP(hipMalloc(&stamps, 65536 * 8 * sizeof(unsigned long long)));
-        a.stamps = stamps;
-    }
     int status = CPC_OK;
     {
-        static const bool no_dma = getenv("CPC_NCE_NO_DMA") != nullptr;           // A/B switch: the register-gather kernel
-        const bool dma = !no_dma && (l.Henc == 256 || l.Henc == 512) && a.stamps == nullptr && l.Nneg % 8 == 0 && l.Nneg <= 256 && a.perm != nullptr;
+        const bool dma = (l.Henc == 256 || l.Henc == 512) && l.Nneg % 8 == 0 && l.Nneg <= 256 && a.perm != nullptr;
         ProfScope prof(PROF_NCE_FWD, st, dma);      // (the stream kernel takes the timing events with its own dispatch: common.h)
         const hipEvent_t e0 = prof.start(), e1 = prof.stop();
         if (dma) {
@@ -1232,20 +1121,6 @@ static int nce_launch_fwd(NceArgs &a, const NceLayout &l, float *losses, float *
     }
     CPC_TRY(status);
     CPC_CHECK_LAUNCH("infonce_fwd_kernel");
-    if (a.stamps != nullptr) {
-        static std::vector<unsigned long long> h(65536 * 8);
-        CPC_CHECK_HIP(hipStreamSynchronize(st));
-        CPC_CHECK_HIP(hipMemcpy(h.data(), stamps, nw * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        double p = 0, f = 0, lp = 0, e = 0;
-        unsigned long long r0 = ~0ull, r1 = 0;
-        for (long i = 0; i < nw; ++i) {
-            p += (double)(h[i * 8 + 1] - h[i * 8]); f += (double)(h[i * 8 + 2] - h[i * 8 + 1]); lp += (double)(h[i * 8 + 3] - h[i * 8 + 2]);
-            e += (double)(h[i * 8 + 4] - h[i * 8 + 3]);
-            r0 = std::min(r0, h[i * 8 + 5]); r1 = std::max(r1, h[i * 8 + 5]);
-        }
-        fprintf(stderr, "infonce_fwd stamps (cycles per wave): P loads %.0f, first tile rows %.0f, tile loop %.0f, epilogue %.0f; last - first wave exit %.1f us\n",
-                p / nw, f / nw, lp / nw, e / nw, (double)(r1 - r0) * 0.01);
-    }
     hipLaunchKernelGGL(infonce_reduce_kernel, dim3(2 * l.K), dim3(256), 0, st, l.lossp, l.hit, (long)l.b * l.W, l.K, a.inv_count, losses, acc);
     CPC_CHECK_LAUNCH("infonce_reduce_kernel");
     return CPC_OK;
@@ -1296,8 +1171,7 @@ static int nce_side(NceSide **out, hipStream_t caller)
     return CPC_OK;
 }
 
-// dz of the criterion: CPC_NCE_ATOMIC in the environment selects the fp32-atomic form, the default stores every
-// contribution once and sums per target row (see infonce_bwd_kernel)
+// dz of the criterion: the sum per target row of the stored contribution rows (see infonce_bwd_kernel)
 static int nce_launch_gather(const NceLayout &l, float *dz, bool fused, hipStream_t st)
 {
     const int rows = l.b * l.T;
@@ -1315,39 +1189,26 @@ static int nce_launch_gather(const NceLayout &l, float *dz, bool fused, hipStrea
 // (the reference lists are queued on its stream) and the caller launches nce_launch_gather there when it wants it to start
 static int nce_launch_bwd(NceArgs &a, const NceLayout &l, float *dz, hipStream_t st, NceSide **late = nullptr)
 {
-    static const bool atomic_dz = getenv("CPC_NCE_ATOMIC") != nullptr;
     const long n = (long)l.b * l.W * l.Nneg;
     const int rows = l.b * l.T;
-    a.dz = dz;
-    a.vbuf = atomic_dz ? nullptr : l.vbuf;
+    a.vbuf = l.vbuf;
     a.ds_buf = l.ds_buf;
-    static const bool stamp = getenv("CPC_NCE_STAMP") != nullptr;
-    if (stamp && (long)l.b * l.W <= 65536) {
-        static unsigned long long *stamps = nullptr;
-        if (stamps == nullptr) CPC_CHECK_HIP(hipMalloc(&stamps, 65536 * 8 * sizeof(unsigned long long)));
-        a.stamps = stamps;
-    }
     ProfScope prof(PROF_NCE_BWD, st);
     NceSide *side = nullptr;
-    if (atomic_dz) {
-        CPC_CHECK_HIP(hipMemsetAsync(dz, 0, sizeof(float) * (size_t)rows * l.Henc, st));
-    } else {
-        CPC_TRY(nce_side(&side, st));
-        CPC_CHECK_HIP(hipEventRecord(side->fork, st));
-        CPC_CHECK_HIP(hipStreamWaitEvent(side->stream, side->fork, 0));
-        const unsigned blocks = (unsigned)std::min<long>(cdiv(n, 256), 4096);
-        CPC_CHECK_HIP(hipMemsetAsync(l.counts, 0, sizeof(int) * (size_t)rows, side->stream));
-        hipLaunchKernelGGL(nce_hist_kernel, dim3(blocks), dim3(256), 0, side->stream, a.ext, n, l.counts);
-        hipLaunchKernelGGL(nce_scan_kernel, dim3(1), dim3(1024), 0, side->stream, l.counts, rows, l.offsets);
-        CPC_CHECK_HIP(hipMemsetAsync(l.counts, 0, sizeof(int) * (size_t)rows, side->stream));
-        hipLaunchKernelGGL(nce_fill_kernel, dim3(blocks), dim3(256), 0, side->stream, a.ext, n, l.offsets, l.counts, l.entries);
-        hipLaunchKernelGGL(nce_sort_kernel, dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, side->stream, l.offsets, l.entries, rows);
-        CPC_CHECK_LAUNCH("infonce reference lists");
-        CPC_CHECK_HIP(hipEventRecord(side->join, side->stream));
-    }
+    CPC_TRY(nce_side(&side, st));
+    CPC_CHECK_HIP(hipEventRecord(side->fork, st));
+    CPC_CHECK_HIP(hipStreamWaitEvent(side->stream, side->fork, 0));
+    const unsigned blocks = (unsigned)std::min<long>(cdiv(n, 256), 4096);
+    CPC_CHECK_HIP(hipMemsetAsync(l.counts, 0, sizeof(int) * (size_t)rows, side->stream));
+    hipLaunchKernelGGL(nce_hist_kernel, dim3(blocks), dim3(256), 0, side->stream, a.ext, n, l.counts);
+    hipLaunchKernelGGL(nce_scan_kernel, dim3(1), dim3(1024), 0, side->stream, l.counts, rows, l.offsets);
+    CPC_CHECK_HIP(hipMemsetAsync(l.counts, 0, sizeof(int) * (size_t)rows, side->stream));
+    hipLaunchKernelGGL(nce_fill_kernel, dim3(blocks), dim3(256), 0, side->stream, a.ext, n, l.offsets, l.counts, l.entries);
+    hipLaunchKernelGGL(nce_sort_kernel, dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, side->stream, l.offsets, l.entries, rows);
+    CPC_CHECK_LAUNCH("infonce reference lists");
+    CPC_CHECK_HIP(hipEventRecord(side->join, side->stream));
     int status = CPC_OK;
-    static const bool no_fused = getenv("CPC_NCE_NO_FUSED_BWD") != nullptr;       // A/B switch: the two one-wave kernels
-    const bool fused = !atomic_dz && !no_fused && (l.Henc == 256 || l.Henc == 512) && a.perm != nullptr && l.lw <= 320 &&
+    const bool fused = (l.Henc == 256 || l.Henc == 512) && a.perm != nullptr && l.lw <= 320 &&
                        l.Nneg % 16 == 0 && (size_t)l.K * (l.Nneg + 1) <= (size_t)(l.Henc / 128) * 16 * NCE_SROW;
     if (fused) {
         const unsigned grid = (unsigned)(l.b * a.p_rows);
@@ -1371,33 +1232,17 @@ static int nce_launch_bwd(NceArgs &a, const NceLayout &l, float *dz, hipStream_t
     }
     CPC_TRY(status);
     CPC_CHECK_LAUNCH("infonce_bwd_kernel");
-    if (fused && a.stamps != nullptr) {
-        const long nw = (long)l.b * l.W;
-        std::vector<unsigned long long> h(nw * 8);
-        CPC_CHECK_HIP(hipStreamSynchronize(st));
-        CPC_CHECK_HIP(hipMemcpy(h.data(), a.stamps, nw * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        double p0 = 0, p1 = 0, p2 = 0;
-        unsigned long long r0 = ~0ull, r1 = 0;
-        for (long i = 0; i < nw; ++i) {
-            p0 += (double)(h[i * 8 + 1] - h[i * 8]); p1 += (double)(h[i * 8 + 2] - h[i * 8 + 1]); p2 += (double)(h[i * 8 + 3] - h[i * 8 + 2]);
-            r0 = std::min(r0, h[i * 8 + 4]); r1 = std::max(r1, h[i * 8 + 4]);
-        }
-        fprintf(stderr, "infonce_bwd_fused stamps (cycles per workgroup): dS %.0f, dP %.0f, contribution rows %.0f; last - first exit %.1f us\n",
-                p0 / nw, p1 / nw, p2 / nw, (double)(r1 - r0) * 0.01);
+    if (!fused) {
+        NCE_DISPATCH(l.Henc, hipLaunchKernelGGL(infonce_dz_store_kernel<HH>, dim3((unsigned)(l.b * l.W)), dim3(64), l.lds_bwd, st, a));
+        CPC_CHECK_LAUNCH("infonce_dz_store_kernel");
     }
-    if (!atomic_dz) {
-        if (!fused) {
-            NCE_DISPATCH(l.Henc, hipLaunchKernelGGL(infonce_dz_store_kernel<HH>, dim3((unsigned)(l.b * l.W)), dim3(64), l.lds_bwd, st, a));
-            CPC_CHECK_LAUNCH("infonce_dz_store_kernel");
-        }
-        if (late != nullptr) {                  // the caller launches the sum on the side stream (nce_launch_gather), later
-            *late = side;
-            side->late_fused = fused;
-            return CPC_OK;
-        }
-        CPC_CHECK_HIP(hipStreamWaitEvent(st, side->join, 0));
-        CPC_TRY(nce_launch_gather(l, dz, fused, st));
+    if (late != nullptr) {                      // the caller launches the sum on the side stream (nce_launch_gather), later
+        *late = side;
+        side->late_fused = fused;
+        return CPC_OK;
     }
+    CPC_CHECK_HIP(hipStreamWaitEvent(st, side->join, 0));
+    CPC_TRY(nce_launch_gather(l, dz, fused, st));
     return CPC_OK;
 }
 

@@ -40,7 +40,7 @@ __device__ __forceinline__ void glds16_addr(unsigned lds_dst, const void *lane_s
 // from sbase + vo[i] + GOFF.  M0 is saved and restored once and stepped by an s_add between the pieces (the single-piece form
 // spends four scalar instructions per piece on it), and the per-lane offsets are inputs: no vector arithmetic between the
 // pieces.  GOFF (0 <= GOFF < 4096) goes into the instruction's offset field, which moves the LDS address by the same amount
-// (tools/scratch/ldsdma_offset_probe.hip) -- compensated in M0, which must stay >= 0: a negative M0 drops the write -- so the K
+// (measured with a stand-alone probe: docs/HISTORY.md) -- compensated in M0, which must stay >= 0: a negative M0 drops the write -- so the K
 // slices of a row share one offset register.  NT: non-temporal loads (data read once -- prediction rows -- should not push the
 // gathered table out of L2).
 #define CPC_GLDS_FIRST(MOD) "s_mov_b32 %0, m0\n\ts_sub_u32 m0, %1, %11\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %10 offset:%11" MOD "\n\t"

@@ -606,12 +606,11 @@ int lstm_layout(LstmLayout &g, int G, int N, int T, int Din, int H, int layers, 
     return CPC_OK;
 }
 
-// cooperative kernels exist for the LSTM at H = 256 / 512 (CPC_LSTM_STREAM forces the streaming ones)
+// cooperative kernels exist for the LSTM at H = 256 / 512
 int lstm_coop_windows(int G, int H, int N, int *members)
 {
-    static const bool coop_off = getenv("CPC_LSTM_STREAM") != nullptr;
     static const int n_cus = coop_cu_count();
-    if (G != 4 || coop_off || !coop_allowed()) return 0;
+    if (G != 4 || !coop_allowed()) return 0;
     return coop_windows_per_group(H, N, n_cus, members);
 }
 

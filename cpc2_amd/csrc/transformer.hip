@@ -208,7 +208,6 @@ struct AttnArgs {
     const float *dctx;     // [N*S][D]
     float *dqkv;           // [N*S][3D]
     float *dkrel_part;     // [N*heads*chunks][dk][SS]
-    unsigned long long *stamps;   // -DAT_STAMPS builds (probes): [workgroup][wave][8] s_memrealtime at the phase boundaries
 };
 
 // one workgroup per (sequence chunk of one head, 32-row query tile)
@@ -322,16 +321,11 @@ __device__ __forceinline__ void at_mfma4(at_f32x16 &acc, const float4 &a4, const
 __device__ __forceinline__ int at_row(int e, int h2) { return (e & 3) + 8 * (e >> 2) + 4 * h2; }   // C/D row of register e
 __device__ __forceinline__ void at_wave_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_wave_barrier(); }
 
-#ifdef AT_STAMPS
-#define AT_STAMP(i) do { if ((threadIdx.x & 63) == 0) a.stamps[((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define AT_STAMP(i) do { } while (0)
-#endif
 // Softmax of the wave's 32 query rows over the column tiles jt <= w, the probabilities to memory and their dropped-out copy to the
 // wave's LDS tile.  In sweeps over the 16 rows a lane holds -- row maxima, exponentials + row sums, normalisation + stores -- with
 // the tile loop outside and no per-element branch: with one wave per SIMD (121 KB of LDS per workgroup) nothing hides the latency
 // of a dependent chain or the bubble of a branch, and the first form of this code (a branch per element for the tile bound, the
-// sequence bound and the dropout switch, five crossbar hops per reduction) took 18 us of the wave's 41 (stamps: -DAT_STAMPS).
+// sequence bound and the dropout switch, five crossbar hops per reduction) took 18 us of the wave's 41 (per-phase clock stamps).
 // Base-2 exponentials: the scores are scaled by log2(e) / sqrt(dk) in the one multiplication they get anyway.
 // FULL: sizeSeq == 128 (no bound checks); DROP: dropout on.
 template <bool FULL, bool DROP>
@@ -375,7 +369,6 @@ __device__ __forceinline__ void at_softmax_store(const AttnArgs &a, at_f32x16 (&
         r = r * (2.f - t * r);                                      // one Newton step: the quotient is as good as a division's
         sm[e] = t > 0.f ? r : 0.f;
     }
-    AT_STAMP(7);
     float *const pb = a.probs + (long)cid * SS * SS;                // (uniform)
     const uint64_t ib = (uint64_t)cid * SS * SS;
 #pragma unroll
@@ -408,7 +401,6 @@ __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(AttnArgs a)
     const int head = nh % TR_HEADS, n = nh / TR_HEADS;
     const long row0 = (long)n * a.S + (long)c * SS;
     const int tid = threadIdx.x;
-    AT_STAMP(0);
     const int lane = tid & 63, w = tid >> 6, r32 = lane & 31, h2 = lane >> 5;
     float *Pw = Ps + w * 32 * AT_LP;
     const int iq = 32 * w + r32;                                 // this lane's A-operand row (requested first: in flight under the staging)
@@ -454,7 +446,6 @@ __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(AttnArgs a)
         }
     }
     __syncthreads();
-    AT_STAMP(1);
 
     at_f32x16 sc[4];
 #pragma unroll
@@ -467,7 +458,6 @@ __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(AttnArgs a)
                 at_mfma4(sc[jt], qf[q], *reinterpret_cast<const float4 *>(&Ks[(32 * jt + r32) * AT_LD + 8 * q + 4 * h2]));
         }
     }
-    AT_STAMP(2);
     if (a.krel != nullptr) {
         const int m_min = SS - 32 * w - 32 > 0 ? SS - 32 * w - 32 : 0;
         for (int mt = m_min >> 5; mt <= (SS - 1) >> 5; ++mt) {
@@ -500,7 +490,6 @@ __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(AttnArgs a)
             }
         at_wave_sync();                                          // Pw is reused for Pd below
     }
-    AT_STAMP(3);
     // softmax over j <= i (a row lives in one 32-lane half, over the tiles jt <= w): at_softmax_store
     if (SS == 128) {
         if (a.thresh != 0u) at_softmax_store<true, true>(a, sc, Pw, cid, w, r32, h2);
@@ -510,7 +499,6 @@ __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(AttnArgs a)
         else at_softmax_store<false, false>(a, sc, Pw, cid, w, r32, h2);
     }
     at_wave_sync();
-    AT_STAMP(4);
     // ctx = Pd V over j < 32 (w + 1)
     at_f32x16 cx;
 #pragma unroll
@@ -523,11 +511,6 @@ __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(AttnArgs a)
         const int i = 32 * w + at_row(e, h2);
         if (i < SS) a.ctx[(row0 + i) * a.D + head * 32 + r32] = cx[e];
     }
-    AT_STAMP(5);
-#ifdef AT_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    AT_STAMP(6);
-#endif
 }
 
 // Backward twin (head size 32, sizeSeq <= 128), same workgroup / wave decomposition.  Wave w owns query rows 32w.. for
@@ -556,7 +539,6 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_kernel(AttnArgs a)
     const int tid = threadIdx.x;
     const bool rel = a.krel != nullptr;
 
-    AT_STAMP(0);
     // staging: every load of the thread requested before the first LDS store (a `for (i = tid; ...; i += 256)` loop is not unrolled --
     // its trip count depends on tid -- and then waits for the loads of one iteration before it requests the next: four, resp. sixteen,
     // round trips to memory in a row, 7.5 of this workgroup's 37 us)
@@ -604,7 +586,7 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_kernel(AttnArgs a)
         of[q] = iq < SS ? *reinterpret_cast<const float4 *>(a.dctx + (row0 + iq) * a.D + head * 32 + 8 * q + 4 * h2)
                         : make_float4(0.f, 0.f, 0.f, 0.f);
     // the probabilities of this wave's rows, requested before anything needs them (the first form read each one inside the branch that
-    // used it: 64 exposed round trips to memory, 33 of the workgroup's 60 us -- stamps, -DAT_STAMPS); masked positions read element 0
+    // used it: 64 exposed round trips to memory, 33 of the workgroup's 60 us -- per-phase clock stamps); masked positions read element 0
     float pv[4][16];
     const float *const pb = a.probs + (long)cid * SS * SS;
 #pragma unroll
@@ -620,7 +602,6 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_kernel(AttnArgs a)
         }
     }
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // (the staging only: __syncthreads would also wait for the loads above)
-    AT_STAMP(1);
     at_f32x16 ds[4];
 #pragma unroll
     for (int jt = 0; jt < 4; ++jt) {
@@ -662,7 +643,6 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_kernel(AttnArgs a)
             for (int e = 0; e < 16; ++e) ds[jt][e] = pv[jt][e] * (ds[jt][e] - rs[e]) * a.inv_sqrt_dk;      // 0 where masked
     }
     __syncthreads();
-    AT_STAMP(2);
     // ---- phase 2: dV[j][d] = sum_{i >= j} Pd[i][j] dO[i][d] for key rows j = 32w + r32
     const int jk = 32 * w + r32;
     {
@@ -683,7 +663,6 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_kernel(AttnArgs a)
         }
     }
     __syncthreads();
-    AT_STAMP(3);
     // ---- phase 3: dS -> PS
 #pragma unroll
     for (int jt = 0; jt < 4; ++jt)
@@ -692,7 +671,6 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_kernel(AttnArgs a)
             for (int e = 0; e < 16; ++e) PS[(32 * w + at_row(e, h2)) * AT_LP + 32 * jt + r32] = ds[jt][e];
         }
     __syncthreads();
-    AT_STAMP(4);
     // ---- phase 4a: dK[j][d] = sum_{i >= j} dS[i][j] Q[i][d]
     {
         at_f32x16 dkk;
@@ -711,7 +689,6 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_kernel(AttnArgs a)
             if (j < SS) a.dqkv[(row0 + j) * 3 * a.D + a.D + head * 32 + r32] = dkk[e];
         }
     }
-    AT_STAMP(5);
     // ---- phase 4b: dQ[i][d] = sum_{j <= i} dS[i][j] K[j][d]  (+ sum_m T[i][m] Krelpos[d][m])
     {
         at_f32x16 dq;
@@ -745,7 +722,6 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_kernel(AttnArgs a)
             if (i < SS) a.dqkv[(row0 + i) * 3 * a.D + head * 32 + r32] = dq[e];
         }
     }
-    AT_STAMP(6);
     // ---- phase 4c: dKrelpos^T[m][d] = sum_i T[i][m] Q[i][d] for m = 32w + r32
     if (rel) {
         at_f32x16 dr;
@@ -770,7 +746,6 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_kernel(AttnArgs a)
             if (m < SS) a.dkrel_part[((long)cid * 32 + r32) * SS + m] = dr[e];
         }
     }
-    AT_STAMP(7);
 }
 
 // one workgroup per sequence chunk of one head; loops over its query tiles.  dK, dV and dKrelpos accumulate
@@ -1052,37 +1027,10 @@ static int transformer_forward(const float *x, const float *const *prm, float *o
         aa.qkv = L.qkv[l]; aa.krel = p[P_KREL]; aa.probs = L.probs[l]; aa.ctx = L.ctx[l];
         aa.N = N; aa.S = S; aa.D = D; aa.dk = L.dk; aa.SS = SS; aa.chunks = L.chunks;
         aa.seed = lseed; aa.thresh = thresh; aa.scale = scale; aa.inv_sqrt_dk = 1.f / std::sqrt((float)L.dk);
-        static const bool attn_valu = getenv("CPC_ATTN_VALU") != nullptr;       // the VALU kernels, for A/B tests
-        if (L.dk == 32 && !attn_valu) {
+        if (L.dk == 32) {
             CPC_TRY(allow_lds_tr(attn_fwd_mfma_kernel, AT_FWD_LDS));
-#ifdef AT_STAMPS
-            static unsigned long long *stamps = nullptr;
-            const int nwg = N * TR_HEADS * L.chunks;
-            if (stamps == nullptr) CPC_CHECK_HIP(hipMalloc(&stamps, 65536 * 32 * sizeof(unsigned long long)));
-            aa.stamps = stamps;
-#endif
             hipLaunchKernelGGL(attn_fwd_mfma_kernel, dim3((unsigned)(N * TR_HEADS * L.chunks)), dim3(256), AT_FWD_LDS, st, aa);
             CPC_CHECK_LAUNCH("attn_fwd_mfma_kernel");
-#ifdef AT_STAMPS
-            {
-                static std::vector<unsigned long long> host(65536 * 32);
-                CPC_CHECK_HIP(hipStreamSynchronize(st));
-                const int nb = std::min(nwg, 65536);
-                CPC_CHECK_HIP(hipMemcpy(host.data(), stamps, (size_t)nb * 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-                for (int w = 0; w < 4; ++w) {
-                    double ph[6] = {0, 0, 0, 0, 0, 0};
-                    for (int b = 0; b < nb; ++b)
-                        for (int i = 0; i < 6; ++i) ph[i] += (double)(host[((size_t)b * 4 + w) * 8 + i + 1] - host[((size_t)b * 4 + w) * 8 + i]);
-                    double sw = 0;
-                    for (int b = 0; b < nb; ++b) sw += (double)(host[((size_t)b * 4 + w) * 8 + 7] - host[((size_t)b * 4 + w) * 8 + 3]);
-                    fprintf(stderr, "attn fwd stamps wave %d (us): load %.2f | q+S %.2f | R+skew %.2f | softmax %.2f (max, exp, sum sweeps %.2f) | PV + ctx %.2f | drain %.2f\n", w,
-                            ph[0] / nb * 0.01, ph[1] / nb * 0.01, ph[2] / nb * 0.01, ph[3] / nb * 0.01, sw / nb * 0.01, ph[4] / nb * 0.01, ph[5] / nb * 0.01);
-                }
-                unsigned long long first = ~0ull, last = 0;
-                for (int b = 0; b < nb; ++b) { first = std::min(first, host[(size_t)b * 32]); for (int w = 0; w < 4; ++w) last = std::max(last, host[((size_t)b * 4 + w) * 8 + 6]); }
-                fprintf(stderr, "attn fwd: %d workgroups, span %.1f us\n", nb, (double)(last - first) * 0.01);
-            }
-#endif
         } else {
             CPC_TRY(allow_lds_tr(attn_fwd_kernel, L.lds_fwd));
             const int tiles = (SS + TR_QT - 1) / TR_QT;
@@ -1199,33 +1147,9 @@ static int transformer_backward(const float *x, const float *const *prm, const f
         aa.dctx = db2; aa.dqkv = L.dqkv; aa.dkrel_part = L.krel_part;
         const int nchunk = N * TR_HEADS * L.chunks;
         int status = CPC_OK;
-        static const bool attn_valu = getenv("CPC_ATTN_VALU") != nullptr;
-        if (L.dk == 32 && !attn_valu) {
+        if (L.dk == 32) {
             status = allow_lds_tr(attn_bwd_mfma_kernel, AT_BWD_LDS);
-#ifdef AT_STAMPS
-            static unsigned long long *bstamps = nullptr;
-            if (bstamps == nullptr) CPC_CHECK_HIP(hipMalloc(&bstamps, 65536 * 32 * sizeof(unsigned long long)));
-            aa.stamps = bstamps;
-#endif
             if (status == CPC_OK) hipLaunchKernelGGL(attn_bwd_mfma_kernel, dim3((unsigned)nchunk), dim3(256), AT_BWD_LDS, st, aa);
-#ifdef AT_STAMPS
-            {
-                static std::vector<unsigned long long> host(65536 * 32);
-                CPC_CHECK_HIP(hipStreamSynchronize(st));
-                const int nb = std::min(nchunk, 65536);
-                CPC_CHECK_HIP(hipMemcpy(host.data(), bstamps, (size_t)nb * 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-                for (int w = 0; w < 4; ++w) {
-                    double ph[7] = {0, 0, 0, 0, 0, 0, 0};
-                    for (int b = 0; b < nb; ++b)
-                        for (int i = 0; i < 7; ++i) ph[i] += (double)(host[((size_t)b * 4 + w) * 8 + i + 1] - host[((size_t)b * 4 + w) * 8 + i]);
-                    fprintf(stderr, "attn bwd stamps wave %d (us): load %.2f | dPd + dS %.2f | dV %.2f | dS -> LDS %.2f | dK %.2f | dQ %.2f | dKrel %.2f\n", w,
-                            ph[0] / nb * 0.01, ph[1] / nb * 0.01, ph[2] / nb * 0.01, ph[3] / nb * 0.01, ph[4] / nb * 0.01, ph[5] / nb * 0.01, ph[6] / nb * 0.01);
-                }
-                unsigned long long first = ~0ull, last = 0;
-                for (int b = 0; b < nb; ++b) { first = std::min(first, host[(size_t)b * 32]); for (int w = 0; w < 4; ++w) last = std::max(last, host[((size_t)b * 4 + w) * 8 + 7]); }
-                fprintf(stderr, "attn bwd: %d workgroups, span %.1f us\n", nb, (double)(last - first) * 0.01);
-            }
-#endif
         } else
         switch (L.dk / 2) {
 #define TR_CASE(X) case X: status = allow_lds_tr(attn_bwd_kernel<X>, L.lds_bwd); \

@@ -376,7 +376,7 @@ int cpc_negidx_expand(const uint32_t *raw, int32_t *ext_idx, int batch, int seq_
  *   losses   [K]  mean_i(w_i * CE_i);  acc [K] = #(argmax == 0) / (b*W)
  * backward: dlosses [K] upstream gradient -> dc [b,T,dim_ar], dz [b,T,dim_enc],
  *           dwpred [K,dim_enc,dim_ar]  (all overwritten; dz is summed per row in a fixed order, so it
- *           is identical from run to run; CPC_NCE_ATOMIC=1 in the environment selects fp32 atomics)
+ *           is identical from run to run)
  * ------------------------------------------------------------------------------------------ */
 size_t cpc_infonce_saved_bytes(int b, int t, int k, int dim_ar, int dim_enc, int n_neg);
 size_t cpc_infonce_scratch_bytes(int b, int t, int k, int dim_ar, int dim_enc, int n_neg);

@@ -4,7 +4,7 @@ conv0 block of a rank's gradient differed slightly from run to run only when two
     python tools/load_determinism_probe.py [hidden=64] [steps=60] [out=gpurun_out/load_determinism.json]
 
 One measuring process: every training step, the encoder's backward library call is enqueued twice with the same inputs and
-the two sets of gradients are compared bit for bit (as tools/dp_conv0_probe.py does).  Beside it, one after the other:
+the two sets of gradients are compared bit for bit.  Beside it, one after the other:
 nothing / an independent training loop of the same model / a bf16 matmul loop (torch) / a device-to-device copy loop (torch)."""
 import json
 import os
