@@ -42,7 +42,7 @@ enum cpc_status {
 };
 
 int cpc_version(void);          /* 100 x major + minor; 105 = the entry points of round 5 (cpc_encoder_forward2 / backward2, cpc_coop_set_policy,
-                                  * cpc_recurrent_backward_calls, cpc_side_tail_wait) */
+                                  * cpc_recurrent_backward_calls, cpc_side_tail_wait); 107 = cpc_abx_dtw / cpc_abx_counts */
 const char *cpc_last_error(void);
 
 /* In-situ kernel timing for bench.py: when enabled, the launchers bracket each launch of the named
@@ -461,6 +461,33 @@ int cpc_window_gather(const float *audio, long total_samples, const long *offset
  * ------------------------------------------------------------------------------------------ */
 int cpc_adam_step(float *p, const float *g, float *m, float *v, long n, int step, float lr,
                   float beta1, float beta2, float eps, float grad_scale, cpc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * ABX phone discriminability (cpc/eval/ABX/abx_group_computation.py, dtw.pyx of the reference).
+ *
+ * Items are spans of frames in one fp32 buffer `frames` [total_frames][dp] (dp a multiple of 4; padding columns zero);
+ * item i is frames item_off[i] .. item_off[i] + item_len[i] - 1.  The work list is in CSR form over "segments": segment s
+ * compares x item seg_x[s] with the y items pair_y[seg_start[s] .. seg_start[s+1]-1]; pair p's result goes to out[p].
+ *
+ * cpc_abx_dtw: out[p] = DTW(x, y) / path length, as dtw.pyx:_dtw(normalized=True): frame distance
+ *   distance = CPC_ABX_COSINE     acos(clamp(<x_r, y_c>, -1, 1)) / pi       (inputs normalised by the caller)
+ *   distance = CPC_ABX_EUCLIDIAN  sqrt(sum_k (x_rk - y_ck)^2)
+ * in f32 (k-ordered fma chain); cost[i][j] = d[i][j] + min(up, diag, left); the path length follows the reference's
+ * backtrack (ties: diag, then left, then up).  Any item length >= 1.  path_len (optional, may be NULL) receives the length.
+ * max_len_x / max_len_y bound the x / y item lengths; scratch: cpc_abx_dtw_scratch_bytes (0 when every x item has <= 64
+ * frames).  A pair whose item index or length is out of range gets NaN (path length -1).
+ *
+ * cpc_abx_counts: triplet t has shape[5t .. 5t+4] = (nx, na, nb, a_off, b_off).  idx_a[a_off + i*na + j] is the pair index
+ * of dxa[i][j] (-1: excluded, the diagonal of a symmetric group), idx_b[b_off + i*nb + k] that of dxb[i][k].
+ *   lt[t] = #{(i,j,k): dxa[i][j] < dxb[i][k]},  eq[t] = #{(i,j,k): dxa[i][j] == dxb[i][k]}   (integers; nx*na*nb < 2^31)
+ * ------------------------------------------------------------------------------------------ */
+enum cpc_abx_distance { CPC_ABX_COSINE = 0, CPC_ABX_EUCLIDIAN = 1 };
+size_t cpc_abx_dtw_scratch_bytes(int n_seg, int max_len_x, int max_len_y);
+int cpc_abx_dtw(const float *frames, int dp, const int *item_off, const int *item_len, int n_items,
+                const int *seg_x, const int *seg_start, const int *pair_y, int n_seg, int max_len_x, int max_len_y,
+                int distance, float *out, int *path_len, void *scratch, size_t scratch_bytes, cpc_stream_t stream);
+int cpc_abx_counts(const float *dist, int n_pairs, const int *idx_a, const int *idx_b, const int *shape, int n_trip,
+                   int *lt, int *eq, cpc_stream_t stream);
 
 #ifdef __cplusplus
 }
