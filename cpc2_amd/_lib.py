@@ -114,6 +114,10 @@ SIGNATURES = {
     "cpc_abx_dtw": (c_int, [c_ptr, c_int, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr,
                             c_ptr, c_size_t, c_ptr]),
     "cpc_abx_counts": (c_int, [c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr]),
+    "cpc_kmeans_scratch_bytes": (c_size_t, [c_long, c_int, c_int]),
+    "cpc_kmeans_assign": (c_int, [c_ptr, c_long, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr]),
+    "cpc_kmeans_distances": (c_int, [c_ptr, c_long, c_int, c_ptr, c_int, c_ptr, c_ptr]),
+    "cpc_kmeans_accumulate": (c_int, [c_ptr, c_long, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_size_t, c_ptr]),
 }
 
 _lib = None

@@ -78,6 +78,42 @@ class CPCModule(torch.nn.Module):
         return torch.softmax(scores[self.n_pred], dim=1)
 
 
+def toOneHot(inputVector, nItems):
+    """[B, S] indices -> [B, S, nItems] int64 one-hot (:307-313)."""
+    batchSize, seqSize = inputVector.size()
+    out = torch.zeros((batchSize, seqSize, nItems), device=inputVector.device, dtype=torch.long)
+    out.scatter_(2, inputVector.view(batchSize, seqSize, 1), 1)
+    return out
+
+
+class ModelClusterCombined(torch.nn.Module):
+    """A feature maker followed by a clustering module (:118-147): outFormat "int" -> [B, S] cluster ids, "oneHot" ->
+    their one-hot [B, S, nk], "softmax" -> softmax of the negated sums of squares.  "int" and "oneHot" take the ids from
+    the cluster's fused assign kernel when it has one (the argmin of its distances, bit for bit)."""
+
+    def __init__(self, model, cluster, nk, outFormat):
+        if outFormat not in ['oneHot', 'int', 'softmax']:
+            raise ValueError(f'Invalid output format {outFormat}')
+        super(ModelClusterCombined, self).__init__()
+        self.model = model
+        self.cluster = cluster
+        self.nk = nk
+        self.outFormat = outFormat
+
+    def getDownsamplingFactor(self):
+        return self.model.getDownsamplingFactor()
+
+    def forward(self, data):
+        c_feature = self.model(data)
+        if self.outFormat == 'softmax':
+            return torch.nn.functional.softmax(-self.cluster(c_feature), dim=2)
+        if hasattr(self.cluster, "assign"):
+            pred = self.cluster.assign(c_feature)
+        else:
+            pred = self.cluster(c_feature).min(dim=2)[1]
+        return toOneHot(pred, self.nk) if self.outFormat == 'oneHot' else pred
+
+
 def get_module(i_module):
     """The CPCModel under any stack of DataParallel / DistributedDataParallel / FeatureModule wrappers (:286-293)."""
     while True:
@@ -116,13 +152,26 @@ def getCheckpointData(pathDir):
     return os.path.abspath(os.path.join(pathDir, newest)), logs, args
 
 
-def loadModel(pathCheckpoints, loadStateDict=True):
+def loadArgs(args, locArgs, forbiddenAttr=None):
+    """Copy every attribute of locArgs onto args, except those in forbiddenAttr (:150-156)."""
+    for k, v in vars(locArgs).items():
+        if forbiddenAttr is None or k not in forbiddenAttr:
+            setattr(args, k, v)
+
+
+def loadModel(pathCheckpoints, loadStateDict=True, updateConfig=None):
     """CPCModel built from the run's checkpoint_args.json, `gEncoder` weights loaded (:238-283; one checkpoint, no
-    nested `load` chains, no ConcatenatedModel).  Returns (model, hiddenGar, hiddenEncoder)."""
+    nested `load` chains, no ConcatenatedModel).  Returns (model, hiddenGar, hiddenEncoder).  updateConfig (a namespace)
+    overrides the run's args before the model is built, e.g. nLevelsGRU=1 on a 2-layer run: the state dict is loaded with
+    strict=False, so the model then gives layer 0's output."""
     if len(pathCheckpoints) != 1:
         raise NotImplementedError("ConcatenatedModel (several checkpoints) is not on the MI355X path")
     (path,) = pathCheckpoints
     _, _, run_args = getCheckpointData(os.path.dirname(path))
+    if updateConfig is not None:
+        print("Updating the configuration file with ")
+        print(f"{json.dumps(vars(updateConfig), indent=4, sort_keys=True)}")
+        loadArgs(run_args, updateConfig)
     model = CPCModel(getEncoder(run_args), getAR(run_args))
     if loadStateDict:
         model.load_state_dict(torch.load(path, "cpu")["gEncoder"], strict=False)

@@ -42,7 +42,8 @@ enum cpc_status {
 };
 
 int cpc_version(void);          /* 100 x major + minor; 105 = the entry points of round 5 (cpc_encoder_forward2 / backward2, cpc_coop_set_policy,
-                                  * cpc_recurrent_backward_calls, cpc_side_tail_wait); 107 = cpc_abx_dtw / cpc_abx_counts */
+                                  * cpc_recurrent_backward_calls, cpc_side_tail_wait); 107 = cpc_abx_dtw / cpc_abx_counts;
+                                  * 108 = cpc_kmeans_scratch_bytes / cpc_kmeans_assign / cpc_kmeans_distances / cpc_kmeans_accumulate */
 const char *cpc_last_error(void);
 
 /* In-situ kernel timing for bench.py: when enabled, the launchers bracket each launch of the named
@@ -488,6 +489,30 @@ int cpc_abx_dtw(const float *frames, int dp, const int *item_off, const int *ite
                 int distance, float *out, int *path_len, void *scratch, size_t scratch_bytes, cpc_stream_t stream);
 int cpc_abx_counts(const float *dist, int n_pairs, const int *idx_a, const int *idx_b, const int *shape, int n_trip,
                    int *lt, int *eq, cpc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * k-means on features (cpc/clustering/clustering.py of the reference).  x [n][d] rows, ck [k][d] centroids, all fp32 DEVICE
+ * pointers, row-major and contiguous.  Limits: 0 <= n < 2^31, 1 <= d <= 4096, 1 <= k <= 2^20; a call outside them returns
+ * CPC_ERR_INVALID with a message.
+ *
+ * Every distance is the f32 chain over ascending feature index f:  t = x[f] - c[f]; acc = fmaf(t, t, acc)  (acc from 0),
+ * never the |x|^2 - 2 x.c + |c|^2 expansion.  cpc_kmeans_assign and cpc_kmeans_distances compute it identically, so
+ * index[i] == argmin_j dist[i][j] exactly.
+ *
+ * cpc_kmeans_assign: index[i] (int32) = the centroid of least distance, the LOWEST index among equal minima (torch.argmin);
+ *   min_sq[i] = that distance (min_sq may be NULL).  The [n][k] matrix is never formed.
+ * cpc_kmeans_distances: dist[i][j] = the distance of row i to centroid j ([n][k], long offsets).
+ * cpc_kmeans_accumulate: running per-cluster sums and counts:  sums[c][:] += sum of the rows with index == c,
+ *   counts[c] += their number (int64).  A row whose index is outside [0, k) is skipped and counted nowhere; a cluster with
+ *   no row is left untouched.  No float atomic: rows are bucketed stably (ascending row order in each cluster), summed in
+ *   chunks of 256 rows, and the chunks added in order, so the result is bitwise reproducible.  scratch:
+ *   cpc_kmeans_scratch_bytes(n, d, k) bytes (0 for sizes outside the limits).
+ * ------------------------------------------------------------------------------------------ */
+size_t cpc_kmeans_scratch_bytes(long n, int d, int k);
+int cpc_kmeans_assign(const float *x, long n, int d, const float *ck, int k, int *index, float *min_sq, cpc_stream_t stream);
+int cpc_kmeans_distances(const float *x, long n, int d, const float *ck, int k, float *dist, cpc_stream_t stream);
+int cpc_kmeans_accumulate(const float *x, long n, int d, const int *index, int k, float *sums, int64_t *counts,
+                          void *scratch, size_t scratch_bytes, cpc_stream_t stream);
 
 #ifdef __cplusplus
 }
