@@ -4,7 +4,9 @@ Mirrors /root/reference/cpc/criterion/criterion.py: PredictionNetwork (:97-173, 
 :144-150), BaseCriterion (:176-183), NoneCriterion (:185-191), CPCUnsupersivedCriterion (:193-363)
 -- same constructor/forward signatures, attribute names and state-dict keys
 (`wPrediction.predictors.{k}.weight`).  The K candidate tensors of sampleClean (:237-286) are never
-materialised: the fused HIP kernel gathers negatives on the fly from the index stream.
+materialised: the fused HIP kernel gathers negatives on the fly from the index stream.  The supervised probe criteria of the
+linear-separability evaluation (SpeakerCriterion, PhoneCriterion, CTCPhoneCriterion, criterion.py:366-495) sit at the end, on
+the loss heads of csrc/probe.hip.
 
 Negative indices are drawn on the HOST with the same MT19937 stream torch's CPU generator would
 produce (the reference's CPU path); by default the criterion consumes -- and advances -- torch's
@@ -942,3 +944,209 @@ class CPCUnsupersivedCriterion(BaseCriterion):
     def _needs_modules(self):
         net = self.wPrediction
         return net.rnnMode in ('transformer_multi', 'transformer', 'LSTM', 'RNN') or (net.dropout is not None and self.training)
+
+
+# --------------------------------------------------------------------------- supervised probe heads (criterion.py:366-538)
+def _rows(x, last_frame):
+    """(tensor, byte offset, row stride, rows, width) of the rows a head reads: every frame of x [..., H], or with last_frame
+    the frame S - 1 of every sequence of x [B, S, H], read in place (lda = S * H)."""
+    if last_frame:
+        b, s, h = x.shape
+        return x, (s - 1) * h * 4, s * h, b, h
+    return x, 0, x.shape[-1], x.numel() // x.shape[-1], x.shape[-1]
+
+
+class _ProbeHeadFn(torch.autograd.Function):
+    """loss of logits = x W^T + b on the library's kernels: cpc_gemm_nt (with the bias) for the logits, then one pass of
+    cpc_probe_xent (kind "xent": labels [rows]; returns loss [1] and the accuracy, double [1]) or cpc_probe_ctc (kind "ctc":
+    targets [B, maxL] + lengths [B] from collapseLabelChain; the accuracy is 0).  The pass leaves dlogits in place of the
+    logits when a gradient is wanted; the backward scales them by the incoming gradient, sums them for db and multiplies them
+    out with cpc_gemm_tn (dW) and cpc_gemm_nt (dX)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, kind, labels, lengths, last_frame, want_grad):
+        require_gpu(x, weight, bias, labels, lengths)
+        lib = _lib.load()
+        x = f32c(x)
+        w = f32c(weight.detach())
+        bvec = f32c(bias.detach())
+        _, off, lda, n, h = _rows(x, last_frame)
+        c = w.shape[0]
+        if w.shape[1] != h:
+            raise ValueError(f"feature width {h} does not match the classifier's {tuple(w.shape)}")
+        dev = x.device
+        logits = torch.empty(n, c, dtype=torch.float32, device=dev)
+        xp = ctypes.c_void_p(x.data_ptr() + off)
+        check(lib.cpc_gemm_nt(xp, lda, ptr(w), h, ptr(logits), c, ptr(bvec), n, c, h, stream_ptr(dev)), "gemm_nt")
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        acc = None
+        if kind == "xent":
+            labels = labels.reshape(-1).to(torch.int64).contiguous()
+            if labels.numel() != n:
+                raise ValueError(f"{labels.numel()} labels for {n} rows")
+            nll = torch.empty(n, dtype=torch.float32, device=dev)
+            correct = torch.empty(n, dtype=torch.int32, device=dev)
+            acc = torch.empty(1, dtype=torch.float64, device=dev)
+            check(lib.cpc_probe_xent(ptr(logits), ptr(labels), n, c, int(want_grad), ptr(nll), ptr(correct), ptr(loss), ptr(acc),
+                                     stream_ptr(dev)), "probe_xent")
+        else:
+            b, t = x.shape[0], x.shape[1]
+            acc = torch.zeros(1, dtype=torch.float32, device=dev)      # (criterion.py:489: avgPER = 0)
+            nll = torch.empty(b, dtype=torch.float32, device=dev)
+            nb = lib.cpc_probe_ctc_scratch_bytes(b, t, labels.shape[1])
+            if nb == 0:
+                check(-1, "probe_ctc shape query")
+            check(lib.cpc_probe_ctc(ptr(logits), b, t, c, ptr(labels), labels.shape[1], ptr(lengths), ptr(nll), ptr(loss),
+                                    ptr(logits) if want_grad else None, ptr(scratch(nb, dev)), nb, stream_ptr(dev)), "probe_ctc")
+        ctx.save_for_backward(x, w, logits if want_grad else None)
+        ctx.geom = (off, lda, n, h, c, last_frame)
+        ctx.params = (weight, bias)
+        ctx.mark_non_differentiable(acc)
+        return loss, acc
+
+    @staticmethod
+    def backward(ctx, dloss, _dacc):
+        lib = _lib.load()
+        x, w, dlogits = ctx.saved_tensors
+        if dlogits is None:
+            raise RuntimeError("the probe head ran without a gradient (want_grad=False) and cannot be differentiated")
+        off, lda, n, h, c, last_frame = ctx.geom
+        dev = x.device
+        st = stream_ptr(dev)
+        dw, db = grad_buffers(ctx.params)
+        nb = lib.cpc_probe_xent_backward_scratch_bytes(c)
+        check(lib.cpc_probe_head_backward(ptr(dlogits), n, c, ptr(f32c(dloss.reshape(1))), ptr(db), ptr(scratch(nb, dev)), nb, st),
+              "probe_head_backward")
+        xp = ctypes.c_void_p(x.data_ptr() + off)
+        nt = lib.cpc_gemm_tn_scratch_bytes(c, h, n)
+        check(lib.cpc_gemm_tn(ptr(dlogits), c, xp, lda, ptr(dw), h, c, h, n, ptr(scratch(nt, dev)), nt, st), "gemm_tn")
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.zeros_like(x) if last_frame else torch.empty_like(x)
+            wt = w.t().contiguous()                                     # [H, C]: the NT form's B operand of dx = dlogits W
+            check(lib.cpc_gemm_nt(ptr(dlogits), c, ptr(wt), c, ctypes.c_void_p(dx.data_ptr() + off), lda, None, n, h, c, st),
+                  "gemm_nt")
+        return dx, dw, db, None, None, None, None, None
+
+
+class _AffineFn(torch.autograd.Function):
+    """y = x W^T + b on the library's GEMMs (the hidden layers of PhoneCriterion with nLayers > 1)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        require_gpu(x, weight, bias)
+        lib = _lib.load()
+        x2 = f32c(x).reshape(-1, x.shape[-1])
+        w = f32c(weight.detach())
+        m, k = x2.shape
+        n = w.shape[0]
+        y = torch.empty(m, n, dtype=torch.float32, device=x.device)
+        check(lib.cpc_gemm_nt(ptr(x2), k, ptr(w), k, ptr(y), n, ptr(f32c(bias.detach())), m, n, k, stream_ptr(x.device)), "gemm_nt")
+        ctx.save_for_backward(x2, w)
+        ctx.xshape = x.shape
+        ctx.params = (weight, bias)
+        return y.view(*x.shape[:-1], n)
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        x2, w = ctx.saved_tensors
+        m, k = x2.shape
+        n = w.shape[0]
+        dev = dy.device
+        st = stream_ptr(dev)
+        dy2 = f32c(dy).reshape(m, n)
+        dw, db = grad_buffers(ctx.params)
+        nb = lib.cpc_probe_xent_backward_scratch_bytes(n)
+        check(lib.cpc_probe_head_backward(ptr(dy2), m, n, None, ptr(db), ptr(scratch(nb, dev)), nb, st), "probe_head_backward")
+        nt = lib.cpc_gemm_tn_scratch_bytes(n, k, m)
+        check(lib.cpc_gemm_tn(ptr(dy2), n, ptr(x2), k, ptr(dw), k, n, k, m, ptr(scratch(nt, dev)), nt, st), "gemm_tn")
+        dx = torch.empty(m, k, dtype=torch.float32, device=dev)
+        wt = w.t().contiguous()
+        check(lib.cpc_gemm_nt(ptr(dy2), n, ptr(wt), n, ptr(dx), k, None, m, k, n, st), "gemm_nt")
+        return dx.view(ctx.xshape), dw, db
+
+
+def _wants_grad(*tensors):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
+def _linear_layers(module):
+    """The nn.Linear layers of a classifier (one Linear, or the reference's Sequential(Linear, ReLU, Linear, ...))."""
+    return [module] if isinstance(module, nn.Linear) else [m for m in module if isinstance(m, nn.Linear)]
+
+
+class SpeakerCriterion(BaseCriterion):
+    """criterion.py:366-386: a linear classifier on the LAST frame of cFeature (read in place); loss = cross-entropy, acc =
+    (argmax == label).double().mean() -- both [1, 1]."""
+
+    def __init__(self, dimEncoder, nSpeakers):
+        super(SpeakerCriterion, self).__init__()
+        self.linearSpeakerClassifier = nn.Linear(dimEncoder, nSpeakers)
+
+    def forward(self, cFeature, otherEncoded, label):
+        lin = self.linearSpeakerClassifier
+        loss, acc = _ProbeHeadFn.apply(cFeature, lin.weight, lin.bias, "xent", label, None, True,
+                                       _wants_grad(cFeature, lin.weight, lin.bias))
+        return loss.view(1, -1), acc.view(1, -1)
+
+
+class PhoneCriterion(BaseCriterion):
+    """criterion.py:418-457: frame-aligned phones; key PhoneCriterionClassifier.{weight,bias} (one layer) or
+    PhoneCriterionClassifier.{0,2,...}.* (Linear, ReLU, Linear, ...).  The hidden layers' ReLU is torch.relu; every product and
+    the loss head are the library's kernels."""
+
+    def __init__(self, dimEncoder, nPhones, onEncoder, nLayers=1):
+        super(PhoneCriterion, self).__init__()
+        if nLayers == 1:
+            self.PhoneCriterionClassifier = nn.Linear(dimEncoder, nPhones)
+        else:
+            outLayers = [nn.Linear(dimEncoder, nPhones)]
+            for _ in range(nLayers - 1):
+                outLayers.append(nn.ReLU())
+                outLayers.append(nn.Linear(nPhones, nPhones))
+            self.PhoneCriterionClassifier = nn.Sequential(*outLayers)
+        self.onEncoder = onEncoder
+
+    def _hidden(self, features):
+        """the input of the last Linear: the features themselves, or the hidden layers' output"""
+        layers = _linear_layers(self.PhoneCriterionClassifier)
+        for lin in layers[:-1]:
+            features = torch.relu(_AffineFn.apply(features, lin.weight, lin.bias))
+        return features, layers[-1]
+
+    def forward(self, cFeature, otherEncoded, label):
+        features = otherEncoded if self.onEncoder else cFeature
+        hidden, lin = self._hidden(features)
+        loss, acc = _ProbeHeadFn.apply(hidden, lin.weight, lin.bias, "xent", label, None, False,
+                                       _wants_grad(hidden, lin.weight, lin.bias))
+        return loss.view(1, -1), acc.view(1, -1)
+
+    def getPrediction(self, cFeature):
+        hidden, lin = self._hidden(cFeature)
+        return _AffineFn.apply(hidden, lin.weight, lin.bias)
+
+
+class CTCPhoneCriterion(BaseCriterion):
+    """criterion.py:460-495: nPhones + 1 outputs (BLANK_LABEL = nPhones), nn.CTCLoss(blank=nPhones, zero_infinity=True) of the
+    log-softmax over the S frames, against the collapsed frame labels of every window.  The logged accuracy is 0."""
+
+    def __init__(self, dimEncoder, nPhones, onEncoder):
+        super(CTCPhoneCriterion, self).__init__()
+        self.PhoneCriterionClassifier = nn.Linear(dimEncoder, nPhones + 1)
+        self.onEncoder = onEncoder
+        if onEncoder:
+            raise ValueError("On encoder version not implemented yet")
+        self.BLANK_LABEL = nPhones
+
+    def getPrediction(self, cFeature):
+        lin = self.PhoneCriterionClassifier
+        return _AffineFn.apply(cFeature, lin.weight, lin.bias)
+
+    def forward(self, cFeature, otherEncoded, label):
+        from .seq_alignment import collapse_padded
+        lin = self.PhoneCriterionClassifier
+        targets, sizes = collapse_padded(label.to(cFeature.device))
+        loss, acc = _ProbeHeadFn.apply(cFeature, lin.weight, lin.bias, "ctc", targets, sizes, False,
+                                       _wants_grad(cFeature, lin.weight, lin.bias))
+        return loss.view(1, -1), acc.view(1, -1)

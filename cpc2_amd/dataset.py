@@ -10,10 +10,13 @@ by one gather kernel (cpc_window_gather); the host only produces b int64 offsets
 by the library's own FLAC / WAV readers (cpc2_amd/audio.py).
 
 Signal-quality side files (per-file snr / c50 estimates, dataset.py:69-77,106-120,257-281) are read too and come out as
-the third element of a batch.  Not on this path: data augmentation (sox / WavAugment), phone labels.
+the third element of a batch.  Frame-level phone labels (parseSeqLabels, dataset.py:97-100,242-245,267-269) replace the
+speaker label when given: a pack's labels go to the device once and a batch's [b, sizeWindow // step] labels are gathered there
+from the window offsets.  Not on this path: data augmentation (sox / WavAugment).
 Without augmentation the reference yields past == future (dataset.py:308-321): batches are returned as an
 expanded [b, 2, 1, W] view whose two halves alias, which cpcStep(dedup=True) can exploit.
 """
+import copy
 import os
 import random
 from pathlib import Path
@@ -50,6 +53,19 @@ def filterSeqs(pathTxt, seqCouples):
         wanted = {p.strip() for p in f.readlines() if p.strip()}
     seqCouples = sorted(seqCouples, key=lambda x: os.path.basename(os.path.splitext(x[1])[0]))
     return [x for x in seqCouples if os.path.basename(os.path.splitext(x[1])[0]) in wanted]
+
+
+def parseSeqLabels(pathLabels):
+    """({"step": 160, name: [labels]}, maxLabel + 1) over every line of a label file `name l0 l1 ...` -- dataset.py:951-960."""
+    with open(pathLabels, 'r') as f:
+        lines = f.readlines()
+    output = {"step": 160}          # one label per 160 samples (10 ms at 16 kHz)
+    maxPhone = 0
+    for line in lines:
+        data = line.split()
+        output[data[0]] = [int(x) for x in data[1:]]
+        maxPhone = max(maxPhone, max(output[data[0]]))
+    return output, maxPhone + 1
 
 
 def shard_for_rank(files, rank, world_size):
@@ -120,8 +136,6 @@ class AudioBatchData:
                  MAX_SIZE_LOADED=4000000000, transform=None, augment_past=False, augment_future=False,
                  augmentation=None, keep_temporality=True, past_equal_future=False, signal_quality_path=None,
                  signal_quality_step=1600, signal_quality_mode=None, device=None):
-        if phoneLabelsDict is not None:
-            raise NotImplementedError("phone labels are not on the MI355X feeder path")
         if transform is not None or augment_past or augment_future or augmentation is not None:
             raise NotImplementedError("audio augmentation is not on the MI355X feeder path")
         self.MAX_SIZE_LOADED = MAX_SIZE_LOADED
@@ -133,7 +147,10 @@ class AudioBatchData:
         self.device = torch.device(device) if device is not None else \
             torch.device("cuda" if torch.cuda.is_available() else "cpu")
         self.doubleLabels = False
-        self.phoneSize = 0
+        # dataset.py:97-102: phoneSize samples per label, phoneStep labels per window
+        self.phoneSize = 0 if phoneLabelsDict is None else phoneLabelsDict["step"]
+        self.phoneStep = 0 if phoneLabelsDict is None else sizeWindow // self.phoneSize
+        self.phoneLabelsDict = copy.deepcopy(phoneLabelsDict)
         # signal-quality estimates (dataset.py:69-77,106-120): one .pt per audio file under signal_quality_path (a list of
         # tensors that concatenate along dim 1 to [frames, 2] = (snr, c50), one frame per signal_quality_step samples) and
         # min_max.csv with the normalisation bounds
@@ -161,6 +178,13 @@ class AudioBatchData:
             self.min_c50, self.max_c50 = float(bounds["min_c50"]), float(bounds["max_c50"])
         except (KeyError, ValueError):
             raise ValueError("min_max.csv should contain the following keys: min_snr, max_snr, min_c50, max_c50.")
+
+    def resetPhoneLabels(self, newPhoneLabels, step):
+        """dataset.py:123-127: new labels (and step) from the next pack on."""
+        self.phoneSize = step
+        self.phoneStep = self.sizeWindow // self.phoneSize
+        self.phoneLabelsDict = copy.deepcopy(newPhoneLabels)
+        self.loadNextPack()
 
     def _quality_file(self, audio_path):
         rel = os.path.relpath(str(audio_path), str(self.dbPath))
@@ -233,6 +257,14 @@ class AudioBatchData:
         where every sequence (seqLabel) and every speaker index up to the last one present (speakerLabel) begins."""
         import numpy as np
         ordered = sorted(nextData, key=lambda item: (item[0], item[1]))
+        if self.phoneLabelsDict is not None:
+            # dataset.py:242-245: a file's audio is cut to its labels (a file without labels: the reference's KeyError); the pack's
+            # labels follow in the same order
+            labels = [self.phoneLabelsDict[item[1]] for item in ordered]
+            ordered = [item[:2] + (item[2][:len(lab) * self.phoneSize],) + item[3:] for item, lab in zip(ordered, labels)]
+            self.phoneLabels = [x for lab in labels for x in lab]
+            self.phoneLabelsDevice = torch.tensor(self.phoneLabels, dtype=torch.int64).to(self.device)
+            self._phone_range = torch.arange(self.phoneStep, dtype=torch.int64, device=self.device)
         sizes = np.array([item[2].size(0) for item in ordered], dtype=np.int64)
         who = np.array([item[0] for item in ordered], dtype=np.int64)
         valid = set(self.speakers)
@@ -251,6 +283,18 @@ class AudioBatchData:
             self.data_quality = torch.cat((q, torch.mean(q, dim=1).view(-1, 1)), dim=1).to(self.device)
 
     # ---- accessors
+    def getPhonem(self, idx):
+        """dataset.py:267-269: the labels of the window at sample offset idx (idx need not be a multiple of the step)."""
+        idPhone = idx // self.phoneSize
+        return self.phoneLabels[idPhone:(idPhone + self.phoneStep)]
+
+    def phonemes_from(self, off_dev):
+        """getPhonem of every offset of a device int64 tensor, gathered on the device: [b, phoneStep] int64.  (Window offsets stay
+        within data.numel() - sizeWindow, so the last index is at most len(labels) - 1; the clamp only guards the gather.)"""
+        first = torch.div(off_dev, self.phoneSize, rounding_mode="floor").unsqueeze(1)
+        idx = (first + self._phone_range).clamp_(max=len(self.phoneLabels) - 1)
+        return self.phoneLabelsDevice[idx]
+
     def getSpeakerLabel(self, idx):
         import bisect
         return bisect.bisect_right(self.speakerLabel, idx) - 1
@@ -358,13 +402,18 @@ class _AudioLoader:
                 labels = torch.bucketize(offs, table, right=True) - 1
                 for i, batch in enumerate(batches):
                     off_dev, label = offs[i, :len(batch)], labels[i, :len(batch)]
+                    if d.phoneSize > 0:                      # dataset.py:298-301: the phone labels replace the speaker's
+                        label = d.phonemes_from(off_dev)
                     if d.signal_quality_path is not None:    # dataset.py:327-330: a third element per sample
                         yield d.windows_from(off_dev), label, torch.stack([d.getSignalQuality(o) for o in batch])
                     else:
                         yield d.windows_from(off_dev), label
             else:
                 for batch in batches:
-                    label = torch.tensor([d.getSpeakerLabel(o) for o in batch], dtype=torch.long, device=d.device)
+                    if d.phoneSize > 0:
+                        label = torch.tensor([d.getPhonem(o) for o in batch], dtype=torch.long, device=d.device)
+                    else:
+                        label = torch.tensor([d.getSpeakerLabel(o) for o in batch], dtype=torch.long, device=d.device)
                     if d.signal_quality_path is not None:
                         yield d.windows(batch), label, torch.stack([d.getSignalQuality(o) for o in batch])
                     else:

@@ -8,6 +8,8 @@ Mirrors (semantics, names) /root/reference/cpc/train.py:27-59 (getCriterion), :7
     HIP Adam launch and data parallelism is one RCCL all-reduce per step (instead of DDP buckets);
   * per-step losses stay on the device; the host reads them every `loggingStep` steps only.
 """
+import copy
+import json
 import time
 
 import numpy as np
@@ -166,6 +168,40 @@ def buildOptimizer(cpcModel, cpcCriterion, lr=2e-4, beta1=0.9, beta2=0.999, epsi
     """train.py:472-479: criterion parameters first, then model parameters."""
     g_params = list(cpcCriterion.parameters()) + list(cpcModel.parameters())
     return FlatAdam(g_params, lr=lr, betas=(beta1, beta2), eps=epsilon)
+
+
+# --------------------------------------------------------------------------- logs (cpc/utils/misc.py:25-60)
+def save_logs(data, pathLogs):
+    with open(pathLogs, 'w') as file:
+        json.dump(data, file, indent=2)
+
+
+def update_logs(logs, logStep, prevlogs=None):
+    """Every entry (minus prevlogs') divided by logStep.  The callers pass the LAST batch index, i.e. the number of batches
+    minus 1: with one batch numpy divides by zero (inf / nan and a warning, no exception), as in the reference."""
+    out = {}
+    for key in logs:
+        out[key] = copy.deepcopy(logs[key])
+        if prevlogs is not None:
+            out[key] -= prevlogs[key]
+        out[key] /= logStep
+    return out
+
+
+def show_logs(text, logs):
+    print("")
+    print('-' * 50)
+    print(text)
+    for key in logs:
+        if key == "iter":
+            continue
+        nPredicts = logs[key].shape[0]
+        strSteps = ['Step'] + [str(s) for s in range(1, nPredicts + 1)]
+        formatCommand = ' '.join(['{:>16}' for x in range(nPredicts + 1)])
+        print(formatCommand.format(*strSteps))
+        strLog = [key] + ["{:10.6f}".format(s) for s in logs[key]]
+        print(formatCommand.format(*strLog))
+    print('-' * 50)
 
 
 # --------------------------------------------------------------------------- learning-rate schedule

@@ -43,7 +43,8 @@ enum cpc_status {
 
 int cpc_version(void);          /* 100 x major + minor; 105 = the entry points of round 5 (cpc_encoder_forward2 / backward2, cpc_coop_set_policy,
                                   * cpc_recurrent_backward_calls, cpc_side_tail_wait); 107 = cpc_abx_dtw / cpc_abx_counts;
-                                  * 108 = cpc_kmeans_scratch_bytes / cpc_kmeans_assign / cpc_kmeans_distances / cpc_kmeans_accumulate */
+                                  * 108 = cpc_kmeans_scratch_bytes / cpc_kmeans_assign / cpc_kmeans_distances / cpc_kmeans_accumulate;
+                                  * 109 = cpc_probe_xent / cpc_probe_head_backward / cpc_probe_ctc / cpc_probe_collapse (+ scratch queries) */
 const char *cpc_last_error(void);
 
 /* In-situ kernel timing for bench.py: when enabled, the launchers bracket each launch of the named
@@ -513,6 +514,37 @@ int cpc_kmeans_assign(const float *x, long n, int d, const float *ck, int k, int
 int cpc_kmeans_distances(const float *x, long n, int d, const float *ck, int k, float *dist, cpc_stream_t stream);
 int cpc_kmeans_accumulate(const float *x, long n, int d, const int *index, int k, float *sums, int64_t *counts,
                           void *scratch, size_t scratch_bytes, cpc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Loss heads of the linear-separability probe (cpc/eval/linear_separability.py and the supervised criteria of
+ * cpc/criterion/criterion.py of the reference).  All pointers are DEVICE pointers, row-major and contiguous; labels, targets and
+ * lengths are int64 (torch.long).  No float atomic: every result is bitwise reproducible.  The logits come from cpc_gemm_nt
+ * (with its bias), the weight and feature gradients from cpc_gemm_tn / cpc_gemm_nt.
+ *
+ * cpc_probe_xent: softmax cross-entropy of logits [n][c] (1 <= c <= 2^20) against labels [n]:  nll[i] = lse_i - x[i][label_i],
+ *   correct[i] = (argmax_i == label_i) with the LOWEST index among equal maxima (predictions.max(1)[1]),
+ *   loss[0] = sum_i nll[i] / n (fixed-order f32 sum), acc[0] = (number correct) / n in double.  want_grad != 0: the logits
+ *   are overwritten by dlogits = (softmax - onehot) / n.  A label outside [0, c) gives nll NaN and counts as wrong.
+ * cpc_probe_head_backward: dlogits [n][c] *= dloss[0] when dloss is not NULL (the loss's incoming gradient, read on the
+ *   device), then db[j] = sum_i dlogits[i][j] (fixed order) when db is not NULL.  scratch: cpc_probe_xent_backward_scratch_bytes(c).
+ * cpc_probe_ctc: nn.CTCLoss(blank = k - 1, reduction = 'mean', zero_infinity = True) of log_softmax(logits) for logits
+ *   [b][t][k] (t <= 1024, 2 <= k <= 65536), every input length t, targets [b][max_l] (max_l <= t, padding ignored) and
+ *   lengths [b]:  nll[i] = -log p_i (0 when no alignment exists), loss[0] = (sum_i nll[i] / max(L_i, 1)) / b.  dlogits (may be
+ *   NULL, may alias logits) = (softmax - occupancy) / (b * max(L_i, 1)), 0 for an infeasible sequence.  A length outside
+ *   [0, max_l] or a label outside [0, k - 1) gives that sequence NaN loss and gradient.  alpha and beta are computed in f64;
+ *   scratch: cpc_probe_ctc_scratch_bytes(b, t, max_l) (f64 [b][t][2 max_l + 1]; 0 for sizes outside the limits).
+ * cpc_probe_collapse: collapseLabelChain (cpc/criterion/seq_alignment.py) of labels [b][t]: consecutive repeats removed,
+ *   out [b][ldo] (ldo >= t) zero padded, lengths [b].
+ * ------------------------------------------------------------------------------------------ */
+int cpc_probe_xent(float *logits, const int64_t *labels, long n, int c, int want_grad, float *nll, int *correct, float *loss,
+                   double *acc, cpc_stream_t stream);
+size_t cpc_probe_xent_backward_scratch_bytes(int c);
+int cpc_probe_head_backward(float *dlogits, long n, int c, const float *dloss, float *db, void *scratch, size_t scratch_bytes,
+                            cpc_stream_t stream);
+size_t cpc_probe_ctc_scratch_bytes(int b, int t, int max_l);
+int cpc_probe_ctc(const float *logits, int b, int t, int k, const int64_t *targets, int max_l, const int64_t *lengths, float *nll,
+                  float *loss, float *dlogits, void *scratch, size_t scratch_bytes, cpc_stream_t stream);
+int cpc_probe_collapse(const int64_t *labels, int b, int t, int64_t *out, long ldo, int64_t *lengths, cpc_stream_t stream);
 
 #ifdef __cplusplus
 }
