@@ -7,6 +7,10 @@ iterator (same order, same random draws), deduplicates the (x item, y item) pair
 kernels per chunk: cpc_abx_dtw (frame distances + DTW of every pair) and cpc_abx_counts (the integer counts of
 dxa < dxb and dxa == dxb per triplet).  The host forms theta from the counts with the reference's float32 arithmetic.
 There is no CPU path: tensors must be on the GPU, and the scores are computed there whatever device the features are on.
+
+A dataset of quantized units (abx_iterators.ABXUnitLoader: one unit id per frame) takes the same plan, pair lists and
+counts, with cpc_abx_dtw_units in place of cpc_abx_dtw: the frame distance of two one-hot rows takes two values, computed
+once on the host by unit_frame_distances, and the one-hot matrix is never built.
 """
 import math
 
@@ -14,6 +18,7 @@ import numpy as np
 import torch
 
 from ... import _lib
+from . import abx_iterators as abx_it
 
 COSINE, EUCLIDIAN = 0, 1
 # index-list entries (Nx*Na + Nx*Nb per triplet) per chunk of triplets; bounds the device memory of a chunk (index lists,
@@ -77,6 +82,10 @@ class _Items:
         self.lens_host = np.asarray(lens_host, dtype=np.int64)
         self.n = int(self.lens_host.shape[0])
 
+    @property
+    def device(self):
+        return self.frames.device
+
     @staticmethod
     def from_padded(groups, device):
         """Items from padded [N, S, D] tensors and their sizes, in order."""
@@ -96,25 +105,89 @@ class _Items:
                       torch.tensor(lens, dtype=torch.int32, device=device), lens)
 
 
-def _dtw_pairs(items, px, py, code):
-    """DTW of the pairs (px[p], py[p]) (item indices, sorted by px) on the device: (values [n] fp32, path lengths)."""
-    dev = items.frames.device
-    n = int(px.shape[0])
+class _UnitItems:
+    """Items of unit ids on the device: units [total_frames] int32, frame offsets and lengths (int32), host copies of the
+    lengths, and the two frame distances {distance code: (d_same, d_diff)} of unit_frame_distances."""
+
+    def __init__(self, units, off, lens, lens_host, distances):
+        self.units, self.off, self.lens = units, off, lens
+        self.lens_host = np.asarray(lens_host, dtype=np.int64)
+        self.n = int(self.lens_host.shape[0])
+        self.distances = distances
+
+    @property
+    def device(self):
+        return self.units.device
+
+
+def unit_frame_distances(n_units, normalize, distance_function):
+    """(d_same, d_diff): the frame distance between two equal and two different one-hot rows of n_units columns, in f32
+    with the torch expressions the reference applies to them: the rows as a [1, 2, n_units] tensor through
+    normalize_with_singularity when `normalize` (as ABXFeatureLoader does with feature_function's output), then the
+    broadcast product / difference of get_cosine_distance_batch / get_euclidian_distance_batch.  On the host: two rows."""
+    code = _distance_code(distance_function)
+    rows = torch.zeros(1, 2, max(int(n_units), 2), dtype=torch.float32)
+    rows[0, 0, 0] = 1
+    rows[0, 1, 1] = 1
+    if normalize:
+        rows = abx_it.normalize_with_singularity(rows)
+    a1 = a2 = rows.view(2, 1, -1)                         # two items of one frame
+    N, S, D = a1.size()
+    if code == COSINE:
+        prod = (a1.view(N, 1, S, 1, D)) * (a2.view(1, N, 1, S, D))
+        dist = torch.clamp(prod.sum(dim=4), -1, 1).acos() / math.pi
+    else:
+        diff = a1.view(N, 1, S, 1, D) - a2.view(1, N, 1, S, D)
+        dist = torch.sqrt((diff**2).sum(dim=4))
+    dist = dist.view(2, 2)
+    return float(dist[0, 0]), float(dist[0, 1])
+
+
+def _segment_lists(items, px, py):
+    """The kernels' work list of the pairs (px[p], py[p]) (sorted by px) on the device: x item of every segment, CSR starts,
+    y items, number of segments, and the longest x / y item."""
+    dev = items.device
     seg_x, counts = np.unique(px, return_counts=True)
     seg_start = np.zeros(len(seg_x) + 1, dtype=np.int32)
     np.cumsum(counts, out=seg_start[1:])
     max_lx = int(items.lens_host[seg_x].max())
     max_ly = int(items.lens_host[np.unique(py)].max())
+    return (torch.from_numpy(seg_x.astype(np.int32)).to(dev), torch.from_numpy(seg_start).to(dev),
+            torch.from_numpy(np.ascontiguousarray(py, dtype=np.int32)).to(dev), len(seg_x), max_lx, max_ly)
+
+
+def _dtw_pairs_units(items, px, py, code):
+    """_dtw_pairs on items of unit ids: cpc_abx_dtw_units with the two frame distances of `code`."""
+    dev = items.device
+    n = int(px.shape[0])
+    d_seg_x, d_seg_start, d_py, n_seg, max_lx, max_ly = _segment_lists(items, px, py)
+    d_same, d_diff = items.distances[code]
     lib = _lib.load()
-    nbytes = lib.cpc_abx_dtw_scratch_bytes(len(seg_x), max_lx, max_ly)
+    nbytes = lib.cpc_abx_dtw_units_scratch_bytes(n_seg, max_lx, max_ly)
     scratch = _lib.scratch(nbytes, dev, tag="abx") if nbytes else None
-    d_seg_x = torch.from_numpy(seg_x.astype(np.int32)).to(dev)
-    d_seg_start = torch.from_numpy(seg_start).to(dev)
-    d_py = torch.from_numpy(np.ascontiguousarray(py, dtype=np.int32)).to(dev)
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+    plen = torch.empty(n, dtype=torch.int32, device=dev)
+    _lib.check(lib.cpc_abx_dtw_units(_lib.ptr(items.units), _lib.ptr(items.off), _lib.ptr(items.lens), items.n,
+                                     _lib.ptr(d_seg_x), _lib.ptr(d_seg_start), _lib.ptr(d_py), n_seg, max_lx, max_ly,
+                                     d_same, d_diff, _lib.ptr(out), _lib.ptr(plen), _lib.ptr(scratch), nbytes,
+                                     _lib.stream_ptr(dev)), "cpc_abx_dtw_units")
+    return out, plen
+
+
+def _dtw_pairs(items, px, py, code):
+    """DTW of the pairs (px[p], py[p]) (item indices, sorted by px) on the device: (values [n] fp32, path lengths)."""
+    if isinstance(items, _UnitItems):
+        return _dtw_pairs_units(items, px, py, code)
+    dev = items.device
+    n = int(px.shape[0])
+    d_seg_x, d_seg_start, d_py, n_seg, max_lx, max_ly = _segment_lists(items, px, py)
+    lib = _lib.load()
+    nbytes = lib.cpc_abx_dtw_scratch_bytes(n_seg, max_lx, max_ly)
+    scratch = _lib.scratch(nbytes, dev, tag="abx") if nbytes else None
     out = torch.empty(n, dtype=torch.float32, device=dev)
     plen = torch.empty(n, dtype=torch.int32, device=dev)
     _lib.check(lib.cpc_abx_dtw(_lib.ptr(items.frames), items.frames.size(1), _lib.ptr(items.off), _lib.ptr(items.lens),
-                               items.n, _lib.ptr(d_seg_x), _lib.ptr(d_seg_start), _lib.ptr(d_py), len(seg_x), max_lx,
+                               items.n, _lib.ptr(d_seg_x), _lib.ptr(d_seg_start), _lib.ptr(d_py), n_seg, max_lx,
                                max_ly, code, _lib.ptr(out), _lib.ptr(plen), _lib.ptr(scratch), nbytes,
                                _lib.stream_ptr(dev)), "cpc_abx_dtw")
     return out, plen
@@ -139,7 +212,7 @@ def _shape_keys(X, A, B, symmetric, n_items):
 def _count_chunk(items, trips, symmetric, code):
     """Integer counts (lt, eq) of a chunk of triplets [(a_items, b_items, x_items)] through the two kernels, plus the
     number of unique pairs and of DTW cells."""
-    dev = items.frames.device
+    dev = items.device
     by_shape = {}
     for t, (a, b, x) in enumerate(trips):
         by_shape.setdefault((len(x), len(a), len(b)), []).append(t)
@@ -290,7 +363,8 @@ def plan_triplets(group_iterator):
 
 def get_abx_scores_dtw_on_group(group_iterator, distance_function, symmetric, max_pairs=MAX_PAIRS_PER_CHUNK, stats=None):
     """Sparse tensor of 1 - theta over the iterator's board (abx_group_computation.py:98-129), computed in a few large
-    launches over all its triplets.  max_pairs caps the index entries per chunk; `stats` (a dict) receives counters."""
+    launches over all its triplets.  max_pairs caps the index entries per chunk; `stats` (a dict) receives counters.
+    A dataset of unit ids (ABXUnitLoader) goes through cpc_abx_dtw_units; everything else is the same code."""
     code = _distance_code(distance_function)
     coords, trips = plan_triplets(group_iterator)
     if not trips:
@@ -298,8 +372,13 @@ def get_abx_scores_dtw_on_group(group_iterator, distance_function, symmetric, ma
                          "single phone, or every phone a single item)")
     dataset = group_iterator.dataset
     device = torch.device("cuda", torch.cuda.current_device())
-    frames, off, lens = dataset.device_frames(device, -(-dataset.feature_dim // _DP_ALIGN) * _DP_ALIGN)
-    items = _Items(frames, off, lens, [f[1] for f in dataset.features])
+    if isinstance(dataset, abx_it.ABXUnitLoader):
+        units, off, lens = dataset.device_units(device)
+        items = _UnitItems(units, off, lens, [f[1] for f in dataset.features],
+                           {code: unit_frame_distances(dataset.n_units, dataset.normalize, distance_function)})
+    else:
+        frames, off, lens = dataset.device_frames(device, -(-dataset.feature_dim // _DP_ALIGN) * _DP_ALIGN)
+        items = _Items(frames, off, lens, [f[1] for f in dataset.features])
     with torch.no_grad():
         theta = _score_triplets(items, trips, symmetric, code, max_pairs, stats)
     values = (1 - theta.to(torch.float64)).to(torch.float32)

@@ -4,6 +4,9 @@ random draws and triplet order.
 The iterators keep the reference's interface (iterating yields padded group tensors, as loc_dtw expects) and add
 `triplets()`, the same traversal with the same `random.sample` calls in the same order, yielding lists of item indices
 instead of tensors.  abx_group_computation.get_abx_scores_dtw_on_group plans its batched kernel launches from it.
+
+ABXUnitLoader is the store for quantized units (eval_ABX_clustering): one int32 unit id per frame instead of a one-hot
+row, same items, same iterators.
 """
 import math
 import random
@@ -205,6 +208,95 @@ class ABXFeatureLoader:
         if mode == 'across':
             return ABXAcrossGroupIterator(self, max_size_group, max_x_across)
         raise ValueError(f"Invalid mode: {mode}")
+
+
+class ABXUnitLoader(ABXFeatureLoader):
+    """All items' frames as ONE int32 unit id each: `units` [total_frames], where the reference (and ABXFeatureLoader on
+    eval_ABX_clustering's feature_function) holds a [total_frames, n_units (+ 1)] one-hot matrix.
+
+    unitMaker(path) gives one file's units, an integer tensor [S] (or [1, S]) with values in [0, n_units).  Items are cut
+    with ABXFeatureLoader's onset / offset arithmetic, so self.features is the same table.  The reference-shaped interface
+    (__getitem__, the iterators' group_data, iterating an iterator) expands the requested items on demand to the rows the
+    reference's loader would hold: the one-hot row as [1, S, n_units] through normalize_with_singularity when `normalize`.
+    abx_group_computation.get_abx_scores_dtw_on_group recognises the store and scores it with cpc_abx_dtw_units, without
+    ever forming the matrix."""
+
+    def __init__(self, path_item_file, seqList, unitMaker, stepFeature, normalize, n_units):
+        if n_units < 1:
+            raise ValueError(f"ABXUnitLoader: n_units={n_units} must be at least 1")
+        self.n_units = int(n_units)
+        self.normalize = bool(normalize)
+        super().__init__(path_item_file, seqList, unitMaker, stepFeature, normalize)
+
+    def loadFromFileData(self, files_data, seqList, unit_maker, normalize):
+        self.features = []
+        self.INDEX_CONTEXT = 2
+        self.INDEX_PHONE = 3
+        self.INDEX_SPEAKER = 4
+        data = []
+        totSize = 0
+
+        for fileID, file_path in seqList:
+            if fileID not in files_data:
+                continue
+            units = unit_maker(file_path).detach().cpu()
+            if units.is_floating_point() or units.dtype == torch.bool:
+                raise TypeError(f"ABXUnitLoader: the unit function must return integer unit ids, got {units.dtype}")
+            units = units.reshape(-1)
+            if units.numel() and (int(units.min()) < 0 or int(units.max()) >= self.n_units):
+                raise ValueError(f"ABXUnitLoader: {file_path} has units outside [0, {self.n_units})")
+
+            for phone_start, phone_end, context_id, phone_id, speaker_id in files_data[fileID]:
+                index_start = max(0, int(math.ceil(self.stepFeature * phone_start - 0.5)))
+                index_end = min(units.size(0), int(math.floor(self.stepFeature * phone_end - 0.5)))
+                if index_start >= units.size(0) or index_end <= index_start:
+                    continue
+                loc_size = index_end - index_start
+                self.features.append([totSize, loc_size, context_id, phone_id, speaker_id])
+                data.append(units[index_start:index_end])
+                totSize += loc_size
+
+        if not data:
+            raise ValueError("ABX: no item of the item file has frames in the given sequences "
+                             "(check the file IDs, the file extension and --feature-size)")
+        self.units = torch.cat(data, dim=0).to(torch.int32)
+        self.feature_dim = self.n_units + (1 if self.normalize else 0)
+        self._frames = {}
+
+    def get_data_device(self):
+        return self.units.device
+
+    def cuda(self):
+        self.units = self.units.cuda()
+
+    def cpu(self):
+        self.units = self.units.cpu()
+
+    def expand(self, start, size):
+        """Frames start .. start + size - 1 as the rows the reference's loader holds: [size, feature_dim] fp32."""
+        u = self.units[start:start + size].long()
+        rows = torch.zeros(1, size, self.n_units, dtype=torch.float32, device=u.device)
+        rows.scatter_(-1, u.view(1, size, 1), 1)
+        if self.normalize:
+            rows = normalize_with_singularity(rows)
+        return rows.view(size, self.feature_dim)
+
+    def device_frames(self, device, dp):
+        raise RuntimeError("ABXUnitLoader holds unit ids, not frames: score it through device_units (cpc_abx_dtw_units)")
+
+    def device_units(self, device):
+        """The unit ids on `device` (int32 [total_frames]) and the items' frame offsets and lengths (int32), uploaded
+        once per device."""
+        key = str(device)
+        if key not in self._frames:
+            meta = torch.tensor([f[:2] for f in self.features], dtype=torch.int32)
+            self._frames[key] = (self.units.to(device).contiguous(), meta[:, 0].contiguous().to(device),
+                                 meta[:, 1].contiguous().to(device))
+        return self._frames[key]
+
+    def __getitem__(self, index):
+        i_data, out_size, context_id, phone_id, speaker_id = self.features[index]
+        return self.expand(i_data, out_size), out_size, (context_id, phone_id, speaker_id)
 
 
 class ABXIterator:

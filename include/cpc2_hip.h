@@ -44,7 +44,8 @@ enum cpc_status {
 int cpc_version(void);          /* 100 x major + minor; 105 = the entry points of round 5 (cpc_encoder_forward2 / backward2, cpc_coop_set_policy,
                                   * cpc_recurrent_backward_calls, cpc_side_tail_wait); 107 = cpc_abx_dtw / cpc_abx_counts;
                                   * 108 = cpc_kmeans_scratch_bytes / cpc_kmeans_assign / cpc_kmeans_distances / cpc_kmeans_accumulate;
-                                  * 109 = cpc_probe_xent / cpc_probe_head_backward / cpc_probe_ctc / cpc_probe_collapse (+ scratch queries) */
+                                  * 109 = cpc_probe_xent / cpc_probe_head_backward / cpc_probe_ctc / cpc_probe_collapse (+ scratch queries);
+                                  * 110 = cpc_abx_dtw_units (+ scratch query) */
 const char *cpc_last_error(void);
 
 /* In-situ kernel timing for bench.py: when enabled, the launchers bracket each launch of the named
@@ -490,6 +491,20 @@ int cpc_abx_dtw(const float *frames, int dp, const int *item_off, const int *ite
                 int distance, float *out, int *path_len, void *scratch, size_t scratch_bytes, cpc_stream_t stream);
 int cpc_abx_counts(const float *dist, int n_pairs, const int *idx_a, const int *idx_b, const int *shape, int n_trip,
                    int *lt, int *eq, cpc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * ABX on quantized units (cpc/eval/eval_ABX_clustering.py of the reference): the DTW of cpc_abx_dtw between items whose
+ * frames are unit ids.  `units` [total_frames] int32; item i is units item_off[i] .. item_off[i] + item_len[i] - 1.  The
+ * frame distance is d_same where the two units are equal and d_diff where they differ: the two values the reference's
+ * distance takes on one-hot rows, computed by the caller.  Segment / pair lists, outputs, path-length rule, limits and the
+ * not-computable convention (NaN, path length -1) are those of cpc_abx_dtw; cost = d + predecessor in f32, one f32 division
+ * by the path length at the end.  scratch: cpc_abx_dtw_units_scratch_bytes (0 when every x item has <= 64 frames).
+ * ------------------------------------------------------------------------------------------ */
+size_t cpc_abx_dtw_units_scratch_bytes(int n_seg, int max_len_x, int max_len_y);
+int cpc_abx_dtw_units(const int *units, const int *item_off, const int *item_len, int n_items,
+                      const int *seg_x, const int *seg_start, const int *pair_y, int n_seg,
+                      int max_len_x, int max_len_y, float d_same, float d_diff,
+                      float *out, int *path_len, void *scratch, size_t scratch_bytes, cpc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * k-means on features (cpc/clustering/clustering.py of the reference).  x [n][d] rows, ck [k][d] centroids, all fp32 DEVICE
