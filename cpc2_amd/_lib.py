@@ -110,6 +110,7 @@ SIGNATURES = {
     "cpc_flac_decode_f32": (c_int, [ctypes.c_char_p, c_ptr, c_long, ctypes.POINTER(c_int)]),
     "cpc_window_gather": (c_int, [c_ptr, c_long, c_ptr, c_ptr, c_int, c_int, c_ptr]),
     "cpc_adam_step": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_long, c_int, c_float, c_float, c_float, c_float, c_float, c_ptr]),
+    "cpc_sgd_step": (c_int, [c_ptr, c_ptr, c_ptr, c_long, c_int, c_float, c_float, c_float, c_ptr]),
     "cpc_abx_dtw_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
     "cpc_abx_dtw": (c_int, [c_ptr, c_int, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr,
                             c_ptr, c_size_t, c_ptr]),

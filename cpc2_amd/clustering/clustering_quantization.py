@@ -90,8 +90,7 @@ def main(argv):
 
     print("")
     print(f"Looking for all {args.file_extension} files in {args.pathDB} with speakerLevel {args.recursionLevel}")
-    seqNames, speakers = findAllSeqs(args.pathDB, speaker_level=args.recursionLevel, extension=args.file_extension,
-                                     loadCache=True)
+    seqNames, speakers = findAllSeqs(args.pathDB, speaker_level=args.recursionLevel, extension=args.file_extension)     # (no sequence cache: the listing is read afresh, as before findAllSeqs had one)
     print(f"Done! Found {len(seqNames)} files and {len(speakers)} speakers!")
 
     nameOutput = "quantized_outputs.txt" if not args.split else f"quantized_outputs_split_{idx_split}-{num_splits}.txt"

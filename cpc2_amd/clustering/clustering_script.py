@@ -76,8 +76,7 @@ def main(argv):
         print(f"The output directory {args.dirOutput} already exists, please check the option --load !")
         return
 
-    seqNames, speakers = findAllSeqs(str(args.pathDB), speaker_level=args.recursionLevel, extension=args.extension,
-                                     loadCache=True)
+    seqNames, speakers = findAllSeqs(str(args.pathDB), speaker_level=args.recursionLevel, extension=args.extension)     # (no sequence cache: the listing is read afresh, as before findAllSeqs had one)
     if args.seqList is not None:
         seqNames = filterSeqs(args.seqList, seqNames)
     if args.debug:

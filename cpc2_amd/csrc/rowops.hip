@@ -1,5 +1,5 @@
 // Small HBM-bound helpers: error state, column sums, weight re-layouts, channel-first ChannelNorm
-// (standalone module API), fused flat Adam.
+// (standalone module API), window gather, fused flat Adam and SGD steps.
 #include "common.h"
 #include "coop.h"
 
@@ -144,7 +144,7 @@ int coop_error_take(const char *where)
     const int code = __atomic_exchange_n(g_err_host, 0, __ATOMIC_ACQ_REL);
     if (code == 0) return CPC_OK;
     if (code == COOP_ERR_NONFINITE_GRAD) {
-        set_error("%s: the Adam step met non-finite gradient elements and skipped THOSE elements (their parameters and moments are "
+        set_error("%s: the optimiser step (Adam / SGD) met non-finite gradient elements and skipped THOSE elements (their parameters and moments are "
                   "unchanged); the finite elements of the same step were applied and the step count advanced -- a partial update, "
                   "unlike torch.optim.Adam, which would have propagated the NaN: reload the last checkpoint or continue knowingly", where);
         return CPC_ERR_HIP;
@@ -426,6 +426,23 @@ __global__ void adam_kernel(float *p, const float *g, float *m, float *v, long n
     if (bad) coop_report(err, COOP_ERR_NONFINITE_GRAD);
 }
 
+// ---------------------------------------------------------------- SGD with momentum
+// torch.optim.SGD(lr, momentum) as built at train.py:480-482 (no dampening, no weight decay, no nesterov): the first step
+// copies the gradient into the momentum buffer, the following ones fold it in.  Non-finite gradient elements: adam_kernel's rule.
+__global__ void sgd_kernel(float *p, const float *g, float *buf, long n, float lr, float momentum, int first,
+                           float grad_scale, int *err)
+{
+    bool bad = false;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const float gi = g[i] * grad_scale;
+        if (!(fabsf(gi) <= 3.4028234e38f)) { bad = true; continue; }
+        const float bi = first ? gi : momentum * buf[i] + gi;
+        buf[i] = bi;
+        p[i] -= lr * bi;
+    }
+    if (bad) coop_report(err, COOP_ERR_NONFINITE_GRAD);
+}
+
 // ---------------------------------------------------------------- streams that run BESIDE a given stream
 // A HIP stream is served by one of a few hardware queues (GPU_MAX_HW_QUEUES, 4 by default, per priority); the runtime hands a new
 // stream the least-used queue AT THAT MOMENT, and two streams on one queue run one after the other -- whatever their events say.
@@ -618,6 +635,17 @@ extern "C" int cpc_adam_step(float *p, const float *g, float *m, float *v, long 
     hipLaunchKernelGGL(cpc::adam_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), p, g, m, v, n,
                        lr_c1, rsqrt_c2, beta1, beta2, eps, grad_scale, cpc::coop_error_word());
     CPC_CHECK_LAUNCH("adam_kernel");
+    return CPC_OK;
+}
+
+extern "C" int cpc_sgd_step(float *p, const float *g, float *buf, long n, int step, float lr, float momentum,
+                            float grad_scale, cpc_stream_t stream)
+{
+    CPC_REQUIRE(p != nullptr && g != nullptr && buf != nullptr && n > 0 && step >= 1, "sgd: bad n=%ld step=%d", n, step);
+    const long blocks = std::min<long>(cpc::cdiv(n, 256), 4096);
+    hipLaunchKernelGGL(cpc::sgd_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), p, g, buf, n,
+                       lr, momentum, step == 1 ? 1 : 0, grad_scale, cpc::coop_error_word());
+    CPC_CHECK_LAUNCH("sgd_kernel");
     return CPC_OK;
 }
 

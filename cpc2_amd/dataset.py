@@ -1,7 +1,7 @@
 """Window feeder: the step in front of the hot path.
 
 Same names and behaviour as the reference's cpc/dataset.py for the parts the training loop uses --
-findAllSeqs (:771-948, format=None branch), filterSeqs (:963-978), AudioBatchData (:23-408: sequences sorted by
+findAllSeqs (:771-948: every naming convention and the sequence cache), filterSeqs (:963-978), AudioBatchData (:23-408: sequences sorted by
 (speaker, name) and concatenated into ONE flat audio vector, speaker / sequence interval tables, chunked
 "packs" of at most MAX_SIZE_LOADED samples, getDataLoader with the uniform / sequential / samespeaker /
 samesequence / temporalsamespeaker samplers :603-757 and the random window offset :395-403) -- but MI355X-first:
@@ -27,23 +27,94 @@ from . import _lib, audio
 from ._lib import check, ptr, stream_ptr
 
 
-def findAllSeqs(dirName, extension='.flac', speaker_level=1, **unused):
-    """(outSequences [(speaker_index, relative_path)], outSpeakers) -- dataset.py:771-948 with format=None."""
+def _naming_convention(format, extension):
+    """(id string of a file name, sort key of a relative path) of one naming convention -- dataset.py:850-865 and :881-937.
+    The id is taken from the FILE name, the key from the RELATIVE PATH (directories included), as in the reference."""
+    def stem_parts(sep):
+        return lambda path: path.replace(extension, '').split(sep)
+    if format == "id_spkr_onset_offset":
+        return (lambda name: '_'.join(name.split('_')[0:-2]),
+                lambda path: ('_'.join(path.split('_')[0:-2]), float(path.split('_')[-2])))
+    if format == "id_spkr_onset_offset_spkr_onset_offset":
+        return (lambda name: '_'.join(name.split('_')[0:-5]),
+                lambda path: ('_'.join(path.split('_')[0:-5]), float(path.split('_')[-5])))
+    if format == "spkr-id":
+        return (lambda name: '-'.join(name.split('-')[0:2]),
+                lambda path: (path.split('-')[0], int(path.split('-')[1])))
+    if format == "spkr_id_nb":
+        parts = stem_parts('_')
+        return (lambda name: '_'.join(name.split('_')[0:-1]), lambda path: (parts(path)[0:-1], int(parts(path)[-1])))
+    if format == "spkr-id-nb":
+        parts = stem_parts('-')
+        return (lambda name: '-'.join(name.split('-')[0:-1]), lambda path: (parts(path)[0:-1], int(parts(path)[-1])))
+    if format == "full_seedlings":
+        return (lambda name: '_'.join(name.split('_')[0:-2] + [name.split('_')[-1]]),
+                lambda path: (path.split('_')[0:-2] + [path.split('_')[-1]], int(path.split('_')[-2])))
+    if format == "no_speaker":
+        parts = stem_parts('_')
+        return (lambda name: 'anonymous', lambda path: (parts(path)[0:-1], int(parts(path)[-1])))
+    raise ValueError("%s format unknown" % format)
+
+
+def findAllSeqs(dirName, no_speaker=False, extension='.flac', loadCache=False, speaker_level=1, format=None,
+                cache_path=None):
+    """(outSequences [(speaker_index, relative_path)], outSpeakers) -- dataset.py:771-948.
+
+    format=None: speakers are the first `speaker_level` directories, sequences in os.walk order.  With a naming convention
+    (`format`, one of cpc_default_config.NAMING_CONVENTIONS): the speaker is the id string cut out of the file name, the list
+    is sorted by the convention's (speaker, position) key so that files follow each other in time, and `no_speaker` (or the
+    convention 'no_speaker') collapses every id into 'anonymous' with index 0.
+
+    The sequence cache (a torch.save of the two lists; :812-821, :943-947): `loadCache` returns it when it can be read,
+    and the listing is saved to it afterwards; `cache_path` defaults to `_seqs_cache.txt` inside dirName.  The cache is
+    keyed by nothing -- it does not know the extension, the convention or no_speaker it was made with.  Unlike the
+    reference, which saves on EVERY call, a call with neither loadCache nor cache_path reads and writes no file."""
     dirName = str(dirName)
+    use_cache = loadCache or cache_path is not None
+    if cache_path is None:
+        cache_path = str(Path(dirName) / '_seqs_cache.txt')
+    if loadCache:
+        try:
+            outSequences, speakers = torch.load(cache_path)
+            print(f'Loaded from cache {cache_path} successfully')
+            return outSequences, speakers
+        except OSError as err:
+            print(f'Ran in an error while loading {cache_path}: {err}')
+        print('Could not load cache, rebuilding')
     if dirName[-1] != os.sep:
         dirName += os.sep
     prefixSize = len(dirName)
+    id_of, sort_key = _naming_convention(format, extension) if format is not None else (None, None)
     speakersTarget, outSequences = {}, []
+    idsTarget, outIds, outSequencesIds = {}, [], []
     for root, _dirs, filenames in os.walk(dirName, followlinks=True):
         filtered_files = [f for f in filenames if f.endswith(extension)]
         if filtered_files:
             speakerStr = os.sep.join(root[prefixSize:].split(os.sep)[:speaker_level])
             speaker = speakersTarget.setdefault(speakerStr, len(speakersTarget))
             for filename in filtered_files:
-                outSequences.append((speaker, os.path.join(root[prefixSize:], filename)))
+                full_path = os.path.join(root[prefixSize:], filename)
+                outSequences.append((speaker, full_path))
+                if format is not None:
+                    idStr = 'anonymous' if no_speaker else id_of(filename)
+                    if idStr not in idsTarget:
+                        idsTarget[idStr] = len(idsTarget)
+                        outIds.append(idStr)
+                    outSequencesIds.append((idsTarget[idStr], full_path))
     outSpeakers = [None] * len(speakersTarget)
     for key, index in speakersTarget.items():
         outSpeakers[index] = key
+    if format is not None:
+        outSequences = sorted(outSequencesIds, key=lambda x: sort_key(x[1]))
+        if format == "no_speaker" or no_speaker:
+            outSequences = [(0, v) for _, v in outSequences]
+        outSpeakers = outIds
+    if use_cache:
+        try:
+            torch.save((outSequences, outSpeakers), cache_path)
+            print(f'Saved cache file at {cache_path}')
+        except (OSError, RuntimeError) as err:          # (torch reports a missing parent directory as RuntimeError)
+            print(f'Ran in an error while saving {cache_path}: {err}')
     return outSequences, outSpeakers
 
 
@@ -127,6 +198,62 @@ def _temporal_same_interval_batches(intervals, sizeWindow, offset, batchSize):
             batches.append(list(range(beg, beg + sizeWindow * batchSize, sizeWindow)))
     random.shuffle(batches)
     return batches
+
+
+def remove_artefacts(batches, seqLabel, sizeWindow, carry_shift=False):
+    """AudioLoader.__remove_artefacts (dataset.py:486-526) on a list of batches of window offsets: a window that begins in
+    sequence i and would run over its end begins at the start of sequence i + 1 instead; in the last sequence it cannot be
+    moved and is dropped, and if it was the LAST window of its batch the whole batch is dropped (the reference's flag is
+    reset per window, so only the last one decides).  An offset that lies in no sequence is dropped from its batch.
+    carry_shift (TemporalSameSpeakerSampler's batches of consecutive windows): the distance a window was moved by is
+    added to every later window of the batch, so that they still follow each other.
+
+    The reference walks every boundary for every window; here the sequence is found by bisection -- for the independent
+    case for all windows of all batches at once (numpy.searchsorted)."""
+    import bisect
+    import numpy as np
+    n = len(seqLabel)
+    if carry_shift:
+        out = []
+        for batch in batches:
+            new_batch, shift, delete = [], 0, False
+            for beg in batch:
+                beg += shift
+                delete = False
+                i = bisect.bisect_right(seqLabel, beg)
+                if not 1 <= i <= n - 1:
+                    continue
+                if beg + sizeWindow > seqLabel[i]:
+                    if i != n - 1:
+                        new_batch.append(seqLabel[i])
+                    else:
+                        delete = True
+                    shift += seqLabel[i] - beg
+                else:
+                    new_batch.append(beg)
+            if not delete:
+                out.append(new_batch)
+        return out
+    if not batches:
+        return []
+    bounds = np.asarray(seqLabel, dtype=np.int64)
+    sizes = np.fromiter((len(b) for b in batches), dtype=np.int64, count=len(batches))
+    flat = np.fromiter((o for b in batches for o in b), dtype=np.int64, count=int(sizes.sum()))
+    i = np.searchsorted(bounds, flat, side="right")
+    inside = (i >= 1) & (i <= n - 1)
+    end = bounds[np.clip(i, 0, n - 1)]
+    over = inside & (flat + sizeWindow > end)
+    stuck = over & (i == n - 1)
+    moved = np.where(over, end, flat)
+    keep = inside & ~stuck
+    stops = np.cumsum(sizes)
+    starts = stops - sizes
+    out = []
+    for lo, hi in zip(starts.tolist(), stops.tolist()):
+        if hi > lo and stuck[hi - 1]:
+            continue
+        out.append(moved[lo:hi][keep[lo:hi]].tolist())
+    return out
 
 
 class AudioBatchData:
@@ -355,20 +482,25 @@ class AudioBatchData:
         raise ValueError("--samplingType should belong to %s" % ["samespeaker", "samesequence", "temporalsamespeaker",
                                                                 "sequential", "uniform"])
 
-    def getDataLoader(self, batchSize, type, randomOffset, numWorkers=0, onLoop=-1, nLoops=-1, **unused):
-        """Iterable of (sequence [b,2,1,W] on the device, speaker label [b]) over nLoops packs -- dataset.py:366-408."""
+    def getDataLoader(self, batchSize, type, randomOffset, numWorkers=0, onLoop=-1, nLoops=-1, remove_artefacts=False,
+                      batch_size_per_gpu=None, **unused):
+        """Iterable of (sequence [b,2,1,W] on the device, speaker label [b]) over nLoops packs -- dataset.py:366-408.
+        remove_artefacts: no window crosses the boundary between two sequences (the module's remove_artefacts, applied to
+        every pack's batches before its first step).  batch_size_per_gpu is accepted and, as in the reference (whose
+        sampler stores it and never reads it), changes nothing."""
         if onLoop >= 0:
             self.currentPack = onLoop - 1
             self.loadNextPack()
             nLoops = 1 if nLoops <= 0 else nLoops
         elif nLoops <= 0:
             nLoops = len(self.packageIndex)
-        return _AudioLoader(self, batchSize, type, randomOffset, nLoops)
+        return _AudioLoader(self, batchSize, type, randomOffset, nLoops, remove_artefacts)
 
 
 class _AudioLoader:
-    def __init__(self, dataset, batchSize, type, randomOffset, nLoops):
+    def __init__(self, dataset, batchSize, type, randomOffset, nLoops, remove_artefacts=False):
         self.dataset, self.batchSize, self.type, self.randomOffset, self.nLoops = dataset, batchSize, type, randomOffset, nLoops
+        self.remove_artefacts = remove_artefacts
 
     def _sampler(self):
         d = self.dataset
@@ -377,7 +509,10 @@ class _AudioLoader:
                 else random.randint(0, d.sizeWindow // 2)
         else:
             offset = 0
-        return d.getBaseSampler(self.type, self.batchSize, offset)
+        batches = d.getBaseSampler(self.type, self.batchSize, offset)
+        if self.remove_artefacts:                            # dataset.py:478-480
+            batches = remove_artefacts(batches, d.seqLabel, d.sizeWindow, carry_shift=self.type == "temporalsamespeaker")
+        return batches
 
     def __len__(self):
         return self.dataset.totSize // (self.dataset.sizeWindow * self.batchSize)

@@ -1,4 +1,5 @@
-"""The caller side of the hot path: factories, the optimisation step and data-parallel glue.
+"""The caller side of the hot path: factories, the optimisation step, data-parallel glue and the training command line
+(`python -m cpc2_amd.train`, the reference's cpc/train.py: parseArgs / main at the end of this file).
 
 Mirrors (semantics, names) /root/reference/cpc/train.py:27-59 (getCriterion), :72-187
 (trainStep / valStep), :472-484 (Adam over criterion + model parameters), :523-527 (DDP wrap) and
@@ -51,7 +52,7 @@ def getAR(args):
 def getCriterion(args, downsampling, nSpeakers=0, nPhones=0):
     """train.py:27-48 (unsupervised branch)."""
     if getattr(args, "supervised", False):
-        raise NotImplementedError("supervised criteria are not on the MI355X hot path")
+        raise NotImplementedError("--supervised: the supervised criteria are not trained through this loop (in the reference this path fails at the first step); train them with python -m cpc2_amd.eval.linear_separability --unfrozen")
     if getattr(args, "cpc_mode", None) == "none":
         return NoneCriterion()
     sizeInputSeq = args.sizeWindow // downsampling
@@ -66,32 +67,24 @@ def getCriterion(args, downsampling, nSpeakers=0, nPhones=0):
                                     inflection_point_x=getattr(args, "inflection_point_x", None))
 
 
-# --------------------------------------------------------------------------- flat parameters + fused Adam
-class FlatAdam(torch.optim.Optimizer):
-    """torch.optim.Adam(params, lr, betas, eps) of train.py:477-479 on one flat buffer.
+# --------------------------------------------------------------------------- flat parameters + fused Adam / SGD
+class _FlatOptimizer(torch.optim.Optimizer):
+    """What FlatAdam and FlatSGD share: every parameter re-homed into `self.flat` (views, same values), every .grad into
+    `self.flat_grad`, ONE param group (so the reference's schedulers attach unchanged: the learning rate is read from
+    param_groups[0]["lr"] at every step), and the bookkeeping DataParallelContext and run() rely on."""
 
-    Re-homes every parameter into `self.flat` (views, same values) and every .grad into
-    `self.flat_grad`, then `step()` is a single cpc_adam_step launch.  State-dict interop with
-    torch.optim.Adam is kept through `state_dict()` / `load_state_dict()` (per-parameter
-    exp_avg / exp_avg_sq / step).  A torch.optim.Optimizer with ONE param group, so the reference's
-    learning-rate schedulers (train.py:501-520: StepLR, the LambdaLR ramp, SchedulerCombiner) attach
-    to it unchanged; the learning rate is read from param_groups[0]["lr"] at every step."""
-
-    def __init__(self, params, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, direct_grads=True):
+    def _rehome(self, params, defaults, direct_grads):
         self.params = [p for p in params]
         self.direct_grads = direct_grads
         if not self.params:
-            raise ValueError("FlatAdam got an empty parameter list")
+            raise ValueError(f"{type(self).__name__} got an empty parameter list")
         dev = self.params[0].device
         _lib.require_gpu(*self.params)
-        super(FlatAdam, self).__init__(self.params, dict(lr=lr, betas=betas, eps=eps))
-        self.lr, self.betas, self.eps = lr, betas, eps
+        torch.optim.Optimizer.__init__(self, self.params, defaults)
         self.step_count = 0
         total = sum(p.numel() for p in self.params)
         self.flat = torch.empty(total, dtype=torch.float32, device=dev)
         self.flat_grad = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.exp_avg = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.exp_avg_sq = torch.zeros(total, dtype=torch.float32, device=dev)
         self.offsets = []
         off = 0
         for p in self.params:
@@ -107,6 +100,7 @@ class FlatAdam(torch.optim.Optimizer):
                 p.grad = self.flat_grad[off:off + n].view(p.shape)
             self.offsets.append(off)
             off += n
+        return total, dev
 
     def zero_grad(self, set_to_none=False):
         self.flat_grad.zero_()
@@ -129,15 +123,51 @@ class FlatAdam(torch.optim.Optimizer):
             if p.grad is not None and p.grad.data_ptr() != base + 4 * off:
                 self.flat_grad[off:off + p.numel()].copy_(p.grad.reshape(-1))
 
-    def step(self, closure=None, grad_scale=1.0):
+    def _before_step(self, closure):
         if closure is not None:
-            raise NotImplementedError("FlatAdam.step does not re-evaluate a closure")
+            raise NotImplementedError(f"{type(self).__name__}.step does not re-evaluate a closure")
         if self.flat.is_cuda:
             join_tail(self.flat.device)          # (a deferred recurrent backward's weight gradients: normally joined at the end of backward)
         if self.direct_grads:
             self._gather_stray_grads()
         self.step_count += 1
-        lr = self.param_groups[0]["lr"]
+        return self.param_groups[0]["lr"]
+
+    def _group_state(self, **hyper):
+        """The param group of a state dict.  `initial_lr` (written into the group by a torch scheduler) travels with it: a
+        scheduler built on a resumed optimiser takes its base rate from there, and from the CURRENT -- already scaled -- rate
+        when it is missing (a run stopped inside the warm-up ramp would ramp from the scaled rate)."""
+        group = dict(lr=self.param_groups[0]["lr"], **hyper)
+        if "initial_lr" in self.param_groups[0]:
+            group["initial_lr"] = self.param_groups[0]["initial_lr"]
+        group["params"] = list(range(len(self.params)))
+        return group
+
+    def _load_group(self, sd):
+        group = sd["param_groups"][0]
+        self.param_groups[0]["lr"] = group["lr"]
+        if "initial_lr" in group:
+            self.param_groups[0]["initial_lr"] = group["initial_lr"]
+
+
+class FlatAdam(_FlatOptimizer):
+    """torch.optim.Adam(params, lr, betas, eps) of train.py:477-479 on one flat buffer.
+
+    Re-homes every parameter into `self.flat` (views, same values) and every .grad into
+    `self.flat_grad`, then `step()` is a single cpc_adam_step launch.  State-dict interop with
+    torch.optim.Adam is kept through `state_dict()` / `load_state_dict()` (per-parameter
+    exp_avg / exp_avg_sq / step).  A torch.optim.Optimizer with ONE param group, so the reference's
+    learning-rate schedulers (train.py:501-520: StepLR, the LambdaLR ramp, SchedulerCombiner) attach
+    to it unchanged; the learning rate is read from param_groups[0]["lr"] at every step."""
+
+    def __init__(self, params, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, direct_grads=True):
+        total, dev = self._rehome(params, dict(lr=lr, betas=betas, eps=eps), direct_grads)
+        self.lr, self.betas, self.eps = lr, betas, eps
+        self.exp_avg = torch.zeros(total, dtype=torch.float32, device=dev)
+        self.exp_avg_sq = torch.zeros(total, dtype=torch.float32, device=dev)
+
+    def step(self, closure=None, grad_scale=1.0):
+        lr = self._before_step(closure)
         check(_lib.load().cpc_adam_step(ptr(self.flat), ptr(self.flat_grad), ptr(self.exp_avg), ptr(self.exp_avg_sq),
                                         self.flat.numel(), self.step_count, lr, self.betas[0], self.betas[1], self.eps,
                                         grad_scale, stream_ptr(self.flat.device)), "adam_step")
@@ -149,8 +179,7 @@ class FlatAdam(torch.optim.Optimizer):
             state[i] = {"step": torch.tensor(float(self.step_count)),
                         "exp_avg": self.exp_avg[off:off + n].view(p.shape).clone(),
                         "exp_avg_sq": self.exp_avg_sq[off:off + n].view(p.shape).clone()}
-        return {"state": state, "param_groups": [{"lr": self.param_groups[0]["lr"], "betas": self.betas,
-                                                  "eps": self.eps, "params": list(range(len(self.params)))}]}
+        return {"state": state, "param_groups": [self._group_state(betas=self.betas, eps=self.eps)]}
 
     def load_state_dict(self, sd):
         for i, (p, off) in enumerate(zip(self.params, self.offsets)):
@@ -161,13 +190,56 @@ class FlatAdam(torch.optim.Optimizer):
             self.exp_avg[off:off + n].copy_(st["exp_avg"].reshape(-1))
             self.exp_avg_sq[off:off + n].copy_(st["exp_avg_sq"].reshape(-1))
             self.step_count = int(st["step"])
-        self.param_groups[0]["lr"] = sd["param_groups"][0]["lr"]
+        self._load_group(sd)
 
 
-def buildOptimizer(cpcModel, cpcCriterion, lr=2e-4, beta1=0.9, beta2=0.999, epsilon=1e-8):
-    """train.py:472-479: criterion parameters first, then model parameters."""
+class FlatSGD(_FlatOptimizer):
+    """torch.optim.SGD(params, lr, momentum=0.9) of train.py:480-482 on one flat buffer: `step()` is a single cpc_sgd_step
+    launch over (flat, flat_grad, momentum_buffer) -- the first step copies the gradient into the buffer, the following ones
+    compute buf = momentum buf + g, and p -= lr buf.  Same non-finite-gradient rule as FlatAdam (element left alone,
+    asynchronous error reported).  `state_dict()` / `load_state_dict()` use torch.optim.SGD's layout (`momentum_buffer` per
+    parameter, no entry before the first step)."""
+
+    def __init__(self, params, lr=2e-4, momentum=0.9, direct_grads=True):
+        total, dev = self._rehome(params, dict(lr=lr, momentum=momentum), direct_grads)
+        self.lr, self.momentum = lr, momentum
+        self.momentum_buffer = torch.zeros(total, dtype=torch.float32, device=dev)
+
+    def step(self, closure=None, grad_scale=1.0):
+        lr = self._before_step(closure)
+        check(_lib.load().cpc_sgd_step(ptr(self.flat), ptr(self.flat_grad), ptr(self.momentum_buffer), self.flat.numel(),
+                                       self.step_count, lr, self.momentum, grad_scale, stream_ptr(self.flat.device)), "sgd_step")
+
+    def state_dict(self):
+        state = {}
+        if self.step_count > 0:
+            for i, (p, off) in enumerate(zip(self.params, self.offsets)):
+                state[i] = {"momentum_buffer": self.momentum_buffer[off:off + p.numel()].view(p.shape).clone()}
+        group = self._group_state(momentum=self.momentum, dampening=0, weight_decay=0, nesterov=False, maximize=False,
+                                  foreach=None, differentiable=False, fused=None)
+        return {"state": state, "param_groups": [group]}
+
+    def load_state_dict(self, sd):
+        """A parameter without a buffer in `sd` gets a zero one, which the next step treats as torch does a missing one
+        (momentum x 0 + g = g); with no buffer at all the next step is a first step."""
+        self.momentum_buffer.zero_()
+        self.step_count = 0
+        for i, (p, off) in enumerate(zip(self.params, self.offsets)):
+            buf = (sd["state"].get(i) or {}).get("momentum_buffer")
+            if buf is not None:
+                self.momentum_buffer[off:off + p.numel()].copy_(buf.reshape(-1))
+                self.step_count = 1
+        self._load_group(sd)
+
+
+def buildOptimizer(cpcModel, cpcCriterion, lr=2e-4, beta1=0.9, beta2=0.999, epsilon=1e-8, optimizer='adam'):
+    """train.py:472-484: criterion parameters first, then model parameters; 'adam' or 'sgd' (momentum 0.9)."""
     g_params = list(cpcCriterion.parameters()) + list(cpcModel.parameters())
-    return FlatAdam(g_params, lr=lr, betas=(beta1, beta2), eps=epsilon)
+    if optimizer == 'adam':
+        return FlatAdam(g_params, lr=lr, betas=(beta1, beta2), eps=epsilon)
+    if optimizer == 'sgd':
+        return FlatSGD(g_params, lr=lr, momentum=0.9)
+    raise ValueError("Unsupported optimizer: %s" % optimizer)
 
 
 # --------------------------------------------------------------------------- logs (cpc/utils/misc.py:25-60)
@@ -259,7 +331,7 @@ def buildScheduler(optimizer, schedulerStep=-1, schedulerRamp=None, epochs_done=
 class DataParallelContext:
     """One process per GPU (train.py:291-295, 523-527 with --distributed).  Replaces the two DDP wrappers by: one
     broadcast of the flat parameter buffer from rank 0 at start, and all-reduces (SUM) of the flat gradient buffer whose
-    1/world_size is folded into the Adam kernel.
+    1/world_size is folded into the optimiser's kernel (Adam or SGD).
 
     Overlap (the reference gets it from DDP's buckets, train.py:523-527): with `early_params` -- the parameters whose
     gradients are complete before the encoder's backward starts: the criterion's and the context network's -- their slices
@@ -762,3 +834,303 @@ def init_distributed_mode(backend="nccl"):
     if world > 1 and not dist.is_initialized():
         dist.init_process_group(init_method="env://", backend=backend, world_size=world, rank=rank)
     return rank, local_rank, world
+
+
+# --------------------------------------------------------------------------- the command line (train.py:260-688)
+def set_seed(seed):
+    """cpc/utils/misc.py:63-68: python's, torch's (host and every device) and numpy's generators."""
+    import random
+    random.seed(seed)
+    torch.manual_seed(seed)
+    np.random.seed(seed)
+    if torch.cuda.is_available():
+        torch.cuda.manual_seed_all(seed)
+
+
+def splitTrainVal(seqTrain, samplingType):
+    """train.py:322-341: shuffle (python's generator), then the first 95 % train and the rest validate.  Under
+    temporalsamespeaker the shuffle moves whole runs of equal speaker index, so that a speaker's files keep their order."""
+    import itertools
+    import random
+    if samplingType == "temporalsamespeaker":
+        blocks = [list(run) for _spk, run in itertools.groupby(seqTrain, key=lambda item: item[0])]
+        random.shuffle(blocks)
+        seqTrain = list(itertools.chain.from_iterable(blocks))
+    else:
+        seqTrain = list(seqTrain)
+        random.shuffle(seqTrain)
+    sizeTrain = int(0.95 * len(seqTrain))
+    return seqTrain[:sizeTrain], seqTrain[sizeTrain:]
+
+
+def loadCriterion(pathCheckpoint, downsampling, nSpeakers, nPhones=None):
+    """train.py:62-69: the criterion of the run that wrote pathCheckpoint (built from ITS arguments), weights loaded."""
+    import os
+    from . import feature_loader as fl
+    _, _, locArgs = fl.getCheckpointData(os.path.dirname(pathCheckpoint))
+    criterion = getCriterion(locArgs, downsampling, nSpeakers, nPhones)
+    criterion.load_state_dict(torch.load(pathCheckpoint, 'cpu')["cpcCriterion"])
+    return criterion
+
+
+TEMPORAL_CONVENTIONS = ['id_spkr_onset_offset', 'id_spkr_onset_offset_spkr_onset_offset', 'spkr-id', 'spkr_id_nb',
+                        'spkr-id-nb', 'no_speaker', 'full_seedlings']
+# train.py:273-277: what a resumed run takes from ITS command line, not from the checkpoint's arguments
+FORBIDDEN_ON_RESUME = {"nGPU", "pathCheckpoint", "debug", "restart", "world_size", "global_rank", "local_rank", "n_nodes",
+                       "node_id", "n_gpu_per_node", "max_size_loaded", "nEpoch", "save_step"}
+
+
+def parseArgs(argv):
+    """train.py:550-682: the same groups, flags, defaults, derived values and errors."""
+    import argparse
+    import os
+    import random
+    import sys
+    from .cpc_default_config import set_default_cpc_config
+    parser = set_default_cpc_config(argparse.ArgumentParser(description='Trainer', prog='python -m cpc2_amd.train'))
+    g = parser.add_argument_group('Dataset')
+    g.add_argument('--pathDB', type=str, default=None, help='Directory of the audio files.')
+    g.add_argument('--file_extension', type=str, default=".flac", help='Extension of the audio files.')
+    g.add_argument('--pathTrain', type=str, default=None, help='Text file listing the training sequences.')
+    g.add_argument('--pathVal', type=str, default=None, help='Text file listing the validation sequences.')
+    g.add_argument('--n_process_loader', type=int, default=8, help='Accepted; files are decoded in this process.')
+    g.add_argument('--ignore_cache', action='store_true',
+                   help='List the data set again instead of reading its sequence cache (which is keyed by nothing: use '
+                        'this after changing the data, the extension, --naming_convention or --no_speaker).')
+    g.add_argument('--path_cache', type=str, default=None,
+                   help='Where the sequence cache lives (default: _seqs_cache.txt inside --pathDB).')
+    g.add_argument('--max_size_loaded', type=int, default=4000000000, help='Samples resident on the device at a time.')
+    g = parser.add_argument_group('Supervised mode (refused: see cpc2_amd.eval.linear_separability --unfrozen)')
+    g.add_argument('--supervised', action='store_true')
+    g.add_argument('--pathPhone', type=str, default=None)
+    g.add_argument('--CTC', action='store_true')
+    g = parser.add_argument_group('Save')
+    g.add_argument('--pathCheckpoint', type=str, default=None, help='Output directory.')
+    g.add_argument('--logging_step', type=int, default=1000)
+    g.add_argument('--save_step', type=int, default=5, help='Epochs between two checkpoints.')
+    g = parser.add_argument_group('Load')
+    g.add_argument('--load', type=str, default=None, nargs='*',
+                   help='A checkpoint (.pt) to start from; its directory holds checkpoint_args.json and checkpoint_logs.json.')
+    g.add_argument('--loadCriterion', action='store_true', help='With --load: the criterion weights too.')
+    g.add_argument('--restart', action='store_true', help='Ignore the checkpoints found in --pathCheckpoint.')
+    g = parser.add_argument_group('GPUs')
+    g.add_argument('--nGPU', type=int, default=-1,
+                   help='One GPU per process here: 1 (or 0); -1 resolves to the device count. Several GPUs: --distributed.')
+    g.add_argument('--batchSizeGPU', type=int, default=8, help='Windows per batch and GPU.')
+    parser.add_argument('--debug', action='store_true', help='Keep the last 1000 / 100 files only.')
+    g = parser.add_argument_group('Distributed training')
+    g.add_argument('--distributed', action='store_true', help='One process per GPU, started by torch.distributed.run.')
+    g.add_argument("--local_rank", type=int, default=-1)
+    g.add_argument("--master_port", type=int, default=-1)
+    args = parser.parse_args(argv)
+
+    if args.pathDB is None and (args.pathCheckpoint is None or args.restart):
+        parser.print_help()
+        print("Either provides an input dataset or a checkpoint to load")
+        sys.exit()
+    assert args.bandreject_scaler >= 0
+    if args.samplingType == "temporalsamespeaker" and (args.pathTrain is not None or args.pathVal is not None):
+        raise ValueError("Can not apply temporal sampling (with same speaker) if pathTrain or pathVal is specified.\n"
+                         "Sequences are loaded in temporal order, and a list of utterances could break it.")
+    if args.samplingType == "temporalsamespeaker" and args.naming_convention not in TEMPORAL_CONVENTIONS:
+        raise ValueError("temporalsamespeaker sampling needs --naming_convention (one of %s): the files have to be sorted in "
+                         "time." % TEMPORAL_CONVENTIONS)
+    if not args.meta_aug and (args.meta_aug_type is not None or args.meta_aug_type == "none"):
+        raise ValueError("You specified parameters --meta_aug_type without having activated --meta_aug flag.")
+    if args.meta_aug and args.meta_aug_type is None or args.meta_aug_type == "none":
+        raise ValueError("You specified flag --meta_aug, but you haven't specified meta_aug_type")
+    if args.pathCheckpoint is not None:
+        args.pathCheckpoint = os.path.abspath(args.pathCheckpoint)
+    if args.load is not None:
+        args.load = [os.path.abspath(x) for x in args.load]
+    if args.random_seed is None:                        # drawn here so that it is dumped with the other arguments
+        args.random_seed = random.randint(0, 2**31)
+    if args.nGPU < 0:
+        args.nGPU = torch.cuda.device_count()
+    assert args.nGPU <= torch.cuda.device_count(), \
+        f"number of GPU asked: {args.nGPU}, number GPU detected: {torch.cuda.device_count()}"
+    print(f"Let's use {args.nGPU} GPUs!")
+    if args.arMode == 'no_ar':
+        args.hiddenGar = args.hiddenEncoder
+    return args
+
+
+def refuseUnsupported(args):
+    """What the command line accepts (for the sake of checkpoint_args.json) and this package does not do: refused with the
+    flag's name and, where there is one, the way that works -- before any file is read."""
+    if args.nGPU > 1 and not args.distributed:
+        raise SystemExit(f"--nGPU {args.nGPU}: this package runs one GPU per process (there is no DataParallel wrapper); run "
+                         f"with --nGPU 1, or one process per GPU: python -m torch.distributed.run --nproc_per_node {args.nGPU} "
+                         "-m cpc2_amd.train --distributed ...")
+    augmenting = args.augment_type is not None and list(args.augment_type) != ['none']
+    if (args.augment_past or args.augment_future) and augmenting:
+        raise NotImplementedError(f"--augment_past / --augment_future with --augment_type {' '.join(args.augment_type)}: audio "
+                                  "augmentation is not on the MI355X feeder path (only --augment_type none)")
+    if args.encoder_type in ("mfcc", "lfb"):
+        raise NotImplementedError(f"--encoder_type {args.encoder_type}: only the raw-waveform encoder (--encoder_type cpc) is built")
+    if args.cpc_mode == "bert":
+        raise NotImplementedError("--cpc_mode bert: the BERT objective is not built (--cpc_mode reverse, none, or no flag)")
+    if args.normMode != "layerNorm":
+        raise NotImplementedError(f"--normMode {args.normMode}: the encoder kernels normalise with layerNorm only")
+    if args.rnnMode in ("ffd", "conv4", "conv8", "conv12", "transformer_adaptive_span"):
+        raise NotImplementedError(f"--rnnMode {args.rnnMode}: the predictors with a kernel path are linear, transformer, LSTM "
+                                  "and RNN")
+    if args.multihead_rnn and args.rnnMode != "transformer":
+        raise NotImplementedError(f"--multihead_rnn with --rnnMode {args.rnnMode}: the multi-head predictor is a transformer "
+                                  "(--rnnMode transformer)")
+    if args.supervised:
+        raise NotImplementedError("--supervised: the supervised criteria are not trained through this loop (in the reference this "
+                                  "path fails at the first step: its trainStep hands the criterion an argument too many); train "
+                                  "them with python -m cpc2_amd.eval.linear_separability --unfrozen")
+
+
+def main(argv):
+    """cpc/train.py:260-547, step for step: a checkpoint found in --pathCheckpoint is resumed (its arguments win except
+    FORBIDDEN_ON_RESUME), the seed, the CONFIG dump, the listing (findAllSeqs with the naming convention and the sequence
+    cache), --pathTrain / --pathVal or the 95 / 5 split, --debug, the per-rank shard, the two AudioBatchData, the model and
+    criterion (--load [--loadCriterion], or built from the arguments), the optimiser (state loaded on resume),
+    checkpoint_args.json, the scheduler fast-forwarded over the epochs done, run().  Returns a namespace of what it built
+    (args, logs, cpcModel, cpcCriterion, optimizer, scheduler).
+
+    Where this package departs from the reference, so does main:
+      * no DataParallel / DistributedDataParallel wrappers: run() builds a DataParallelContext.  One GPU per process --
+        --nGPU above 1 without --distributed is refused; --distributed reads the torch.distributed.run environment
+        (init_distributed_mode) instead of SLURM's;
+      * what refuseUnsupported lists is refused before any file is read (and again for the arguments of a resumed run);
+      * no validation sequence is an error here (the reference builds no validation set and fails inside run());
+      * logs that lack saveStep / logging_step (a hand-made run directory) get them from the command line;
+      * audio files are decoded in this process: --n_process_loader is accepted and unused."""
+    import os
+    from . import feature_loader as fl
+    from .dataset import AudioBatchData, filterSeqs, findAllSeqs, shard_for_rank
+    args = parseArgs(argv)
+    refuseUnsupported(args)
+
+    logs = {"epoch": [], "iter": [], "saveStep": args.save_step}
+    logs["logging_step"] = args.logging_step
+    loadOptimizer = False
+    if args.pathCheckpoint is not None and not args.restart:
+        cdata = fl.getCheckpointData(args.pathCheckpoint)
+        if cdata is not None:
+            data, logs, locArgs = cdata
+            print(f"Checkpoint detected at {data}")
+            fl.loadArgs(args, locArgs, forbiddenAttr=FORBIDDEN_ON_RESUME)
+            args.load, loadOptimizer = [data], True
+            args.loadCriterion = True
+            refuseUnsupported(args)
+            logs.setdefault("saveStep", args.save_step)         # (a hand-made run directory: run() reads both)
+            if args.random_seed is None:                        # (... whose arguments may hold no seed either)
+                import random
+                args.random_seed = random.randint(0, 2**31)
+    logs["logging_step"] = args.logging_step
+    if args.nGPU == 0:
+        args.nGPU = 1
+    if args.pathDB is None:
+        raise ValueError("--pathDB is missing and the checkpoint's arguments hold none")
+    if args.signal_quality_path is not None and not os.path.exists(args.signal_quality_path):
+        raise ValueError("%s can't be found. Are you sure you provided the right location ?" % args.signal_quality_path)
+    batchSize = args.nGPU * args.batchSizeGPU
+
+    if args.distributed:
+        print('Distributed mode, moving to 1 process for data loading')
+        args.n_process_loader = 1
+        args.global_rank, args.local_rank, args.world_size = init_distributed_mode()
+    args.is_local_master = (not args.distributed) or (args.global_rank == 0)
+
+    set_seed(args.random_seed)
+    print(f'CONFIG:\n{json.dumps(vars(args), indent=4, sort_keys=True)}')
+    print('-' * 50)
+
+    seqNames, speakers = findAllSeqs(args.pathDB, no_speaker=args.no_speaker, extension=args.file_extension,
+                                     loadCache=not args.ignore_cache, format=args.naming_convention,
+                                     cache_path=args.path_cache)
+    print(f'Found files: {len(seqNames)} seqs, {len(speakers)} speakers')
+    seqTrain = filterSeqs(args.pathTrain, seqNames) if args.pathTrain is not None else seqNames
+    if len(seqTrain) == 0:
+        raise ValueError("No training sequences can be found. Please check that you provided the right path, and specified "
+                         "the right audio extension.")
+    if args.pathVal is None:
+        print('No validation data specified!')
+        seqTrain, seqVal = splitTrainVal(seqTrain, args.samplingType)
+        print(f'Found files: {len(seqTrain)} train, {len(seqVal)} val')
+    else:
+        seqVal = filterSeqs(args.pathVal, seqNames)
+    if args.debug:
+        seqTrain = seqTrain[-1000:]
+        seqVal = seqVal[-100:]
+    if args.distributed:
+        print(f'Initial worker files: {len(seqTrain)} train, {len(seqVal)} val')
+        seqTrain = shard_for_rank(seqTrain, args.global_rank, args.world_size)
+        seqVal = shard_for_rank(seqVal, args.global_rank, args.world_size)
+        print(f'Current worker files: {len(seqTrain)} train, {len(seqVal)} val')
+    if not seqTrain:
+        raise ValueError("No training sequences are left after the train / validation split (a single file goes to validation).")
+    if not seqVal:
+        raise ValueError("No validation sequences: the 95 / 5 split (or --pathVal) left none, and every epoch validates. "
+                         "Give more files, or --pathVal.")
+
+    print(f'\nLoading audio data at {args.pathDB}')
+    print("Loading the training dataset")
+    trainDataset = AudioBatchData(args.pathDB, args.sizeWindow, seqTrain, None, len(speakers),
+                                  nProcessLoader=args.n_process_loader, MAX_SIZE_LOADED=args.max_size_loaded,
+                                  keep_temporality=args.samplingType == "temporalsamespeaker",
+                                  signal_quality_path=args.signal_quality_path, signal_quality_step=args.signal_quality_step,
+                                  signal_quality_mode=args.signal_quality_mode, past_equal_future=args.past_equal_future)
+    print("Training dataset loaded\n")
+    print("Loading the validation dataset")
+    valDataset = AudioBatchData(args.pathDB, args.sizeWindow, seqVal, None, len(speakers),
+                                nProcessLoader=args.n_process_loader)
+    print("Validation dataset loaded\n")
+    device = torch.device("cuda", torch.cuda.current_device())       # (the feeder's default device too)
+
+    if args.load is not None:
+        cpcModel, args.hiddenGar, args.hiddenEncoder = fl.loadModel(args.load)
+    else:
+        cpcModel = CPCModel(getEncoder(args), getAR(args), args.mask_prob, args.mask_length)
+    downsampling = cpcModel.gEncoder.DOWNSAMPLING
+    print(args)
+    if args.load is not None and args.loadCriterion:
+        cpcCriterion = loadCriterion(args.load[0], downsampling, len(speakers), None)
+    else:
+        cpcCriterion = getCriterion(args, downsampling, len(speakers), None)
+    if loadOptimizer:
+        cpcCriterion.load_state_dict(torch.load(args.load[0], 'cpu')["cpcCriterion"])
+    cpcCriterion.to(device)
+    cpcModel.to(device)
+
+    print("Using Adam optimizer." if args.optimizer == 'adam' else "Using SGD optimizer.")
+    optimizer = buildOptimizer(cpcModel, cpcCriterion, lr=args.learningRate, beta1=args.beta1, beta2=args.beta2,
+                               epsilon=args.epsilon, optimizer=args.optimizer)
+    if loadOptimizer:
+        print("Loading optimizer " + args.load[0])
+        state_dict = torch.load(args.load[0], 'cpu')
+        if "optimizer" in state_dict:
+            optimizer.load_state_dict(state_dict["optimizer"])
+
+    if args.pathCheckpoint is not None:
+        os.makedirs(args.pathCheckpoint, exist_ok=True)
+        args.pathCheckpoint = os.path.join(args.pathCheckpoint, "checkpoint")
+        if args.is_local_master:
+            with open(args.pathCheckpoint + "_args.json", 'w') as file:
+                json.dump(vars(args), file, indent=2)
+
+    if args.schedulerRamp is not None:
+        print(f"Ramp activated. n_e = {args.schedulerRamp}")
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")                 # (fast-forwarding steps the scheduler before the optimiser, as the reference does)
+        scheduler = buildScheduler(optimizer, args.schedulerStep, args.schedulerRamp, epochs_done=len(logs["epoch"]))
+
+    print('args.local_rank: ' + str(args.local_rank))
+    run(trainDataset, valDataset, batchSize, args.samplingType, cpcModel, cpcCriterion, args.nEpoch,
+        args.pathCheckpoint if args.is_local_master else None, optimizer, scheduler, logs, args.no_artefacts,
+        args.batchSizeGPU)
+    import types
+    return types.SimpleNamespace(args=args, logs=logs, cpcModel=cpcModel, cpcCriterion=cpcCriterion, optimizer=optimizer,
+                                 scheduler=scheduler)
+
+
+if __name__ == "__main__":
+    import sys
+    from cpc2_amd.train import main as _main        # (the package's copy of this module, not the __main__ one)
+    _main(sys.argv[1:])

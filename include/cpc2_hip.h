@@ -466,6 +466,16 @@ int cpc_adam_step(float *p, const float *g, float *m, float *v, long n, int step
                   float beta1, float beta2, float eps, float grad_scale, cpc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * SGD with momentum on one flat fp32 buffer (torch.optim.SGD as built at train.py:480-482: momentum 0.9,
+ * no dampening, no weight decay, no nesterov).  g is multiplied by grad_scale first.
+ *   step == 1: buf = g ; step > 1: buf = momentum buf + g ;   p -= lr buf
+ * One launch.  Non-finite gradient elements: the rule of cpc_adam_step (p and buf of that element unchanged,
+ * asynchronous error word set, the finite elements applied).
+ * ------------------------------------------------------------------------------------------ */
+int cpc_sgd_step(float *p, const float *g, float *buf, long n, int step, float lr, float momentum,
+                 float grad_scale, cpc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * ABX phone discriminability (cpc/eval/ABX/abx_group_computation.py, dtw.pyx of the reference).
  *
  * Items are spans of frames in one fp32 buffer `frames` [total_frames][dp] (dp a multiple of 4; padding columns zero);
