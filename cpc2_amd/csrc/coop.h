@@ -141,10 +141,4 @@ template <typename K> static inline bool coop_fits(K kernel, unsigned grid, int 
     return per_cu >= 1 && (int)grid <= n_cus;   // one workgroup per CU is what the grouping assumes
 }
 
-// granules of the backward kernels: [groups][2][G][NB][H] with groups*NB < N + 8 windows and G <= 16
-static inline size_t coop_comm_bytes(int H, int N)
-{
-    return (H == 256 || H == 512) ? sizeof(gu64_t) * 2 * 16 * (size_t)(N + 8) * H : 256;
-}
-
 }  // namespace cpc

@@ -10,6 +10,7 @@
 // is streamed from L2 every step.  Backward mirrors it (BPTT), then three GEMMs give dW_hh, dW_ih and dX.
 #include "common.h"
 #include "coop.h"
+#include "recurrent.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -563,7 +564,7 @@ template <int H, int NB> __global__ __launch_bounds__(512) void gru_fwd_mfma_ker
 // Backward twin of gru_fwd_coop_kernel: member m keeps the SAME 3 U rows of W_hh (its U units x 3 gates) in
 // registers, now one COLUMN j' per thread (thread (j', half): 96 rows), forms its partial W_hh^T dGH for all H
 // columns and the members exchange the U-column pieces the others own.
-//   comm: [groups][2][G (sender)][NB][H] granules, zeroed before the launch.
+//   comm: [groups][2][G (sender)][NB][H] granules (their epochs tell the launches apart: coop_comm_acquire).
 template <int H, int NB> __global__ __launch_bounds__(512) void gru_bwd_coop_kernel(GruCoopArgs ca)
 {
     using C = CoopCfg<H>;
@@ -889,258 +890,64 @@ static bool mfma_wanted(int H, int nb, bool backward)
     if (off) return false;
     return all || (H == 512 && nb == 8) || (backward && H == 256 && nb >= 2);
 }
-template <int H, int NB> static bool mfma_fits_fwd() { static const bool f = coop_fits(gru_fwd_mfma_kernel<H, NB>, 1, 1); return f; }
-template <int H, int NB> static bool mfma_fits_bwd() { static const bool f = coop_fits(gru_bwd_mfma_kernel<H, NB>, 1, 1); return f; }
 
-template <int H> static void launch_coop_fwd(int nb, dim3 grid, hipStream_t st, const GruCoopArgs &ca)
-{
-    coop_count_launch();
-    const bool mm = mfma_wanted(H, nb, false);
-    if (nb == 1) { if (mm && mfma_fits_fwd<H, 1>()) hipLaunchKernelGGL((gru_fwd_mfma_kernel<H, 1>), grid, dim3(512), 0, st, ca); else hipLaunchKernelGGL((gru_fwd_coop_kernel<H, 1>), grid, dim3(512), 0, st, ca); }
-    else if (nb == 2) { if (mm && mfma_fits_fwd<H, 2>()) hipLaunchKernelGGL((gru_fwd_mfma_kernel<H, 2>), grid, dim3(512), 0, st, ca); else hipLaunchKernelGGL((gru_fwd_coop_kernel<H, 2>), grid, dim3(512), 0, st, ca); }
-    else if (nb == 4) { if (mm && mfma_fits_fwd<H, 4>()) hipLaunchKernelGGL((gru_fwd_mfma_kernel<H, 4>), grid, dim3(512), 0, st, ca); else hipLaunchKernelGGL((gru_fwd_coop_kernel<H, 4>), grid, dim3(512), 0, st, ca); }
-    else { if (mm && mfma_fits_fwd<H, 8>()) hipLaunchKernelGGL((gru_fwd_mfma_kernel<H, 8>), grid, dim3(512), 0, st, ca); else hipLaunchKernelGGL((gru_fwd_coop_kernel<H, 8>), grid, dim3(512), 0, st, ca); }
-}
-template <int H> static void launch_coop_bwd(int nb, dim3 grid, hipStream_t st, const GruCoopArgs &ca)
-{
-    coop_count_launch();
-    const bool mm = mfma_wanted(H, nb, true);
-    if (nb == 1) { if (mm && mfma_fits_bwd<H, 1>()) hipLaunchKernelGGL((gru_bwd_mfma_kernel<H, 1>), grid, dim3(512), 0, st, ca); else hipLaunchKernelGGL((gru_bwd_coop_kernel<H, 1>), grid, dim3(512), 0, st, ca); }
-    else if (nb == 2) { if (mm && mfma_fits_bwd<H, 2>()) hipLaunchKernelGGL((gru_bwd_mfma_kernel<H, 2>), grid, dim3(512), 0, st, ca); else hipLaunchKernelGGL((gru_bwd_coop_kernel<H, 2>), grid, dim3(512), 0, st, ca); }
-    else if (nb == 4) { if (mm && mfma_fits_bwd<H, 4>()) hipLaunchKernelGGL((gru_bwd_mfma_kernel<H, 4>), grid, dim3(512), 0, st, ca); else hipLaunchKernelGGL((gru_bwd_coop_kernel<H, 4>), grid, dim3(512), 0, st, ca); }
-    else { if (mm && mfma_fits_bwd<H, 8>()) hipLaunchKernelGGL((gru_bwd_mfma_kernel<H, 8>), grid, dim3(512), 0, st, ca); else hipLaunchKernelGGL((gru_bwd_coop_kernel<H, 8>), grid, dim3(512), 0, st, ca); }
-}
+// what the shared host driver (recurrent.h) needs to know about the GRU
+struct GruCell {
+    static constexpr int G = 3;
+    static constexpr const char *name = "gru", *kernel_names[2] = {"gru_fwd_kernel", "gru_bwd_kernel"},
+                                *pack_names[2] = {"gru_pack_fwd_kernel", "gru_pack_bwd_kernel"};
+    using Args = GruArgs;
+    using CoopArgs = GruCoopArgs;
+    using CoopKernel = void (*)(GruCoopArgs);
+    static constexpr auto fwd_kernel = gru_fwd_kernel, bwd_kernel = gru_bwd_kernel;
 
-// does the cooperative kernel fit a CU, and the grid the chip?  (cached per instance: the occupancy query is not free)
-template <int H> static bool coop_fwd_fits(int nb, unsigned grid, int n_cus)
-{
-    static int ok[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};        // 0 unknown, 1 fits a CU, -1 does not
-    if (ok[nb] == 0)
-        ok[nb] = (nb == 1 ? coop_fits(gru_fwd_coop_kernel<H, 1>, 1, 1) : nb == 2 ? coop_fits(gru_fwd_coop_kernel<H, 2>, 1, 1)
-                  : nb == 4 ? coop_fits(gru_fwd_coop_kernel<H, 4>, 1, 1) : coop_fits(gru_fwd_coop_kernel<H, 8>, 1, 1)) ? 1 : -1;
-    return ok[nb] == 1 && (int)grid <= n_cus;
-}
-template <int H> static bool coop_bwd_fits(int nb, unsigned grid, int n_cus)
-{
-    static int ok[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (ok[nb] == 0)
-        ok[nb] = (nb == 1 ? coop_fits(gru_bwd_coop_kernel<H, 1>, 1, 1) : nb == 2 ? coop_fits(gru_bwd_coop_kernel<H, 2>, 1, 1)
-                  : nb == 4 ? coop_fits(gru_bwd_coop_kernel<H, 4>, 1, 1) : coop_fits(gru_bwd_coop_kernel<H, 8>, 1, 1)) ? 1 : -1;
-    return ok[nb] == 1 && (int)grid <= n_cus;
-}
-
-// ------------------------------------------------------------------------------------------------
-struct GruLayout {
-    int N, T, Din, H, layers;
-    // saved, per layer
-    float *gates[8], *hn[8], *hall[8], *outl[8];
-    size_t saved_bytes;
-    // scratch
-    float *gi, *dgi, *dgh, *dxa, *dxb, *wt_l[8], *cs, *tn, *tn2;
-    float *dgi_l[8], *dgh_l[8];            // layers 1..: gate gradients of their own (deferred tail: the side stream still reads them)
-    size_t tn2_bytes;
-    float4 *wpack;
-    unsigned long long *comm;
-    size_t comm_bytes;
-    size_t tn_bytes, scratch_bytes;
+    static void take_saved(RecLayout &g, Carver &sv, int l)
+    {
+        g.gates[l] = sv.take<float>((size_t)g.N * g.T * 3 * g.H);
+        g.extra[l] = sv.take<float>((size_t)g.N * g.T * g.H);             // hn
+        g.hall[l] = sv.take<float>((size_t)g.N * (g.T + 1) * g.H);
+    }
+    static void cell_args(GruArgs &a, float *hn, const float *, float *) { a.hn = hn; }
+    static void pack(bool backward, const float *w_hh, float4 *wpack, int H, hipStream_t st)
+    {
+        hipLaunchKernelGGL((backward ? gru_pack_bwd_kernel : gru_pack_fwd_kernel), dim3(256), dim3(256), 0, st, w_hh, wpack, H);
+    }
+    // the matrix-pipe form where mfma_wanted says so and it fits a CU too
+    template <auto Plain, auto Mfma> static CoopKernel pick(bool mfma)
+    {
+        if (!coop_kernel_fits<Plain>()) return nullptr;
+        return mfma && coop_kernel_fits<Mfma>() ? Mfma : Plain;
+    }
+    static CoopKernel coop_kernel(bool backward, int H, int nb)
+    {
+        return coop_dispatch(H, nb, [&](auto h, auto n) -> CoopKernel {
+            constexpr int HH = decltype(h)::value, NB = decltype(n)::value;
+            if (backward) return pick<gru_bwd_coop_kernel<HH, NB>, gru_bwd_mfma_kernel<HH, NB>>(mfma_wanted(HH, NB, true));
+            return pick<gru_fwd_coop_kernel<HH, NB>, gru_fwd_mfma_kernel<HH, NB>>(mfma_wanted(HH, NB, false));
+        });
+    }
 };
-
-static int gru_layout(GruLayout &g, int N, int T, int Din, int H, int layers, void *saved, void *scratch)
-{
-    CPC_REQUIRE(N > 0 && T > 0 && Din > 0, "gru: bad shape n=%d t=%d in=%d", N, T, Din);
-    CPC_REQUIRE(H % 4 == 0 && H >= 4 && H <= 1024, "gru: hidden %d must be a multiple of 4 and <= 1024", H);
-    CPC_REQUIRE(layers >= 1 && layers <= 8, "gru: 1..8 layers supported (got %d)", layers);
-    g.N = N; g.T = T; g.Din = Din; g.H = H; g.layers = layers;
-    Carver sv(saved);
-    for (int l = 0; l < layers; ++l) {
-        g.gates[l] = sv.take<float>((size_t)N * T * 3 * H);
-        g.hn[l] = sv.take<float>((size_t)N * T * H);
-        g.hall[l] = sv.take<float>((size_t)N * (T + 1) * H);
-        g.outl[l] = (l + 1 < layers) ? sv.take<float>((size_t)N * T * H) : nullptr;
-    }
-    g.saved_bytes = sv.used();
-    Carver sc(scratch);
-    const int dmax = std::max(Din, H);
-    g.gi = sc.take<float>((size_t)N * T * 3 * H);
-    g.dgi = g.gi;                                     // forward's GI and backward's dGI never coexist
-    g.dgh = sc.take<float>((size_t)N * (T + 1) * 3 * H);
-    g.dxa = sc.take<float>((size_t)N * T * dmax);
-    g.dxb = sc.take<float>((size_t)N * T * dmax);
-    for (int l = 0; l < layers; ++l) g.wt_l[l] = sc.take<float>((size_t)3 * H * dmax);        // W_ih^T of every layer (backward)
-    g.wpack = sc.take<float4>((size_t)3 * H * H / 4);
-    g.cs = sc.take<float>(colsum_rows_scratch_bytes(3 * H) / sizeof(float));
-    // granules of the cooperative kernels: backward [groups][2][G][NB][H], groups*NB < N + 8 windows, G <= 16
-    g.comm_bytes = coop_comm_bytes(H, N);
-    g.comm = sc.take<unsigned long long>(g.comm_bytes / sizeof(unsigned long long));
-    g.tn_bytes = std::max(gemm_tn_scratch_bytes(3 * H, H, (long)N * (T + 1)), gemm_tn_scratch_bytes(3 * H, dmax, (long)N * T));
-    g.tn_bytes = std::max(g.tn_bytes, gemm_tn_scratch_bytes(3 * H, Din, (long)N * T));
-    // the same room serves an ordered K split of the projections (GI = X W_ih^T, dX = dGI W_ih) when they have few tiles
-    g.tn_bytes = std::max(g.tn_bytes, std::max(gemm_nt_scratch_bytes((long)N * T, 3 * H, dmax), gemm_nt_scratch_bytes((long)N * T, dmax, 3 * H)));
-    g.tn = sc.take<float>(g.tn_bytes / sizeof(float));
-    // (the input-gradient product's K split when the weight-gradient products run beside it on the side stream: gru_backward, defer_tail)
-    g.tn2_bytes = gemm_nt_scratch_bytes((long)N * T, dmax, 3 * H);
-    g.tn2 = sc.take<float>(g.tn2_bytes / sizeof(float));
-    g.dgi_l[0] = g.dgi; g.dgh_l[0] = g.dgh;
-    for (int l = 1; l < layers; ++l) {
-        g.dgi_l[l] = sc.take<float>((size_t)N * T * 3 * H);
-        g.dgh_l[l] = sc.take<float>((size_t)N * (T + 1) * 3 * H);
-    }
-    g.scratch_bytes = sc.used();
-    return CPC_OK;
-}
-
-static int gru_forward(const float *x, const float *const *prm, const float *h0, float *out, float *h_last, void *saved,
-                       void *scratch, int N, int T, int Din, int H, int layers, hipStream_t st)
-{
-    GruLayout g;
-    CPC_TRY(gru_layout(g, N, T, Din, H, layers, saved, scratch));
-    const int hp = std::max(64, (int)cdiv(H, 64) * 64);
-    const int kq = std::max(1, std::min(1024 / hp, H / 4));
-    const float *xin = x;
-    int din = Din;
-    for (int l = 0; l < layers; ++l) {
-        const float *w_ih = prm[4 * l], *w_hh = prm[4 * l + 1], *b_ih = prm[4 * l + 2], *b_hh = prm[4 * l + 3];
-        RowMap none{};
-        none.splitk_scratch = g.tn; none.splitk_bytes = g.tn_bytes;
-        CPC_TRY(gemm_nt(xin, din, w_ih, din, g.gi, 3L * H, b_ih, (long)N * T, 3 * H, din, none, st));
-        GruArgs a{};
-        a.gi = g.gi; a.wpack = g.wpack; a.bhh = b_hh;
-        a.h0 = h0 ? h0 + (size_t)l * N * H : nullptr;
-        a.out = (l + 1 < layers) ? g.outl[l] : out;
-        a.hall = g.hall[l]; a.gates = g.gates[l]; a.hn = g.hn[l];
-        a.hlast = h_last ? h_last + (size_t)l * N * H : nullptr;
-        a.N = N; a.T = T; a.H = H; a.hp = hp; a.kq = kq; a.whh = w_hh;
-        static const int n_cus = coop_cu_count();
-        // the cooperative kernel needs every workgroup resident at once (1 per CU)
-        int G = 0;
-        int nb = coop_allowed() ? coop_windows_per_group(H, N, n_cus, &G) : 0;
-        if (nb != 0 && !(H == 256 ? coop_fwd_fits<256>(nb, (unsigned)(cdiv(N, nb) * G), n_cus) : coop_fwd_fits<512>(nb, (unsigned)(cdiv(N, nb) * G), n_cus)))
-            nb = 0;                             // not resident all at once: the streaming kernel has no such requirement
-        if (nb != 0) {
-            GruCoopArgs ca{};
-            ca.g = a; ca.groups = (int)cdiv(N, nb);
-            ca.xcd_map = (ca.groups % 8 == 0) ? 1 : 0;
-            ca.err = coop_error_word(); ca.fault = coop_fault_injection();
-            CPC_TRY(coop_comm_acquire(sizeof(gu64_t) * (size_t)ca.groups * 2 * nb * H, T, st, &ca.comm, &ca.epoch0));
-            {
-                ProfScope prof(PROF_GRU_FWD, st);
-                const dim3 grid((unsigned)(ca.groups * G));
-                if (H == 256) launch_coop_fwd<256>(nb, grid, st, ca);
-                else launch_coop_fwd<512>(nb, grid, st, ca);
-            }
-        } else {
-            hipLaunchKernelGGL(gru_pack_fwd_kernel, dim3(256), dim3(256), 0, st, w_hh, g.wpack, H);      // (the streaming kernel's weight layout only)
-            CPC_CHECK_LAUNCH("gru_pack_fwd_kernel");
-            ProfScope prof(PROF_GRU_FWD, st);
-            const size_t lds = sizeof(float) * (cdiv(H, 4) * 4 + (size_t)kq * 3 * hp);
-            hipLaunchKernelGGL(gru_fwd_kernel, dim3((unsigned)N), dim3(kq * hp), lds, st, a);
-        }
-        CPC_CHECK_LAUNCH("gru_fwd_kernel");
-        xin = a.out;
-        din = H;
-    }
-    return CPC_OK;
-}
-
-// defer_tail: the weight gradients of every layer (nothing on `st` needs them before the optimiser) are produced on the library's
-// side stream: layer l's beside the recurrent kernel of layer l - 1 (latency-bound: the matrix pipe is idle), layer 0's beside what
-// the caller enqueues next (the encoder's backward: its normalisation / reduction kernels leave the matrix pipe idle for ~0.3 ms per
-// step).  Each layer keeps its gate gradients in a buffer of its own for that.  cpc_side_tail_join makes a stream wait for them
-static int gru_backward(const float *x, const float *const *prm, const float *dout, void *saved, void *scratch, float *dx,
-                        float *const *grads, int N, int T, int Din, int H, int layers, hipStream_t st, bool defer_tail = false)
-{
-    GruLayout g;
-    CPC_TRY(gru_layout(g, N, T, Din, H, layers, saved, scratch));
-    const int hp = std::max(64, (int)cdiv(H, 64) * 64);
-    const int kq = std::max(1, std::min(1024 / hp, H / 4));
-    const float *dcur = dout;
-    // W_ih^T of every layer that has an input gradient, in front of the first recurrent kernel: the transposes depend on the weights
-    // only, and a small kernel queued BEHIND a recurrent kernel starts while the deferred criterion sum / the weight-gradient
-    // products hold the chip on the side stream -- seen at 212 us (3 MB) on the critical path of CPC-large, 5 us alone
-    for (int l = layers - 1; l >= 0; --l)
-        if (l > 0 || dx != nullptr) CPC_TRY(transpose2d(prm[4 * l], g.wt_l[l], 3 * H, (l == 0) ? Din : H, st));
-    for (int l = layers - 1; l >= 0; --l) {
-        const float *w_hh = prm[4 * l + 1];
-        const float *xin = (l == 0) ? x : g.outl[l - 1];
-        const int din = (l == 0) ? Din : H;
-        GruArgs a{};
-        a.wpack = g.wpack; a.hall = g.hall[l]; a.gates = g.gates[l]; a.hn = g.hn[l];
-        a.N = N; a.T = T; a.H = H; a.hp = hp; a.kq = kq; a.whh = w_hh;
-        // (deferred tail: every layer's gate gradients stay where they are until the side stream has used them)
-        float *const dgi = defer_tail ? g.dgi_l[l] : g.dgi, *const dgh = defer_tail ? g.dgh_l[l] : g.dgh;
-        a.dout = dcur; a.dgi = dgi; a.dgh = dgh;
-        CPC_TRY(infonce_deferred_mark(st));       // (see infonce_deferred_start below)
-        static const int n_cus = coop_cu_count();
-        int G = 0;
-        int nb = coop_allowed() ? coop_windows_per_group(H, N, n_cus, &G) : 0;
-        if (nb != 0 && !(H == 256 ? coop_bwd_fits<256>(nb, (unsigned)(cdiv(N, nb) * G), n_cus) : coop_bwd_fits<512>(nb, (unsigned)(cdiv(N, nb) * G), n_cus)))
-            nb = 0;
-        if (nb != 0) {
-            GruCoopArgs ca{};
-            ca.g = a; ca.groups = (int)cdiv(N, nb);
-            ca.xcd_map = (ca.groups % 8 == 0) ? 1 : 0;
-            ca.err = coop_error_word(); ca.fault = coop_fault_injection();
-            CPC_TRY(coop_comm_acquire(sizeof(gu64_t) * (size_t)ca.groups * 2 * G * nb * H, T, st, &ca.comm, &ca.epoch0));
-            {
-                ProfScope prof(PROF_GRU_BWD, st);
-                const dim3 grid((unsigned)(ca.groups * G));
-                if (H == 256) launch_coop_bwd<256>(nb, grid, st, ca);
-                else launch_coop_bwd<512>(nb, grid, st, ca);
-            }
-        } else {
-            hipLaunchKernelGGL(gru_pack_bwd_kernel, dim3(256), dim3(256), 0, st, w_hh, g.wpack, H);
-            CPC_CHECK_LAUNCH("gru_pack_bwd_kernel");
-            ProfScope prof(PROF_GRU_BWD, st);
-            const size_t lds = sizeof(float) * ((size_t)3 * H + (size_t)kq * hp);
-            hipLaunchKernelGGL(gru_bwd_kernel, dim3((unsigned)N), dim3(kq * hp), lds, st, a);
-        }
-        CPC_CHECK_LAUNCH("gru_bwd_kernel");
-        CPC_TRY(infonce_deferred_start(st));      // (no-op unless a deferred criterion backward is waiting to run beside this)
-
-        hipStream_t wst = st;
-        const bool tail = defer_tail;
-        if (tail) CPC_TRY(side_tail_begin(st, &wst));
-        // dW_hh[g][k] = sum_{n,t} dGH[n,t][g] * h_{t-1}[n][k]   (hall row t is h_{t-1}; row T of dGH is zero)
-        CPC_TRY(gemm_tn(dgh, 3L * H, g.hall[l], H, grads[4 * l + 1], H, 3 * H, H, (long)N * (T + 1), g.tn, g.tn_bytes, 0, 0, wst));
-        CPC_TRY(colsum_rows(dgh, 3L * H, (long)N * (T + 1), 3 * H, grads[4 * l + 3], g.cs, wst));
-        // dW_ih[g][k] = sum dGI[n,t][g] * x[n,t][k]
-        CPC_TRY(gemm_tn(dgi, 3L * H, xin, din, grads[4 * l], din, 3 * H, din, (long)N * T, g.tn, g.tn_bytes, 0, 0, wst));
-        CPC_TRY(colsum_rows(dgi, 3L * H, (long)N * T, 3 * H, grads[4 * l + 2], g.cs, wst));
-        if (tail) CPC_TRY(side_tail_end());
-        // dX = dGI . W_ih
-        float *dxl = (l == 0) ? dx : ((l % 2) ? g.dxa : g.dxb);
-        if (dxl != nullptr) {
-            RowMap none{};
-            if (tail) { none.splitk_scratch = g.tn2; none.splitk_bytes = g.tn2_bytes; }        // (g.tn is the side stream's now)
-            else { none.splitk_scratch = g.tn; none.splitk_bytes = g.tn_bytes; }
-            CPC_TRY(gemm_nt(dgi, 3L * H, g.wt_l[l], 3L * H, dxl, din, nullptr, (long)N * T, din, 3 * H, none, st));
-        }
-        dcur = dxl;
-    }
-    return CPC_OK;
-}
 
 }  // namespace cpc
 
+using cpc::GruCell;
+
 extern "C" size_t cpc_gru_saved_bytes(int n, int t, int dim_in, int hidden, int layers)
 {
-    cpc::GruLayout g;
-    if (cpc::gru_layout(g, n, t, dim_in, hidden, layers, nullptr, nullptr) != CPC_OK) return 0;
-    return g.saved_bytes;
+    return cpc::rec_bytes<GruCell>(&cpc::RecLayout::saved_bytes, n, t, dim_in, hidden, layers);
 }
 
 extern "C" size_t cpc_gru_scratch_bytes(int n, int t, int dim_in, int hidden, int layers)
 {
-    cpc::GruLayout g;
-    if (cpc::gru_layout(g, n, t, dim_in, hidden, layers, nullptr, nullptr) != CPC_OK) return 0;
-    return g.scratch_bytes;
+    return cpc::rec_bytes<GruCell>(&cpc::RecLayout::scratch_bytes, n, t, dim_in, hidden, layers);
 }
 
 extern "C" int cpc_gru_forward(const float *x, const float *const *params, const float *h0, float *out, float *h_last,
                                void *saved, void *scratch, int n, int t, int dim_in, int hidden, int layers, cpc_stream_t stream)
 {
     CPC_TRY(cpc::coop_error_take("cpc_gru_forward"));      // a time-out of an earlier cooperative launch surfaces here
-    return cpc::gru_forward(x, params, h0, out, h_last, saved, scratch, n, t, dim_in, hidden, layers, static_cast<hipStream_t>(stream));
+    return cpc::rec_forward<GruCell>(x, params, h0, nullptr, out, h_last, nullptr, saved, scratch, n, t, dim_in, hidden, layers,
+                                     static_cast<hipStream_t>(stream));
 }
 
 extern "C" int cpc_gru_backward(const float *x, const float *const *params, const float *dout, void *saved, void *scratch,
@@ -1149,8 +956,8 @@ extern "C" int cpc_gru_backward(const float *x, const float *const *params, cons
 {
     cpc::coop_count_backward_call();
     CPC_TRY(cpc::coop_error_take("cpc_gru_backward"));      // a time-out of an earlier cooperative launch surfaces here
-    return cpc::gru_backward(x, params, dout, saved, scratch, dx, grads, n, t, dim_in, hidden, layers,
-                             static_cast<hipStream_t>(stream));
+    return cpc::rec_backward<GruCell>(x, params, dout, saved, scratch, dx, grads, n, t, dim_in, hidden, layers,
+                                      static_cast<hipStream_t>(stream), false);
 }
 
 extern "C" int cpc_gru_backward_deferred(const float *x, const float *const *params, const float *dout, void *saved, void *scratch,
@@ -1159,9 +966,10 @@ extern "C" int cpc_gru_backward_deferred(const float *x, const float *const *par
 {
     cpc::coop_count_backward_call();
     CPC_TRY(cpc::coop_error_take("cpc_gru_backward_deferred"));
-    return cpc::gru_backward(x, params, dout, saved, scratch, dx, grads, n, t, dim_in, hidden, layers,
-                             static_cast<hipStream_t>(stream), true);
+    return cpc::rec_backward<GruCell>(x, params, dout, saved, scratch, dx, grads, n, t, dim_in, hidden, layers,
+                                      static_cast<hipStream_t>(stream), true);
 }
+
 
 extern "C" int cpc_side_tail_join(cpc_stream_t stream) { return cpc::side_tail_join(static_cast<hipStream_t>(stream)); }
 extern "C" int cpc_side_tail_wait(cpc_stream_t stream) { return cpc::side_tail_wait(static_cast<hipStream_t>(stream)); }

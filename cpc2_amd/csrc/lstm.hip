@@ -14,6 +14,7 @@
 // dW_ih and dX.  Both bias gradients are column sums of the same pre-activation gradient.
 #include "common.h"
 #include "coop.h"
+#include "recurrent.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -377,7 +378,7 @@ template <int H, int NB> __global__ __launch_bounds__(512) void lstm_fwd_coop_ke
 
 // Backward twin: member m keeps the SAME 4 U rows of W_hh (its U units x 4 gates) in registers, one COLUMN j' per
 // thread (thread (j', half): 128 rows), forms its partial W_hh^T dG for all H columns and the members exchange the
-// U-column pieces the others own.   comm: [groups][2][G (sender)][NB][H] granules, zeroed before the launch.
+// U-column pieces the others own.   comm: [groups][2][G (sender)][NB][H] granules (coop_comm_acquire).
 template <int H, int NB> __global__ __launch_bounds__(512) void lstm_bwd_coop_kernel(LstmCoopArgs ca)
 {
     using C = CoopCfg<H>;
@@ -515,255 +516,54 @@ template <int H, int NB> __global__ __launch_bounds__(512) void lstm_bwd_coop_ke
     }
 }
 
-template <int H> static bool lstm_coop_fwd_fits(int nb, unsigned grid, int n_cus)
-{
-    static int ok[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};        // 0 unknown, 1 fits a CU, -1 does not
-    if (ok[nb] == 0)
-        ok[nb] = (nb == 1 ? coop_fits(lstm_fwd_coop_kernel<H, 1>, 1, 1) : nb == 2 ? coop_fits(lstm_fwd_coop_kernel<H, 2>, 1, 1)
-                  : nb == 4 ? coop_fits(lstm_fwd_coop_kernel<H, 4>, 1, 1) : coop_fits(lstm_fwd_coop_kernel<H, 8>, 1, 1)) ? 1 : -1;
-    return ok[nb] == 1 && (int)grid <= n_cus;
-}
-template <int H> static bool lstm_coop_bwd_fits(int nb, unsigned grid, int n_cus)
-{
-    static int ok[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (ok[nb] == 0)
-        ok[nb] = (nb == 1 ? coop_fits(lstm_bwd_coop_kernel<H, 1>, 1, 1) : nb == 2 ? coop_fits(lstm_bwd_coop_kernel<H, 2>, 1, 1)
-                  : nb == 4 ? coop_fits(lstm_bwd_coop_kernel<H, 4>, 1, 1) : coop_fits(lstm_bwd_coop_kernel<H, 8>, 1, 1)) ? 1 : -1;
-    return ok[nb] == 1 && (int)grid <= n_cus;
-}
-template <int H> static void launch_lstm_coop_fwd(int nb, dim3 grid, hipStream_t st, const LstmCoopArgs &ca)
-{
-    coop_count_launch();
-    if (nb == 1) hipLaunchKernelGGL((lstm_fwd_coop_kernel<H, 1>), grid, dim3(512), 0, st, ca);
-    else if (nb == 2) hipLaunchKernelGGL((lstm_fwd_coop_kernel<H, 2>), grid, dim3(512), 0, st, ca);
-    else if (nb == 4) hipLaunchKernelGGL((lstm_fwd_coop_kernel<H, 4>), grid, dim3(512), 0, st, ca);
-    else hipLaunchKernelGGL((lstm_fwd_coop_kernel<H, 8>), grid, dim3(512), 0, st, ca);
-}
-template <int H> static void launch_lstm_coop_bwd(int nb, dim3 grid, hipStream_t st, const LstmCoopArgs &ca)
-{
-    coop_count_launch();
-    if (nb == 1) hipLaunchKernelGGL((lstm_bwd_coop_kernel<H, 1>), grid, dim3(512), 0, st, ca);
-    else if (nb == 2) hipLaunchKernelGGL((lstm_bwd_coop_kernel<H, 2>), grid, dim3(512), 0, st, ca);
-    else if (nb == 4) hipLaunchKernelGGL((lstm_bwd_coop_kernel<H, 4>), grid, dim3(512), 0, st, ca);
-    else hipLaunchKernelGGL((lstm_bwd_coop_kernel<H, 8>), grid, dim3(512), 0, st, ca);
-}
+// G = 4: LSTM, G = 1: tanh RNN
+template <int GATES> struct LstmCell {
+    static constexpr int G = GATES;
+    static constexpr const char *name = G == 4 ? "lstm" : "rnn", *kernel_names[2] = {"lstm_fwd_kernel", "lstm_bwd_kernel"},
+                                *pack_names[2] = {"lstm_pack_fwd_kernel", "lstm_pack_bwd_kernel"};
+    using Args = LstmArgs;
+    using CoopArgs = LstmCoopArgs;
+    using CoopKernel = void (*)(LstmCoopArgs);
+    static constexpr auto fwd_kernel = lstm_fwd_kernel<G>, bwd_kernel = lstm_bwd_kernel<G>;
 
-struct LstmLayout {
-    int N, T, Din, H, layers, G;
-    // saved, per layer
-    float *gates[8], *hall[8], *call[8], *outl[8];
-    size_t saved_bytes;
-    // scratch
-    float *gi, *dgi, *dgh, *dxa, *dxb, *wt_l[8], *cs, *tn, *tn2;
-    float *dgi_l[8], *dgh_l[8];            // layers 1..: gate gradients of their own (deferred tail: the side stream still reads them)
-    size_t tn2_bytes;
-    float4 *wpack;
-    gu64_t *comm;
-    size_t comm_bytes;
-    size_t tn_bytes, scratch_bytes;
+    static void take_saved(RecLayout &g, Carver &sv, int l)
+    {
+        if (G == 4) g.gates[l] = sv.take<float>((size_t)g.N * g.T * 4 * g.H);
+        g.hall[l] = sv.take<float>((size_t)g.N * (g.T + 1) * g.H);
+        if (G == 4) g.extra[l] = sv.take<float>((size_t)g.N * (g.T + 1) * g.H);       // call
+    }
+    static void cell_args(LstmArgs &a, float *call, const float *c0, float *clast) { a.call = call; a.c0 = c0; a.clast = clast; }
+    static void pack(bool backward, const float *w_hh, float4 *wpack, int H, hipStream_t st)
+    {
+        hipLaunchKernelGGL((backward ? lstm_pack_bwd_kernel : lstm_pack_fwd_kernel), dim3(256), dim3(256), 0, st, w_hh, wpack, H, G);
+    }
+    // cooperative kernels exist for the LSTM at H = 256 / 512
+    static CoopKernel coop_kernel(bool backward, int H, int nb)
+    {
+        if (G != 4) return nullptr;
+        return coop_dispatch(H, nb, [&](auto h, auto n) -> CoopKernel {
+            constexpr int HH = decltype(h)::value, NB = decltype(n)::value;
+            if (backward) return coop_kernel_fits<lstm_bwd_coop_kernel<HH, NB>>() ? lstm_bwd_coop_kernel<HH, NB> : nullptr;
+            return coop_kernel_fits<lstm_fwd_coop_kernel<HH, NB>>() ? lstm_fwd_coop_kernel<HH, NB> : nullptr;
+        });
+    }
 };
-
-int lstm_layout(LstmLayout &g, int G, int N, int T, int Din, int H, int layers, void *saved, void *scratch)
-{
-    const char *who = G == 4 ? "lstm" : "rnn";
-    CPC_REQUIRE(N > 0 && T > 0 && Din > 0, "%s: bad shape n=%d t=%d in=%d", who, N, T, Din);
-    CPC_REQUIRE(H % 4 == 0 && H >= 4 && H <= 1024, "%s: hidden %d must be a multiple of 4 and <= 1024", who, H);
-    CPC_REQUIRE(layers >= 1 && layers <= 8, "%s: 1..8 layers supported (got %d)", who, layers);
-    g.N = N; g.T = T; g.Din = Din; g.H = H; g.layers = layers; g.G = G;
-    Carver sv(saved);
-    for (int l = 0; l < layers; ++l) {
-        g.gates[l] = G == 4 ? sv.take<float>((size_t)N * T * 4 * H) : nullptr;
-        g.hall[l] = sv.take<float>((size_t)N * (T + 1) * H);
-        g.call[l] = G == 4 ? sv.take<float>((size_t)N * (T + 1) * H) : nullptr;
-        g.outl[l] = (l + 1 < layers) ? sv.take<float>((size_t)N * T * H) : nullptr;
-    }
-    g.saved_bytes = sv.used();
-    Carver sc(scratch);
-    const int dmax = std::max(Din, H);
-    g.gi = sc.take<float>((size_t)N * T * G * H);
-    g.dgi = g.gi;                                     // forward's GI and backward's dGI never coexist
-    g.dgh = sc.take<float>((size_t)N * (T + 1) * G * H);
-    g.dxa = sc.take<float>((size_t)N * T * dmax);
-    g.dxb = sc.take<float>((size_t)N * T * dmax);
-    for (int l = 0; l < layers; ++l) g.wt_l[l] = sc.take<float>((size_t)G * H * dmax);        // W_ih^T of every layer (backward)
-    g.wpack = sc.take<float4>((size_t)G * H * H / 4);
-    g.cs = sc.take<float>(colsum_rows_scratch_bytes(G * H) / sizeof(float));
-    g.comm_bytes = G == 4 ? coop_comm_bytes(H, N) : 256;
-    g.comm = sc.take<gu64_t>(g.comm_bytes / sizeof(gu64_t));
-    g.tn_bytes = std::max(gemm_tn_scratch_bytes(G * H, H, (long)N * (T + 1)), gemm_tn_scratch_bytes(G * H, dmax, (long)N * T));
-    g.tn_bytes = std::max(g.tn_bytes, gemm_tn_scratch_bytes(G * H, Din, (long)N * T));
-    // the same room serves an ordered K split of the projections when they have few tiles
-    g.tn_bytes = std::max(g.tn_bytes, std::max(gemm_nt_scratch_bytes((long)N * T, G * H, dmax), gemm_nt_scratch_bytes((long)N * T, dmax, G * H)));
-    g.tn = sc.take<float>(g.tn_bytes / sizeof(float));
-    g.tn2_bytes = gemm_nt_scratch_bytes((long)N * T, dmax, G * H);      // (the input-gradient product's K split beside a deferred tail)
-    g.tn2 = sc.take<float>(g.tn2_bytes / sizeof(float));
-    g.dgi_l[0] = g.dgi; g.dgh_l[0] = g.dgh;
-    for (int l = 1; l < layers; ++l) {
-        g.dgi_l[l] = sc.take<float>((size_t)N * T * G * H);
-        g.dgh_l[l] = sc.take<float>((size_t)N * (T + 1) * G * H);
-    }
-    g.scratch_bytes = sc.used();
-    return CPC_OK;
-}
-
-// cooperative kernels exist for the LSTM at H = 256 / 512
-int lstm_coop_windows(int G, int H, int N, int *members)
-{
-    static const int n_cus = coop_cu_count();
-    if (G != 4 || !coop_allowed()) return 0;
-    return coop_windows_per_group(H, N, n_cus, members);
-}
-
-void lstm_threads(int H, int G, int &hp, int &kq)
-{
-    hp = std::max(64, (int)cdiv(H, 64) * 64);
-    kq = std::max(1, std::min(1024 / hp, G * H / 4));
-    kq = std::min(kq, H / 4);
-}
 
 }  // namespace
 
-template <int G>
-static int lstm_forward(const float *x, const float *const *prm, const float *h0, const float *c0, float *out, float *h_last,
-                        float *c_last, void *saved, void *scratch, int N, int T, int Din, int H, int layers, hipStream_t st)
-{
-    LstmLayout g;
-    CPC_TRY(lstm_layout(g, G, N, T, Din, H, layers, saved, scratch));
-    int hp, kq;
-    lstm_threads(H, G, hp, kq);
-    const float *xin = x;
-    int din = Din;
-    for (int l = 0; l < layers; ++l) {
-        const float *w_ih = prm[4 * l], *w_hh = prm[4 * l + 1], *b_ih = prm[4 * l + 2], *b_hh = prm[4 * l + 3];
-        RowMap none{};
-        none.splitk_scratch = g.tn; none.splitk_bytes = g.tn_bytes;
-        CPC_TRY(gemm_nt(xin, din, w_ih, din, g.gi, (long)G * H, b_ih, (long)N * T, G * H, din, none, st));
-        LstmArgs a{};
-        a.gi = g.gi; a.wpack = g.wpack; a.whh = w_hh; a.bhh = b_hh;
-        a.h0 = h0 ? h0 + (size_t)l * N * H : nullptr;
-        a.c0 = c0 ? c0 + (size_t)l * N * H : nullptr;
-        a.out = (l + 1 < layers) ? g.outl[l] : out;
-        a.hall = g.hall[l]; a.call = g.call[l]; a.gates = g.gates[l];
-        a.hlast = h_last ? h_last + (size_t)l * N * H : nullptr;
-        a.clast = c_last ? c_last + (size_t)l * N * H : nullptr;
-        a.N = N; a.T = T; a.H = H; a.hp = hp; a.kq = kq;
-        int members = 0;
-        int nb = lstm_coop_windows(G, H, N, &members);
-        if (nb != 0 && !(H == 256 ? lstm_coop_fwd_fits<256>(nb, (unsigned)(cdiv(N, nb) * members), coop_cu_count())
-                                  : lstm_coop_fwd_fits<512>(nb, (unsigned)(cdiv(N, nb) * members), coop_cu_count())))
-            nb = 0;                             // not resident all at once: the streaming kernel has no such requirement
-        if (nb != 0) {
-            LstmCoopArgs ca{};
-            ca.g = a; ca.groups = (int)cdiv(N, nb);
-            ca.xcd_map = (ca.groups % 8 == 0) ? 1 : 0;
-            ca.err = coop_error_word(); ca.fault = coop_fault_injection();
-            CPC_TRY(coop_comm_acquire(sizeof(gu64_t) * (size_t)ca.groups * 2 * nb * H, T, st, &ca.comm, &ca.epoch0));
-            ProfScope prof(PROF_GRU_FWD, st);
-            const dim3 grid((unsigned)(ca.groups * members));
-            if (H == 256) launch_lstm_coop_fwd<256>(nb, grid, st, ca);
-            else launch_lstm_coop_fwd<512>(nb, grid, st, ca);
-        } else {
-            hipLaunchKernelGGL(lstm_pack_fwd_kernel, dim3(256), dim3(256), 0, st, w_hh, g.wpack, H, G);
-            CPC_CHECK_LAUNCH("lstm_pack_fwd_kernel");
-            ProfScope prof(PROF_GRU_FWD, st);
-            const size_t lds = sizeof(float) * (cdiv(H, 4) * 4 + (size_t)kq * G * hp);
-            hipLaunchKernelGGL(lstm_fwd_kernel<G>, dim3((unsigned)N), dim3(kq * hp), lds, st, a);
-        }
-        CPC_CHECK_LAUNCH("lstm_fwd_kernel");
-        xin = a.out;
-        din = H;
-    }
-    return CPC_OK;
-}
-
-template <int G>
-static int lstm_backward(const float *x, const float *const *prm, const float *dout, void *saved, void *scratch, float *dx,
-                         float *const *grads, int N, int T, int Din, int H, int layers, hipStream_t st, bool defer_tail = false)
-{
-    LstmLayout g;
-    CPC_TRY(lstm_layout(g, G, N, T, Din, H, layers, saved, scratch));
-    int hp, kq;
-    lstm_threads(H, G, hp, kq);
-    const float *dcur = dout;
-    // W_ih^T of every layer that has an input gradient, in front of the first recurrent kernel: the transposes depend on the weights
-    // only, and a small kernel queued BEHIND a recurrent kernel starts while the deferred criterion sum / the weight-gradient
-    // products hold the chip on the side stream -- seen at 212 us (3 MB) on the critical path of CPC-large, 5 us alone
-    for (int l = layers - 1; l >= 0; --l)
-        if (l > 0 || dx != nullptr) CPC_TRY(transpose2d(prm[4 * l], g.wt_l[l], G * H, (l == 0) ? Din : H, st));
-    for (int l = layers - 1; l >= 0; --l) {
-        const float *w_hh = prm[4 * l + 1];
-        const float *xin = (l == 0) ? x : g.outl[l - 1];
-        const int din = (l == 0) ? Din : H;
-        LstmArgs a{};
-        a.wpack = g.wpack; a.whh = w_hh; a.hall = g.hall[l]; a.call = g.call[l]; a.gates = g.gates[l];
-        a.N = N; a.T = T; a.H = H; a.hp = hp; a.kq = kq;
-        // (deferred tail: every layer's gate gradients stay where they are until the side stream has used them)
-        float *const dgi = defer_tail ? g.dgi_l[l] : g.dgi, *const dgh = defer_tail ? g.dgh_l[l] : g.dgh;
-        a.dout = dcur; a.dgi = dgi; a.dgh = dgh;
-        CPC_TRY(infonce_deferred_mark(st));       // (see infonce_deferred_start below)
-        int members = 0;
-        int nb = lstm_coop_windows(G, H, N, &members);
-        if (nb != 0 && !(H == 256 ? lstm_coop_bwd_fits<256>(nb, (unsigned)(cdiv(N, nb) * members), coop_cu_count())
-                                  : lstm_coop_bwd_fits<512>(nb, (unsigned)(cdiv(N, nb) * members), coop_cu_count())))
-            nb = 0;
-        if (nb != 0) {
-            LstmCoopArgs ca{};
-            ca.g = a; ca.groups = (int)cdiv(N, nb);
-            ca.xcd_map = (ca.groups % 8 == 0) ? 1 : 0;
-            ca.err = coop_error_word(); ca.fault = coop_fault_injection();
-            CPC_TRY(coop_comm_acquire(sizeof(gu64_t) * (size_t)ca.groups * 2 * members * nb * H, T, st, &ca.comm, &ca.epoch0));
-            ProfScope prof(PROF_GRU_BWD, st);
-            const dim3 grid((unsigned)(ca.groups * members));
-            if (H == 256) launch_lstm_coop_bwd<256>(nb, grid, st, ca);
-            else launch_lstm_coop_bwd<512>(nb, grid, st, ca);
-        } else {
-            hipLaunchKernelGGL(lstm_pack_bwd_kernel, dim3(256), dim3(256), 0, st, w_hh, g.wpack, H, G);
-            CPC_CHECK_LAUNCH("lstm_pack_bwd_kernel");
-            ProfScope prof(PROF_GRU_BWD, st);
-            const size_t lds = sizeof(float) * ((size_t)G * H + (size_t)kq * hp);
-            hipLaunchKernelGGL(lstm_bwd_kernel<G>, dim3((unsigned)N), dim3(kq * hp), lds, st, a);
-        }
-        CPC_CHECK_LAUNCH("lstm_bwd_kernel");
-        CPC_TRY(infonce_deferred_start(st));      // (no-op unless a deferred criterion backward is waiting to run beside this)
-        const int GH = G * H;
-        // (defer_tail: layer 0's weight gradients on the library's side stream, as in gru_backward)
-        hipStream_t wst = st;
-        const bool tail = defer_tail;
-        if (tail) CPC_TRY(side_tail_begin(st, &wst));
-        // dW_hh[g][k] = sum_{n,t} dG[n,t][g] * h_{t-1}[n][k]   (hall row t is h_{t-1}; row T of dGH is zero)
-        CPC_TRY(gemm_tn(dgh, GH, g.hall[l], H, grads[4 * l + 1], H, GH, H, (long)N * (T + 1), g.tn, g.tn_bytes, 0, 0, wst));
-        CPC_TRY(colsum_rows(dgh, GH, (long)N * (T + 1), GH, grads[4 * l + 3], g.cs, wst));
-        // dW_ih[g][k] = sum dG[n,t][g] * x[n,t][k]
-        CPC_TRY(gemm_tn(dgi, GH, xin, din, grads[4 * l], din, GH, din, (long)N * T, g.tn, g.tn_bytes, 0, 0, wst));
-        CPC_TRY(colsum_rows(dgi, GH, (long)N * T, GH, grads[4 * l + 2], g.cs, wst));
-        if (tail) CPC_TRY(side_tail_end());
-        // dX = dG . W_ih
-        float *dxl = (l == 0) ? dx : ((l % 2) ? g.dxa : g.dxb);
-        if (dxl != nullptr) {
-            RowMap none{};
-            if (tail) { none.splitk_scratch = g.tn2; none.splitk_bytes = g.tn2_bytes; }        // (g.tn is the side stream's now)
-            else { none.splitk_scratch = g.tn; none.splitk_bytes = g.tn_bytes; }
-            CPC_TRY(gemm_nt(dgi, GH, g.wt_l[l], GH, dxl, din, nullptr, (long)N * T, din, GH, none, st));
-        }
-        dcur = dxl;
-    }
-    return CPC_OK;
-}
-
 }  // namespace cpc
+
+using cpc::LstmCell;
+using cpc::RecLayout;
 
 extern "C" size_t cpc_lstm_saved_bytes(int n, int t, int dim_in, int hidden, int layers)
 {
-    cpc::LstmLayout g;
-    if (cpc::lstm_layout(g, 4, n, t, dim_in, hidden, layers, nullptr, nullptr) != CPC_OK) return 0;
-    return g.saved_bytes;
+    return cpc::rec_bytes<LstmCell<4>>(&RecLayout::saved_bytes, n, t, dim_in, hidden, layers);
 }
 
 extern "C" size_t cpc_lstm_scratch_bytes(int n, int t, int dim_in, int hidden, int layers)
 {
-    cpc::LstmLayout g;
-    if (cpc::lstm_layout(g, 4, n, t, dim_in, hidden, layers, nullptr, nullptr) != CPC_OK) return 0;
-    return g.scratch_bytes;
+    return cpc::rec_bytes<LstmCell<4>>(&RecLayout::scratch_bytes, n, t, dim_in, hidden, layers);
 }
 
 extern "C" int cpc_lstm_forward(const float *x, const float *const *params, const float *h0, const float *c0, float *out,
@@ -771,8 +571,8 @@ extern "C" int cpc_lstm_forward(const float *x, const float *const *params, cons
                                 int layers, cpc_stream_t stream)
 {
     CPC_TRY(cpc::coop_error_take("cpc_lstm_forward"));      // a time-out of an earlier cooperative launch surfaces here
-    return cpc::lstm_forward<4>(x, params, h0, c0, out, h_last, c_last, saved, scratch, n, t, dim_in, hidden, layers,
-                                static_cast<hipStream_t>(stream));
+    return cpc::rec_forward<LstmCell<4>>(x, params, h0, c0, out, h_last, c_last, saved, scratch, n, t, dim_in, hidden, layers,
+                                         static_cast<hipStream_t>(stream));
 }
 
 extern "C" int cpc_lstm_backward(const float *x, const float *const *params, const float *dout, void *saved, void *scratch,
@@ -781,8 +581,8 @@ extern "C" int cpc_lstm_backward(const float *x, const float *const *params, con
 {
     cpc::coop_count_backward_call();
     CPC_TRY(cpc::coop_error_take("cpc_lstm_backward"));      // a time-out of an earlier cooperative launch surfaces here
-    return cpc::lstm_backward<4>(x, params, dout, saved, scratch, dx, grads, n, t, dim_in, hidden, layers,
-                                 static_cast<hipStream_t>(stream));
+    return cpc::rec_backward<LstmCell<4>>(x, params, dout, saved, scratch, dx, grads, n, t, dim_in, hidden, layers,
+                                          static_cast<hipStream_t>(stream), false);
 }
 
 extern "C" int cpc_lstm_backward_deferred(const float *x, const float *const *params, const float *dout, void *saved, void *scratch,
@@ -791,22 +591,18 @@ extern "C" int cpc_lstm_backward_deferred(const float *x, const float *const *pa
 {
     cpc::coop_count_backward_call();
     CPC_TRY(cpc::coop_error_take("cpc_lstm_backward_deferred"));
-    return cpc::lstm_backward<4>(x, params, dout, saved, scratch, dx, grads, n, t, dim_in, hidden, layers,
-                                 static_cast<hipStream_t>(stream), true);
+    return cpc::rec_backward<LstmCell<4>>(x, params, dout, saved, scratch, dx, grads, n, t, dim_in, hidden, layers,
+                                          static_cast<hipStream_t>(stream), true);
 }
 
 extern "C" size_t cpc_rnn_saved_bytes(int n, int t, int dim_in, int hidden, int layers)
 {
-    cpc::LstmLayout g;
-    if (cpc::lstm_layout(g, 1, n, t, dim_in, hidden, layers, nullptr, nullptr) != CPC_OK) return 0;
-    return g.saved_bytes;
+    return cpc::rec_bytes<LstmCell<1>>(&RecLayout::saved_bytes, n, t, dim_in, hidden, layers);
 }
 
 extern "C" size_t cpc_rnn_scratch_bytes(int n, int t, int dim_in, int hidden, int layers)
 {
-    cpc::LstmLayout g;
-    if (cpc::lstm_layout(g, 1, n, t, dim_in, hidden, layers, nullptr, nullptr) != CPC_OK) return 0;
-    return g.scratch_bytes;
+    return cpc::rec_bytes<LstmCell<1>>(&RecLayout::scratch_bytes, n, t, dim_in, hidden, layers);
 }
 
 extern "C" int cpc_rnn_forward(const float *x, const float *const *params, const float *h0, float *out, float *h_last,
@@ -814,8 +610,8 @@ extern "C" int cpc_rnn_forward(const float *x, const float *const *params, const
                                cpc_stream_t stream)
 {
     CPC_TRY(cpc::coop_error_take("cpc_rnn_forward"));      // a time-out of an earlier cooperative launch surfaces here
-    return cpc::lstm_forward<1>(x, params, h0, nullptr, out, h_last, nullptr, saved, scratch, n, t, dim_in, hidden, layers,
-                                static_cast<hipStream_t>(stream));
+    return cpc::rec_forward<LstmCell<1>>(x, params, h0, nullptr, out, h_last, nullptr, saved, scratch, n, t, dim_in, hidden, layers,
+                                         static_cast<hipStream_t>(stream));
 }
 
 extern "C" int cpc_rnn_backward(const float *x, const float *const *params, const float *dout, void *saved, void *scratch,
@@ -824,6 +620,6 @@ extern "C" int cpc_rnn_backward(const float *x, const float *const *params, cons
 {
     cpc::coop_count_backward_call();
     CPC_TRY(cpc::coop_error_take("cpc_rnn_backward"));      // a time-out of an earlier cooperative launch surfaces here
-    return cpc::lstm_backward<1>(x, params, dout, saved, scratch, dx, grads, n, t, dim_in, hidden, layers,
-                                 static_cast<hipStream_t>(stream));
+    return cpc::rec_backward<LstmCell<1>>(x, params, dout, saved, scratch, dx, grads, n, t, dim_in, hidden, layers,
+                                          static_cast<hipStream_t>(stream), false);
 }

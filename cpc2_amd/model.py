@@ -141,7 +141,7 @@ class _EncoderFn(torch.autograd.Function):
             check(lib.cpc_encoder_backward(ptr(x), ptr_array(params), ptr(dz), ptr(saved), ptr(sc), ptr_array(grads),
                                            n, length, hidden, ctx.eps, stream_ptr(x.device)), "encoder_backward")
         if defer:
-            _keep_for_tail(x.device, (x, x2, saved, params, dz, sc))  # (not `grads`: see _GruFn.backward)
+            _keep_for_tail(x.device, (x, x2, saved, params, dz, sc))  # (not `grads`: see _RecurrentFn.backward)
         return (None, None, None, None) + tuple(grads)
 
 
@@ -193,18 +193,19 @@ class CPCEncoder(nn.Module):
 
 
 # --------------------------------------------------------------------------- CPCAR (GRU / LSTM)
-class _GruFn(torch.autograd.Function):
-    """kind = "gru" or "rnn" (tanh): the two single-state recurrences share one calling convention."""
+class _RecurrentFn(torch.autograd.Function):
+    """kind = "gru", "lstm" or "rnn" (tanh): one calling convention; c0 and the returned c_last are the LSTM's cell state (None for
+    the two single-state recurrences)."""
 
     @staticmethod
-    def forward(ctx, x, h0, n_layers, want_hidden, kind, defer_tail, *params):
+    def forward(ctx, x, h0, c0, n_layers, want_hidden, kind, defer_tail, *params):
         require_gpu(x, *params)
         lib = _lib.load()
         ctx.dx_home = grad_home(x)             # (cpcStep's split_windows: dx has a fixed place in the encoder output's gradient)
         x = f32c(x)
         ctx.param_refs = params
         ctx.kind = kind
-        ctx.defer_tail = bool(defer_tail) and kind == "gru"
+        ctx.defer_tail = bool(defer_tail) and kind != "rnn"        # (there is no cpc_rnn_backward_deferred)
         params = tuple(f32c(p) for p in params)
         n, t, dim_in = x.shape
         hidden = params[1].shape[1]
@@ -214,82 +215,19 @@ class _GruFn(torch.autograd.Function):
             check(-1, f"{kind} shape query")
         out = torch.empty(n, t, hidden, dtype=torch.float32, device=x.device)
         h_last = torch.empty(n_layers, n, hidden, dtype=torch.float32, device=x.device) if want_hidden else None
-        h0c = f32c(h0) if h0 is not None else None
-        saved = torch.empty(nsaved, dtype=torch.uint8, device=x.device)
-        sc = scratch(nscratch, x.device)
-        check(getattr(lib, f"cpc_{kind}_forward")(ptr(x), ptr_array(params), ptr(h0c), ptr(out), ptr(h_last), ptr(saved),
-                                                  ptr(sc), n, t, dim_in, hidden, n_layers, stream_ptr(x.device)),
-              f"{kind}_forward")
-        ctx.save_for_backward(x, saved, *params)
-        ctx.dims = (n, t, dim_in, hidden, n_layers)
-        if want_hidden:
-            ctx.mark_non_differentiable(h_last)
-            return out, h_last
-        return out, None
-
-    @staticmethod
-    def backward(ctx, dout, _dh):
-        lib = _lib.load()
-        x, saved, *params = ctx.saved_tensors
-        n, t, dim_in, hidden, n_layers = ctx.dims
-        dout = f32c(dout)
-        need_dx = ctx.needs_input_grad[0]
-        dx = grad_home_view(ctx.dx_home, x) if need_dx else None
-        grads = grad_buffers(ctx.param_refs)
-        kind = ctx.kind
-        # The deferred form (cpc2_hip.h, cpc_gru_backward_deferred): every layer's weight gradients finish on a stream of the library's
-        # while the encoder's backward runs.  Only inside the caller's scope (CPCAR.deferred_weight_gradients: nothing reads these
-        # gradients before the backward pass has ended) and only when every one of them is written IN PLACE into the flat gradient
-        # buffer -- a private buffer would be added to .grad by autograd the moment this function returns.
-        defer = ctx.defer_tail and _all_in_place(ctx.param_refs, grads)
-        nscratch = getattr(lib, f"cpc_{kind}_scratch_bytes")(n, t, dim_in, hidden, n_layers)
-        if defer:
-            sc = scratch(nscratch, x.device, tag=_tail_tag("gru_tail", x.device))      # a buffer of its own: the side stream outlives this call
-            check(lib.cpc_gru_backward_deferred(ptr(x), ptr_array(params), ptr(dout), ptr(saved), ptr(sc), ptr(dx), ptr_array(grads),
-                                                n, t, dim_in, hidden, n_layers, stream_ptr(x.device)), "gru_backward_deferred")
-            # alive until the join.  NOT `grads`: autograd adopts a returned gradient as .grad only while nobody else holds it -- with a
-            # second reference it CLONES it on the spot (the flat buffer's not yet written bytes) and the clone becomes .grad
-            _keep_for_tail(x.device, (x, saved, params, dout, sc))
-        else:
-            sc = scratch(nscratch, x.device)
-            check(getattr(lib, f"cpc_{kind}_backward")(ptr(x), ptr_array(params), ptr(dout), ptr(saved), ptr(sc), ptr(dx),
-                                                       ptr_array(grads), n, t, dim_in, hidden, n_layers,
-                                                       stream_ptr(x.device)), f"{kind}_backward")
-        return (dx, None, None, None, None, None) + tuple(grads)
-
-
-class _LstmFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, h0, c0, n_layers, want_hidden, defer_tail, *params):
-        require_gpu(x, *params)
-        lib = _lib.load()
-        ctx.dx_home = grad_home(x)
-        x = f32c(x)
-        ctx.param_refs = params
-        ctx.defer_tail = bool(defer_tail)
-        params = tuple(f32c(p) for p in params)
-        n, t, dim_in = x.shape
-        hidden = params[1].shape[1]
-        nsaved = lib.cpc_lstm_saved_bytes(n, t, dim_in, hidden, n_layers)
-        nscratch = lib.cpc_lstm_scratch_bytes(n, t, dim_in, hidden, n_layers)
-        if nsaved == 0:
-            check(-1, "lstm shape query")
-        out = torch.empty(n, t, hidden, dtype=torch.float32, device=x.device)
-        h_last = torch.empty(n_layers, n, hidden, dtype=torch.float32, device=x.device) if want_hidden else None
-        c_last = torch.empty_like(h_last) if want_hidden else None
+        c_last = torch.empty_like(h_last) if want_hidden and kind == "lstm" else None
         h0c = f32c(h0) if h0 is not None else None
         c0c = f32c(c0) if c0 is not None else None
+        state = (ptr(h0c), ptr(c0c), ptr(out), ptr(h_last), ptr(c_last)) if kind == "lstm" else (ptr(h0c), ptr(out), ptr(h_last))
         saved = torch.empty(nsaved, dtype=torch.uint8, device=x.device)
         sc = scratch(nscratch, x.device)
-        check(lib.cpc_lstm_forward(ptr(x), ptr_array(params), ptr(h0c), ptr(c0c), ptr(out), ptr(h_last), ptr(c_last),
-                                   ptr(saved), ptr(sc), n, t, dim_in, hidden, n_layers, stream_ptr(x.device)),
-              "lstm_forward")
+        check(getattr(lib, f"cpc_{kind}_forward")(ptr(x), ptr_array(params), *state, ptr(saved), ptr(sc), n, t, dim_in, hidden,
+                                                  n_layers, stream_ptr(x.device)), f"{kind}_forward")
         ctx.save_for_backward(x, saved, *params)
         ctx.dims = (n, t, dim_in, hidden, n_layers)
         if want_hidden:
-            ctx.mark_non_differentiable(h_last, c_last)
-            return out, h_last, c_last
-        return out, None, None
+            ctx.mark_non_differentiable(*(s for s in (h_last, c_last) if s is not None))
+        return out, h_last, c_last
 
     @staticmethod
     def backward(ctx, dout, _dh, _dc):
@@ -300,18 +238,24 @@ class _LstmFn(torch.autograd.Function):
         need_dx = ctx.needs_input_grad[0]
         dx = grad_home_view(ctx.dx_home, x) if need_dx else None
         grads = grad_buffers(ctx.param_refs)
-        nscratch = lib.cpc_lstm_scratch_bytes(n, t, dim_in, hidden, n_layers)
-        if ctx.defer_tail and _all_in_place(ctx.param_refs, grads):                # (the deferred form: see _GruFn.backward)
-            sc = scratch(nscratch, x.device, tag=_tail_tag("lstm_tail", x.device))
-            check(lib.cpc_lstm_backward_deferred(ptr(x), ptr_array(params), ptr(dout), ptr(saved), ptr(sc), ptr(dx), ptr_array(grads),
-                                                 n, t, dim_in, hidden, n_layers, stream_ptr(x.device)), "lstm_backward_deferred")
+        kind = ctx.kind
+        # The deferred form (cpc2_hip.h, cpc_gru_backward_deferred / cpc_lstm_backward_deferred): every layer's weight gradients finish
+        # on a stream of the library's while the encoder's backward runs.  Only inside the caller's scope
+        # (CPCAR.deferred_weight_gradients: nothing reads these gradients before the backward pass has ended) and only when every
+        # one of them is written IN PLACE into the flat gradient buffer -- a private buffer would be added to .grad by autograd the
+        # moment this function returns.
+        defer = ctx.defer_tail and _all_in_place(ctx.param_refs, grads)
+        entry = f"{kind}_backward_deferred" if defer else f"{kind}_backward"
+        nscratch = getattr(lib, f"cpc_{kind}_scratch_bytes")(n, t, dim_in, hidden, n_layers)
+        # (deferred: a buffer of its own -- the side stream outlives this call)
+        sc = scratch(nscratch, x.device, tag=_tail_tag(f"{kind}_tail", x.device)) if defer else scratch(nscratch, x.device)
+        check(getattr(lib, f"cpc_{entry}")(ptr(x), ptr_array(params), ptr(dout), ptr(saved), ptr(sc), ptr(dx), ptr_array(grads),
+                                           n, t, dim_in, hidden, n_layers, stream_ptr(x.device)), entry)
+        if defer:
+            # alive until the join.  NOT `grads`: autograd adopts a returned gradient as .grad only while nobody else holds it -- with a
+            # second reference it CLONES it on the spot (the flat buffer's not yet written bytes) and the clone becomes .grad
             _keep_for_tail(x.device, (x, saved, params, dout, sc))
-        else:
-            sc = scratch(nscratch, x.device)
-            check(lib.cpc_lstm_backward(ptr(x), ptr_array(params), ptr(dout), ptr(saved), ptr(sc), ptr(dx),
-                                        ptr_array(grads), n, t, dim_in, hidden, n_layers, stream_ptr(x.device)),
-                  "lstm_backward")
-        return (dx, None, None, None, None, None) + tuple(grads)
+        return (dx, None, None, None, None, None, None) + tuple(grads)
 
 
 class CPCAR(nn.Module):
@@ -350,16 +294,14 @@ class CPCAR(nn.Module):
         if self.reverse:
             x = torch.flip(x, [1])
         layers, keep = self.baseNet.num_layers, bool(self.keepHidden)
-        if isinstance(self.baseNet, nn.LSTM):
+        kind = "lstm" if isinstance(self.baseNet, nn.LSTM) else "rnn" if isinstance(self.baseNet, nn.RNN) else "gru"
+        if kind == "lstm":
             h0, c0 = self.hidden if self.hidden is not None else (None, None)
-            x, h, c = _LstmFn.apply(x, h0, c0, layers, keep, self._defer_tail and self._may_defer(), *self._param_list())
-            if self.keepHidden:
-                self.hidden = (h.detach(), c.detach())
         else:
-            kind = "rnn" if isinstance(self.baseNet, nn.RNN) else "gru"
-            x, h = _GruFn.apply(x, self.hidden, layers, keep, kind, self._defer_tail and self._may_defer(), *self._param_list())
-            if self.keepHidden:
-                self.hidden = h.detach()
+            h0, c0 = self.hidden, None
+        x, h, c = _RecurrentFn.apply(x, h0, c0, layers, keep, kind, self._defer_tail and self._may_defer(), *self._param_list())
+        if self.keepHidden:
+            self.hidden = (h.detach(), c.detach()) if kind == "lstm" else h.detach()
         # a sequence's order is preserved by each module (model.py:203-206)
         if self.reverse:
             x = torch.flip(x, [1])
@@ -395,8 +337,8 @@ class BiDIRARTangled(nn.Module):
 
     def forward(self, x):
         for layer in range(self.ARNet.num_layers):
-            xf = _GruFn.apply(x, None, 1, False, "gru", False, *_gru_layer_params(self.ARNet, layer))[0]
-            xb = _GruFn.apply(torch.flip(x, [1]), None, 1, False, "gru", False, *_gru_layer_params(self.ARNet, layer, "_reverse"))[0]
+            xf = _RecurrentFn.apply(x, None, None, 1, False, "gru", False, *_gru_layer_params(self.ARNet, layer))[0]
+            xb = _RecurrentFn.apply(torch.flip(x, [1]), None, None, 1, False, "gru", False, *_gru_layer_params(self.ARNet, layer, "_reverse"))[0]
             x = torch.cat([xf, torch.flip(xb, [1])], dim=2)
         return x
 
@@ -415,7 +357,7 @@ class BiDIRAR(nn.Module):
 
     def _run(self, gru, x):
         params = [p for layer in range(gru.num_layers) for p in _gru_layer_params(gru, layer)]
-        return _GruFn.apply(x, None, gru.num_layers, False, "gru", False, *params)[0]
+        return _RecurrentFn.apply(x, None, None, gru.num_layers, False, "gru", False, *params)[0]
 
     def forward(self, x):
         xf = self._run(self.netForward, x)
@@ -432,7 +374,7 @@ class LSTMPredictor(nn.LSTM):
             raise NotImplementedError("LSTMPredictor: batch_first, unidirectional, zero initial state only")
         params = [getattr(self, f"{n}_l{layer}") for layer in range(self.num_layers)
                   for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
-        return _LstmFn.apply(x, None, None, self.num_layers, False, False, *params)[0], None
+        return _RecurrentFn.apply(x, None, None, self.num_layers, False, "lstm", False, *params)[0], None
 
 
 class RNNPredictor(nn.RNN):
@@ -444,7 +386,7 @@ class RNNPredictor(nn.RNN):
             raise NotImplementedError("RNNPredictor: time-major, unidirectional tanh RNN with zero initial state only")
         params = [getattr(self, f"{n}_l{layer}") for layer in range(self.num_layers)
                   for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
-        out = _GruFn.apply(x.transpose(0, 1).contiguous(), None, self.num_layers, False, "rnn", False, *params)[0]
+        out = _RecurrentFn.apply(x.transpose(0, 1).contiguous(), None, None, self.num_layers, False, "rnn", False, *params)[0]
         return out.transpose(0, 1).contiguous(), None
 
 

@@ -107,7 +107,7 @@ class _TransformerFn(torch.autograd.Function):
         per = lib.cpc_transformer_param_count()
         l0 = [(p, g) for p, g in zip(ctx.param_refs[:per], grads[:per]) if p is not None]
         # the deferred form (cpc2_hip.h): inside the caller's scope (TransformerLayer.deferred_weight_gradients) and with every
-        # gradient of layer 0 written in place into the flat gradient buffer (model.py, _GruFn.backward)
+        # gradient of layer 0 written in place into the flat gradient buffer (model.py, _RecurrentFn.backward)
         if ctx.defer_tail and _all_in_place([p for p, _g in l0], [g for _p, g in l0]):
             # a buffer of its own, and one PER PENDING CALL: the side stream reads it after this call has returned, and a second
             # TransformerLayer of the same context network (nLevelsGRU >= 2) runs its backward before the join

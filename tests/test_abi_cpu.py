@@ -40,6 +40,32 @@ def test_shape_queries_and_error_reporting():
     assert lib.cpc_infonce_saved_bytes(8, 128, 17, 256, 256, 128) == 0
 
 
+@pytest.mark.parametrize("kind", ["gru", "lstm", "rnn"])
+def test_recurrent_size_queries(kind):
+    """cpc_{gru,lstm,rnn}_saved_bytes is the sum over layers of the cell's saved tensors (floats, each rounded up to 256 bytes; the
+    layer output `outl` for all but the last layer), and a shape the cell does not take gives 0 with a message that names the cell."""
+    lib = _lib.load()
+    saved_bytes, scratch_bytes = getattr(lib, f"cpc_{kind}_saved_bytes"), getattr(lib, f"cpc_{kind}_scratch_bytes")
+
+    def tensors(n, t, h):
+        return {"gru": [n * t * 3 * h, n * t * h, n * (t + 1) * h],                  # gates, hn, hall
+                "lstm": [n * t * 4 * h, n * (t + 1) * h, n * (t + 1) * h],           # gates, hall, call
+                "rnn": [n * (t + 1) * h]}[kind]                                      # hall
+
+    def up(floats):
+        return (4 * floats + 255) // 256 * 256
+
+    for n, t, dim_in, h, layers in [(1, 1, 4, 4, 8), (3, 17, 40, 36, 3), (4, 116, 256, 256, 1), (128, 128, 512, 512, 2)]:
+        want = layers * sum(up(f) for f in tensors(n, t, h)) + (layers - 1) * up(n * t * h)
+        assert saved_bytes(n, t, dim_in, h, layers) == want, (n, t, dim_in, h, layers)
+        assert scratch_bytes(n, t, dim_in, h, layers) > 0
+    assert saved_bytes(1, 1, 4, 4, 8) == {"gru": 7936, "lstm": 7936, "rnn": 3840}[kind]
+    for bad in [(3, 17, 40, 38, 1), (3, 17, 40, 36, 9), (0, 17, 40, 36, 1)]:          # hidden not a multiple of 4, 9 layers, no windows
+        for query in (saved_bytes, scratch_bytes):
+            assert query(*bad) == 0, bad
+            assert lib.cpc_last_error().startswith(kind.encode() + b":"), lib.cpc_last_error()
+
+
 @pytest.mark.parametrize("tag", ["tiny", "mid"])
 def test_sampler_bit_exact_vs_reference(golden, tag):
     g = golden("g1_negidx.npz")
