@@ -477,7 +477,7 @@ class _InfoNCEFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, c, z, ext_idx, weights, n_neg, defer, *wk):
-        require_gpu(c, z, ext_idx, *wk)
+        require_gpu(c, z, ext_idx, weights, *wk)
         lib = _lib.load()
         ctx.c_first_of = getattr(c, "_cpc_first_of", None) if (c.is_contiguous() and c.dtype == torch.float32) else None
         c = f32c(c)
@@ -499,6 +499,8 @@ class _InfoNCEFn(torch.autograd.Function):
         ctx.cw = tc != t
         if ext_idx.dtype != torch.int32 or ext_idx.numel() != b * n_neg * (t - k):
             raise ValueError("ext_idx must be int32 [b, W, n_neg]")
+        if weights is not None and weights.numel() != b * (t - k):
+            raise ValueError(f"weights must hold one value per (window, frame): {b * (t - k)}, got {weights.numel()}")
         w = f32c(weights) if weights is not None else None
         nsaved = lib.cpc_infonce_saved_bytes(b, t, k, dim_ar, dim_enc, n_neg)
         nscratch = lib.cpc_infonce_scratch_bytes(b, t, k, dim_ar, dim_enc, n_neg)
@@ -581,7 +583,7 @@ class _InfoNCEPredFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, ext_idx, weights, n_neg, *preds):
-        require_gpu(z, ext_idx, *preds)
+        require_gpu(z, ext_idx, weights, *preds)
         lib = _lib.load()
         z = f32c(z)
         preds = tuple(f32c(p) for p in preds)
@@ -591,6 +593,8 @@ class _InfoNCEPredFn(torch.autograd.Function):
             raise ValueError(f"predictions must be [b, W, dim_enc] = {(b, t - k, dim_enc)}")
         if ext_idx.dtype != torch.int32 or ext_idx.numel() != b * n_neg * (t - k):
             raise ValueError("ext_idx must be int32 [b, W, n_neg]")
+        if weights is not None and weights.numel() != b * (t - k):
+            raise ValueError(f"weights must hold one value per (window, frame): {b * (t - k)}, got {weights.numel()}")
         w = f32c(weights) if weights is not None else None
         nsaved = lib.cpc_infonce_saved_bytes(b, t, k, dim_enc, dim_enc, n_neg)
         nscratch = lib.cpc_infonce_scratch_bytes(b, t, k, dim_enc, dim_enc, n_neg)

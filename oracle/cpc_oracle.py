@@ -177,11 +177,13 @@ def relpos_bias(q, krelpos):
     return qp.reshape(b, s + 1, s)[:, 1:, :]
 
 
-def transformer_layer_forward(x, p, prefix, n_heads=8, size_seq=None, n_classifiers=1):
+def transformer_layer_forward(x, p, prefix, n_heads=8, size_seq=None, n_classifiers=1, pre_out=None):
     """One TransformerLayer (transformers.py:119-134) in eval mode (dropout off).
     x [N, S, D] with S == sizeSeq (the training window).
     n_classifiers > 1: MultiClassifierTransformerHead (transformers.py:137-158): lin2 emits n_classifiers
-    residual branches, output [N, S, n_classifiers, Dout]."""
+    residual branches, output [N, S, n_classifiers, Dout].
+    pre_out (test infrastructure): a list that receives the feed-forward net's pre-activations [N, S, dff] (detached) -- an
+    element within fp32 rounding of zero is a ReLU decision an fp32 evaluation may take the other way (see encoder_forward)."""
     n, s, d = x.shape
     dk = d // n_heads
     if size_seq is not None and size_seq != s:
@@ -190,7 +192,8 @@ def transformer_layer_forward(x, p, prefix, n_heads=8, size_seq=None, n_classifi
         pad = (-s) % size_seq
         xp = torch.cat([x, torch.zeros(n, pad, d, dtype=x.dtype)], dim=1) if pad else x
         blocks = xp.reshape(n * ((s + pad) // size_seq), size_seq, d)
-        out = transformer_layer_forward(blocks, p, prefix, n_heads=n_heads, size_seq=size_seq, n_classifiers=n_classifiers)
+        out = transformer_layer_forward(blocks, p, prefix, n_heads=n_heads, size_seq=size_seq, n_classifiers=n_classifiers,
+                                        pre_out=pre_out)
         return out.reshape((n, s + pad) + tuple(out.shape[2:]))[:, :s]
 
     def split(v):   # trans_ (transformers.py:89-91)
@@ -208,7 +211,10 @@ def transformer_layer_forward(x, p, prefix, n_heads=8, size_seq=None, n_classifi
     y = (att @ v).view(n, n_heads, s, dk).transpose(1, 2).reshape(n, s, d)
     y = y @ p[f"{prefix}multihead.Wo.weight"].t()
     y = layer_norm(x + y, p[f"{prefix}ln_multihead.weight"], p[f"{prefix}ln_multihead.bias"])
-    ff = torch.relu(y @ p[f"{prefix}ffnetwork.lin1.weight"].t() + p[f"{prefix}ffnetwork.lin1.bias"])
+    ff = y @ p[f"{prefix}ffnetwork.lin1.weight"].t() + p[f"{prefix}ffnetwork.lin1.bias"]
+    if pre_out is not None:
+        pre_out.append(ff.detach())
+    ff = torch.relu(ff)
     ff = ff @ p[f"{prefix}ffnetwork.lin2.weight"].t() + p[f"{prefix}ffnetwork.lin2.bias"]
     if n_classifiers > 1:            # transformers.py:153-158
         ff = ff.view(n, s, n_classifiers, d)
@@ -322,13 +328,22 @@ def criterion_forward_sparse(c, z, predictors, ext_idx, n_neg, mode=None, n_skip
     draw serves all K), dz collects the contributions of the negatives by index_add_.  Computes in the dtype of z (use float64).
 
     dlosses [K - n_skipped]: gradient of the returned losses (default ones = `losses.sum().backward()`, train.py:108).
-    Returns dict(losses [1, K-s], acc [1, K-s], dc like c, dz like z, dW list of K [Henc, Har])."""
-    if mode == "reverse":            # criterion.py:292-294
-        z, c = torch.flip(z, [1]), torch.flip(c, [1])
-    c, z = c.detach(), z.detach()
+    Returns dict(losses [1, K-s], acc [1, K-s], dc like c, dz like z, dW list of K [Henc, Har]).
+
+    predictors may instead be K precomputed prediction tensors [b, W, Henc] (the outputs of predictor modules on c[:, :W], after
+    the flip in reverse mode: what criterion.py:161-169 hands to the scores); c is then not looked at (pass None) and the
+    result holds dP, the list of the K gradients [b, W, Henc], in place of dc and dW."""
     b, t_len, h_enc = z.shape
     k_steps = len(predictors)
     w_len = t_len - k_steps
+    given = predictors[0].dim() == 3
+    if given and any(tuple(p.shape) != (b, w_len, h_enc) for p in predictors):
+        raise ValueError(f"predictions must be [b, W, Henc] = {(b, w_len, h_enc)}")
+    if mode == "reverse":            # criterion.py:292-294
+        z = torch.flip(z, [1])
+        c = c if given else torch.flip(c, [1])
+    z = z.detach()
+    c = torch.zeros(b, w_len, 1, dtype=z.dtype) if given else c.detach()
     dt = z.dtype
     idx = torch.as_tensor(np.asarray(ext_idx), dtype=torch.long).view(b, n_neg, w_len)   # criterion.py:263-265
     wts = (torch.ones(b * w_len, dtype=dt) if weights is None else weights.to(dt)).view(b, w_len)
@@ -341,7 +356,7 @@ def criterion_forward_sparse(c, z, predictors, ext_idx, n_neg, mode=None, n_skip
     dc = torch.zeros_like(c)
     dz = torch.zeros_like(z)
     dzflat = dz.view(-1, h_enc)
-    dws = [torch.zeros_like(p) for p in preds_w]
+    dws = [torch.zeros_like(p) for p in preds_w]      # (predictions given: these ARE dP, filled window chunk by window chunk)
     scale = 1.0 / (b * w_len)        # torch.mean over the b * W rows (criterion.py:349)
     rows = torch.arange(b).view(b, 1) * t_len + torch.arange(w_len).view(1, w_len)       # flat z row of frame t of window b
     for lo in range(0, b, windows_per_chunk):
@@ -351,7 +366,7 @@ def criterion_forward_sparse(c, z, predictors, ext_idx, n_neg, mode=None, n_skip
         cw = c[lo:hi, :w_len]
         for k in range(1, k_steps + 1):
             wk = preds_w[k - 1]
-            pred = cw @ wk.t()                                                           # [cb, W, Henc]
+            pred = wk[lo:hi] if given else cw @ wk.t()                                   # [cb, W, Henc]
             pos = z[lo:hi, k:k + w_len]
             s_pos = (pred * pos).sum(-1) / h_enc                                         # mean over features, criterion.py:171
             s_neg = torch.einsum("bwh,bnwh->bwn", pred, neg) / h_enc
@@ -370,12 +385,20 @@ def criterion_forward_sparse(c, z, predictors, ext_idx, n_neg, mode=None, n_skip
             d_pred = d_pos.unsqueeze(-1) * pos + torch.einsum("bwn,bnwh->bwh", d_neg, neg)
             dz[lo:hi, k:k + w_len] += d_pos.unsqueeze(-1) * pred
             g_neg += d_neg.permute(0, 2, 1).unsqueeze(-1) * pred.unsqueeze(1)
+            if given:
+                dws[k - 1][lo:hi] = d_pred
+                continue
             dc[lo:hi, :w_len] += d_pred @ wk
             dws[k - 1] += d_pred.reshape(-1, h_enc).t() @ cw.reshape(-1, cw.shape[-1])
         dzflat.index_add_(0, idx[lo:hi].reshape(-1), g_neg.view(-1, h_enc))
+    out = {"losses": loss[n_skipped:].view(1, -1), "acc": (hits[n_skipped:] * scale).view(1, -1)}
+    if given:
+        out.update(dz=torch.flip(dz, [1]) if mode == "reverse" else dz, dP=dws)
+        return out
     if mode == "reverse":
         dc, dz = torch.flip(dc, [1]), torch.flip(dz, [1])
-    return {"losses": loss[n_skipped:].view(1, -1), "acc": (hits[n_skipped:] * scale).view(1, -1), "dc": dc, "dz": dz, "dW": dws}
+    out.update(dc=dc, dz=dz, dW=dws)
+    return out
 
 
 def candidates(z, ext_idx, n_neg, k_steps):
@@ -437,17 +460,19 @@ def predictor_list(p, k_steps, prefix="wPrediction.predictors."):
     return [p[f"{prefix}{k}.weight"] for k in range(k_steps)]
 
 
-def train_step_loss(past, future, model_p, crit_p, mt, k_steps, n_neg, n_layers_gru=1, ar="GRU"):
+def train_step_loss(past, future, model_p, crit_p, mt, k_steps, n_neg, n_layers_gru=1, ar="GRU", predictors=None):
     """Forward of one training step exactly as train.py:95-108 wires it: the model runs on
     cat([past, future]) (2b windows); context comes from the PAST half, targets from the
     FUTURE half.  mt is an MT19937 whose stream supplies the negatives.
+    predictors: the K predictors as criterion_forward takes them (callables for predictor modules); default: the linear
+    predictors of crit_p.
     Returns (total_loss, losses [1,K], acc [1,K])."""
     b = past.shape[0]
     c, z = model_forward(torch.cat([past, future], dim=0), model_p, n_layers_gru, ar)
     c, z = c[:b], z[b:]
     t_len = z.shape[1]
     _, _, ext = negative_indices(mt, b, t_len, t_len - k_steps, n_neg)
-    losses, acc = criterion_forward(c, z, predictor_list(crit_p, k_steps), ext, n_neg)
+    losses, acc = criterion_forward(c, z, predictor_list(crit_p, k_steps) if predictors is None else predictors, ext, n_neg)
     return losses.sum(), losses, acc
 
 
