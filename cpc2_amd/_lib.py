@@ -128,6 +128,11 @@ SIGNATURES = {
     "cpc_probe_ctc_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
     "cpc_probe_ctc": (c_int, [c_ptr, c_int, c_int, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size_t, c_ptr]),
     "cpc_probe_collapse": (c_int, [c_ptr, c_int, c_int, c_ptr, c_long, c_ptr, c_ptr]),
+    "cpc_augment_additive": (c_int, [c_ptr, c_long, c_ptr, c_ptr, c_long, c_ptr, c_int, c_ptr, c_ptr, c_int, c_int, c_ptr]),
+    "cpc_augment_peak_norm": (c_int, [c_ptr, c_long, c_ptr, c_ptr, c_int, c_int, c_ptr]),
+    "cpc_augment_fir_scratch_bytes": (c_size_t, [c_int, c_int]),
+    "cpc_augment_fir": (c_int, [c_ptr, c_ptr, c_long, c_ptr, c_ptr, c_ptr, c_ptr, c_size_t, c_int, c_int, c_ptr]),
+    "cpc_augment_time_dropout": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_int, c_ptr]),
 }
 
 _lib = None

@@ -1,8 +1,8 @@
 """The architecture / optimisation / augmentation flags shared by every command line of the package.
 
 Same flags, types, choices and defaults as the reference's cpc/cpc_default_config.py:13-162 -- all of them, the
-augmentation group included: cpc2_amd.train parses those and then refuses them with a message (train.py, _refuse), and
-checkpoint_args.json carries the same keys as a reference run, so that either side can resume the other's run."""
+augmentation group included: cpc2_amd.train builds additive / natural_reverb / time_dropout (data_augmentation.py) and
+refuses the sox-based types with a message (train.py, refuseUnsupported), and checkpoint_args.json carries the same keys as a reference run, so that either side can resume the other's run."""
 import argparse
 
 NAMING_CONVENTIONS = ['full_seedlings', 'no_speaker', 'id_spkr_onset_offset', 'spkr-id', 'spkr-id-nb',
@@ -73,7 +73,9 @@ def set_default_cpc_config(parser):
     g.add_argument('--n_skipped', type=int, default=0, help='Time steps skipped before the first prediction.')
     g.add_argument('--no_speaker', action='store_true', help='Collapse every speaker into one.')
     a = parser.add_argument_group('Data augmentation configuration',
-                                  description="Parsed for checkpoint compatibility; augmentation itself is not built here.")
+                                  description="Device-side augmentation of the past / future half (cpc2_amd/data_augmentation.py): "
+                                  "additive, natural_reverb, time_dropout and none are built, alone or combined; the sox-based "
+                                  "types are parsed for checkpoint compatibility and refused by name.")
     a.add_argument('--noise_extension', type=str, default='.wav')
     a.add_argument('--augment_future', action='store_true')
     a.add_argument('--augment_past', action='store_true')

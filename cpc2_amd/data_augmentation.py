@@ -1,0 +1,468 @@
+"""Audio augmentation on device batches: the reference's cpc/data_augmentation.py for the types whose arithmetic is fixed.
+
+Built: `additive` (AdditiveNoiseAugment :157-228), `natural_reverb` (NaturalReverb :278-318), `time_dropout`
+(TimeDropoutAugment :268-275), their combinations (CombinedTransforms :331-344) and the reverberated noise
+(`augmentation_factory(..., applied_on_noise=True)`).  The sox types (UNBUILT_TYPES) are refused by name: neither sox nor
+WavAugment is available, and their filters cannot be pinned to anything.
+
+The reference augments one window at a time on the CPU, inside DataLoader workers.  Here a pack of audio lives in HBM as one
+flat vector and so do the noise pack and the impulse responses; a batch's augmentation is a few kernels
+(csrc/augment.hip) that read the windows by offset, and the host only draws numbers -- once per pack:
+
+  * a transform draws ONE window's numbers with `draw_one(window)` (an "entry"), in the order the reference's `__call__` draws
+    them and from the same generators -- numpy's global generator for the SNR, the dropout's two integers and the
+    impulse_response_prob test; Python's `random` for the impulse-response choice; the noise loader's samplers draw from
+    `random` and torch's generator;
+  * `seal(entries, device)` turns a list of entries into a PLAN: a dict of host numpy arrays (what the tests replay through the
+    fp64 statement of the transforms) plus, under "_dev", the same arrays on the device (one pinned, non-blocking copy each);
+  * `apply(plan, lo, hi, src, dst=None, window=None)` augments the windows `src` with rows [lo, hi) of the plan; a step of the training loop
+    uploads nothing and waits for nothing.  `src` is a [b, 1, W] / [b, W] device buffer or FlatWindows(vector, offsets).
+
+`transform(x)` on a [b, 1, W] device batch or on the reference's single [1, W] window draws, seals and applies in one go; the
+plan it used stays in `transform.last_plan`.
+
+Deviations from the reference, all deliberate:
+  * impulse responses are never resampled: a file whose rate is not `sr` is refused with an error that names it;
+  * sequence-wise NaturalReverb: the probability test is drawn from numpy and the file from `random` (the reference's library
+    draws both from torch); a file is drawn only for a window the test lets through;
+  * TimeDropoutAugment follows the definition in its docstring (the library the reference calls is not available);
+  * `--augment_type none` gives None (the reference's factory raises on the one-element list ['none']).
+"""
+import collections
+import os
+import random
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check, ptr, stream_ptr
+
+BUILT_TYPES = ('additive', 'natural_reverb', 'time_dropout')
+UNBUILT_TYPES = ('bandreject', 'pitch', 'pitch_quick', 'pitch_dropout', 'pitch_deropout', 'artificial_reverb',
+                 'artificial_reverb_dropout', 'random_noise')
+
+energy_normalization = lambda wav: wav / (torch.sqrt(torch.mean(wav ** 2)) + 1e-8)                  # noqa: E731
+peak_normalization = lambda wav: wav / (wav.abs().max(dim=1, keepdim=True)[0] + 1e-8)              # noqa: E731
+
+FlatWindows = collections.namedtuple("FlatWindows", "data offsets")     # windows data[offsets[i] : offsets[i] + W] (device tensors)
+
+
+def unbuilt_message(augment_type):
+    """The refusal of a request that names a type without a kernel path (train.refuseUnsupported, augmentation_factory)."""
+    asked = [augment_type] if isinstance(augment_type, str) else list(augment_type)
+    missing = [t for t in asked if t not in BUILT_TYPES and t != 'none']
+    return (f"--augment_past / --augment_future with --augment_type {' '.join(asked)}: {', '.join(missing)} "
+            f"{'is' if len(missing) == 1 else 'are'} not built (sox / WavAugment effects); the augmentation types on the MI355X "
+            f"feeder path are {', '.join(BUILT_TYPES)} and none, alone or combined")
+
+
+# --------------------------------------------------------------------------- device helpers
+def _upload(array, device):
+    """A host array on the device through one pinned, asynchronous copy (nothing waits for it)."""
+    t = torch.from_numpy(np.ascontiguousarray(array))
+    if device.type != "cuda":
+        return t
+    return t.pin_memory().to(device, non_blocking=True)
+
+
+def _rows(t):
+    return t.reshape(-1, t.shape[-1])
+
+
+def _operand(src):
+    """(pointer, total, offsets pointer) of a kernel operand: FlatWindows or a contiguous buffer."""
+    if isinstance(src, FlatWindows):
+        return ptr(src.data), src.data.numel(), ptr(src.offsets)
+    return ptr(src), 0, ptr(None)
+
+
+def _count(src):
+    return src.offsets.numel() if isinstance(src, FlatWindows) else _rows(src).size(0)
+
+
+def _device_of(src):
+    return src.data.device if isinstance(src, FlatWindows) else src.device
+
+
+def _buffer(src, window, dst=None):
+    """`src` as a [b, W] buffer: itself, or its windows gathered into dst (a new buffer when None)."""
+    if not isinstance(src, FlatWindows):
+        return src
+    b = src.offsets.numel()
+    out = dst if dst is not None else torch.empty(b, window, dtype=torch.float32, device=src.data.device)
+    check(_lib.load().cpc_window_gather(ptr(src.data), src.data.numel(), ptr(src.offsets), ptr(out), b, window,
+                                        stream_ptr(src.data.device)), "window_gather")
+    return out
+
+
+def _window(src, dst, window=None):
+    """Samples per window: of the buffer operand, of dst, or as told (windows given by offsets carry no length)."""
+    if not isinstance(src, FlatWindows):
+        return src.shape[-1]
+    if dst is not None:
+        return dst.shape[-1]
+    if window is None:
+        raise ValueError("windows given by offsets need dst or window")
+    return window
+
+
+def _check_src(src):
+    if isinstance(src, FlatWindows):
+        _lib.require_gpu(src.data, src.offsets)
+        if src.data.dtype != torch.float32 or src.offsets.dtype != torch.int64 or not src.offsets.is_contiguous():
+            raise TypeError("FlatWindows needs a float32 vector and contiguous int64 offsets")
+    else:
+        _lib.require_gpu(src)
+        if src.dtype != torch.float32 or not src.is_contiguous():
+            raise TypeError("augmentation kernels take contiguous float32 batches")
+
+
+def peak_norm_windows(src, window, dst=None):
+    """PeakNorm (cpc/dataset.py:433-438) of every window of `src`, on the device: w / (max|w| + 1e-8)."""
+    _check_src(src)
+    b, dev = _count(src), _device_of(src)
+    out = dst if dst is not None else torch.empty(b, window, dtype=torch.float32, device=dev)
+    p, total, off = _operand(src)
+    check(_lib.load().cpc_augment_peak_norm(p, total, off, ptr(out), b, window, stream_ptr(dev)), "augment_peak_norm")
+    return out
+
+
+class _Transform:
+    """What the built transforms share: draw / seal / apply (module docstring) and the reference's `__call__`."""
+    inplace = False
+
+    def plan(self, n, window, device):
+        return self.seal([self.draw_one(window) for _ in range(n)], torch.device(device))
+
+    def __call__(self, x):
+        _lib.require_gpu(x)
+        window = x.shape[-1]
+        rows = _rows(x.contiguous())
+        plan = self.plan(rows.size(0), window, x.device)
+        self.last_plan = plan
+        src = rows.clone() if self.inplace else rows
+        return _rows(self.apply(plan, 0, rows.size(0), src)).view(x.shape)
+
+
+# --------------------------------------------------------------------------- additive noise
+class AdditiveNoiseAugment(_Transform):
+    """data_augmentation.py:157-228.  Per window: the next window of the noise data set (after its PeakNorm transform and, with
+    meta-augmentation, its own augmentation), snr = (snr_max - snr_min) u + snr_min with u one np.random.random_sample(),
+    g = 10 ** (-snr / 20), and peak_normalization(energy_normalization(x) + energy_normalization(noise) * g).
+
+    Noise windows are taken as the reference takes them (:176-211): a loader of batchSize windows over all packs of the noise
+    data set -- `uniform`, or `temporalsamespeaker` with remove_artefacts -- with a random offset, consumed one window per
+    call and started again when it runs out.  The first noise batch is fetched when the transform is built, as there.  When a
+    noise batch is fetched and the noise data set carries an augmentation (`--meta_aug`), that augmentation's numbers for the
+    batch's windows are drawn right then.
+
+    Entry: (noise vector, noise offset, meta entry or None, snr).  Plan: snr [n] f64, gain [n] f32, noise_off [n] i64,
+    noise_src [n] (index into noise_data, the device vectors the offsets refer to), meta (the noise augmentation's plan)."""
+
+    def __init__(self, noise_dataset, snr_min, snr_max, batchSize, sampling='uniform'):
+        assert noise_dataset and snr_min <= snr_max
+        self.noise_dataset = noise_dataset
+        self.sampling = sampling
+        self.batchSize = batchSize
+        self.snr_min = snr_min
+        self.snr_max = snr_max
+        self.meta = noise_dataset.augmentation if getattr(noise_dataset, "augment_past", False) else None
+        self.peak_norm = getattr(noise_dataset, "transform", None) is not None
+        self.current_noise_batch = collections.deque()
+        self.update_noise_loader()
+        self.get_next_batch()
+
+    def update_noise_loader(self):
+        loader = self.noise_dataset.getDataLoader(self.batchSize, type=self.sampling, randomOffset=True, numWorkers=0,
+                                                  onLoop=-1, nLoops=-1, remove_artefacts=self.sampling != "uniform")
+        self.noise_data_loader = loader.offsets()
+
+    def get_next_batch(self):
+        try:
+            data, batch = next(self.noise_data_loader)
+        except StopIteration:
+            self.update_noise_loader()
+            try:
+                data, batch = next(self.noise_data_loader)
+            except StopIteration:
+                raise RuntimeError("the noise data set yields no window (is it shorter than a batch of windows?)")
+        window = self.noise_dataset.sizeWindow
+        self.current_noise_batch = collections.deque(
+            (data, int(o), self.meta.draw_one(window) if self.meta is not None else None) for o in batch)
+
+    def get_noise_sequence(self):
+        if not self.current_noise_batch:
+            self.get_next_batch()
+        return self.current_noise_batch.popleft()
+
+    def draw_one(self, window):
+        data, offset, meta = self.get_noise_sequence()
+        snr = (self.snr_max - self.snr_min) * np.random.random_sample() + self.snr_min
+        return data, offset, meta, snr
+
+    def seal(self, entries, device):
+        tensors, index = [], {}
+        src = np.empty(len(entries), dtype=np.int64)
+        for i, (data, _o, _m, _s) in enumerate(entries):
+            key = id(data)
+            if key not in index:
+                index[key] = len(tensors)
+                tensors.append(data)
+            src[i] = index[key]
+        snr = np.array([e[3] for e in entries], dtype=np.float64)
+        gain = (1.0 / (10.0 ** (snr / 20.0))).astype(np.float32)               # :219-220, a = snr / 20, 1 / 10 ** a
+        plan = {"kind": "additive", "n": len(entries), "snr": snr, "gain": gain,
+                "noise_off": np.array([e[1] for e in entries], dtype=np.int64), "noise_src": src, "noise_data": tensors,
+                "noise_peak_norm": self.peak_norm,
+                "meta": self.meta.seal([e[2] for e in entries], device) if self.meta is not None else None}
+        plan["_dev"] = {"gain": _upload(gain, device), "noise_off": _upload(plan["noise_off"], device)}
+        return plan
+
+    @staticmethod
+    def _runs(plan, lo, hi):
+        """[lo, hi) cut where the noise vector changes (a noise data set of several packs); almost always one run."""
+        if len(plan["noise_data"]) == 1:
+            return [(lo, hi, plan["noise_data"][0])]
+        src = plan["noise_src"][lo:hi]
+        cuts = [0] + (np.flatnonzero(np.diff(src)) + 1).tolist() + [hi - lo]
+        return [(lo + a, lo + b, plan["noise_data"][int(src[a])]) for a, b in zip(cuts[:-1], cuts[1:])]
+
+    def apply(self, plan, lo, hi, src, dst=None, window=None):
+        _check_src(src)
+        lib, dev = _lib.load(), _device_of(src)
+        b = hi - lo
+        window = _window(src, dst, window if window is not None else self.noise_dataset.sizeWindow)
+        out = dst if dst is not None else torch.empty(b, window, dtype=torch.float32, device=dev)
+        d = plan["_dev"]
+        for a, e, noise in self._runs(plan, lo, hi):
+            noise_src = FlatWindows(noise, d["noise_off"][a:e])
+            peak = 1 if plan["noise_peak_norm"] else 0
+            if plan["meta"] is not None:
+                # the noise window as the noise data set yields it: PeakNorm, then its own augmentation
+                clean = peak_norm_windows(noise_src, window) if peak else _buffer(noise_src, window)
+                noise_src, peak = self.meta.apply(plan["meta"], a, e, clean), 0
+            if isinstance(src, FlatWindows):
+                part = FlatWindows(src.data, src.offsets[a - lo:e - lo])
+            else:
+                part = _rows(src)[a - lo:e - lo]
+            sp, st, so = _operand(part)
+            np_, nt, no = _operand(noise_src)
+            check(lib.cpc_augment_additive(sp, st, so, np_, nt, no, peak, ptr(d["gain"][a:e]), ptr(_rows(out)[a - lo:e - lo]),
+                                           e - a, window, stream_ptr(dev)), "augment_additive")
+        return out
+
+
+# --------------------------------------------------------------------------- natural reverberation
+class NaturalReverb(_Transform):
+    """data_augmentation.py:278-318: y[t] = sum_{k <= t} ir[k] x[t - k] for t < W (the convolution cut to the input length, no
+    delay compensation), then peak_normalization.  With probability 1 - p the convolution is skipped; the normalisation is
+    applied either way.  Sequence-wise (default): every window draws its own impulse response; batch_wise: one response serves
+    batchSize consecutive windows, then a new one is drawn (:312-317; the first one when the transform is built).
+
+    The responses are the .wav files under ir_paths (findAllSeqs, no cache), mixed to mono and loaded once to the device as one
+    flat vector with an offsets table.  A file whose rate is not `sr` is refused: there is no resampler here.
+
+    Entry: index of the response, or -1 for a skipped convolution.  Plan: ir_index [n] i64, ir_off [n] i64, ir_len [n] i32."""
+
+    def __init__(self, ir_paths, p, batchSize, sr=32000, batch_wise=False, device=None):
+        from . import audio
+        from .dataset import findAllSeqs
+        self.p = p
+        self.sr = sr
+        self.batch_wise = batch_wise
+        self.count = 0
+        self.batchSize = batchSize
+        if ir_paths is None:
+            raise ValueError("natural_reverb needs --pathImpulseResponses")
+        files, _ = findAllSeqs(ir_paths, extension=".wav")
+        self.ir_files = [os.path.join(ir_paths, data[1]) for data in files]
+        print("Found %d files for natural reverberation" % len(self.ir_files))
+        if not self.ir_files:
+            raise ValueError(f"no .wav impulse response under {ir_paths}")
+        responses = []
+        for path in self.ir_files:
+            wav, rate = audio.load(path)
+            if rate != sr:
+                raise ValueError(f"impulse response {path} is sampled at {rate} Hz, not at --ir_sample_rate {sr}: responses "
+                                 "are not resampled here, convert the file")
+            responses.append(wav.float().mean(dim=0))
+        self.ir_len = np.array([r.numel() for r in responses], dtype=np.int64)
+        self.ir_off = np.concatenate([[0], np.cumsum(self.ir_len)[:-1]]).astype(np.int64)
+        self.device = torch.device(device) if device is not None else \
+            torch.device("cuda" if torch.cuda.is_available() else "cpu")
+        self.ir_data = torch.cat(responses).to(self.device)
+        if batch_wise:
+            self.get_new_impulse_response()
+
+    def get_new_impulse_response(self):
+        self.current = random.choice(range(len(self.ir_files)))
+
+    def draw_one(self, window):
+        applied = np.random.random_sample() < self.p
+        if self.batch_wise:
+            index = self.current if applied else -1
+            self.count += 1
+            if self.count == self.batchSize:
+                self.get_new_impulse_response()
+                self.count = 0
+            return index
+        return random.choice(range(len(self.ir_files))) if applied else -1
+
+    def seal(self, entries, device):
+        index = np.array(entries, dtype=np.int64).reshape(-1)
+        safe = np.maximum(index, 0)
+        plan = {"kind": "natural_reverb", "n": len(index), "ir_index": index,
+                "ir_off": np.where(index >= 0, self.ir_off[safe], 0).astype(np.int64),
+                "ir_len": np.where(index >= 0, self.ir_len[safe], 0).astype(np.int32)}
+        plan["_dev"] = {"ir_off": _upload(plan["ir_off"], device), "ir_len": _upload(plan["ir_len"], device)}
+        return plan
+
+    def apply(self, plan, lo, hi, src, dst=None, window=None):
+        _check_src(src)
+        lib, dev = _lib.load(), _device_of(src)
+        b = hi - lo
+        window = _window(src, dst, window)
+        src = _buffer(src, window)
+        out = dst if dst is not None else torch.empty(b, window, dtype=torch.float32, device=dev)
+        need = lib.cpc_augment_fir_scratch_bytes(b, window)
+        scratch = _lib.scratch(need, dev, tag="augment_fir")
+        d = plan["_dev"]
+        check(lib.cpc_augment_fir(ptr(src), ptr(self.ir_data), self.ir_data.numel(), ptr(d["ir_off"][lo:hi]),
+                                  ptr(d["ir_len"][lo:hi]), ptr(out), ptr(scratch), scratch.numel(), b, window, stream_ptr(dev)),
+              "augment_fir")
+        return out
+
+
+# --------------------------------------------------------------------------- time dropout
+class TimeDropoutAugment(_Transform):
+    """data_augmentation.py:268-275, by this definition: max_frames = int(sr * T_ms / 1000); per window
+    length = np.random.randint(0, max_frames), then start = np.random.randint(0, max(1, W - length)); samples
+    [start, start + length) become zero and every other sample is untouched, bit for bit.  T_ms below one sample's worth
+    (max_frames == 0) is refused here.  In place.
+
+    Entry: (start, length).  Plan: start [n] i64, length [n] i64."""
+    inplace = True
+
+    def __init__(self, T_ms=100, sr=16000.0):
+        self.sr = sr
+        self.max_frames = int(sr * T_ms / 1000)
+        if self.max_frames <= 0:
+            raise ValueError(f"--t_ms {T_ms}: a dropout of at most {self.max_frames} samples; give at least 1 ms")
+
+    def draw_one(self, window):
+        length = int(np.random.randint(0, self.max_frames))
+        start = int(np.random.randint(0, max(1, window - length)))
+        return start, length
+
+    def seal(self, entries, device):
+        arr = np.array(entries, dtype=np.int64).reshape(-1, 2)
+        plan = {"kind": "time_dropout", "n": len(arr), "start": arr[:, 0].copy(), "length": arr[:, 1].copy()}
+        plan["_dev"] = {"start": _upload(plan["start"], device), "length": _upload(plan["length"], device)}
+        return plan
+
+    def apply(self, plan, lo, hi, src, dst=None, window=None):
+        _check_src(src)
+        dev = _device_of(src)
+        src = _buffer(src, _window(src, dst, window), dst)
+        d = plan["_dev"]
+        check(_lib.load().cpc_augment_time_dropout(ptr(src), ptr(d["start"][lo:hi]), ptr(d["length"][lo:hi]), hi - lo,
+                                                   src.shape[-1], stream_ptr(dev)), "augment_time_dropout")
+        return src
+
+
+# --------------------------------------------------------------------------- combinations
+class CombinedTransforms(_Transform):
+    """data_augmentation.py:331-344: the transforms of `augment_cfgs`, applied in the order given ('none' entries skipped).
+    Entry: the tuple of the parts' entries (drawn in that order, window by window).  Plan: {"parts": [plan, ...]}."""
+
+    def __init__(self, augment_cfgs, **kwargs):
+        self.transfors_cfgs = [get_augment(x, **kwargs) for x in augment_cfgs]
+        self._parts = [t for t in self.transfors_cfgs if t is not None]
+        self._draws = [t.draw_one for t in self._parts]
+
+    def draw_one(self, window):
+        return tuple([draw(window) for draw in self._draws])
+
+    def seal(self, entries, device):
+        parts = self._parts
+        return {"kind": "combined", "n": len(entries),
+                "parts": [t.seal([e[i] for e in entries], device) for i, t in enumerate(parts)]}
+
+    def apply(self, plan, lo, hi, src, dst=None, window=None):
+        parts = self._parts
+        out_of_place = [i for i, t in enumerate(parts) if not t.inplace]
+        last = out_of_place[-1] if out_of_place else -1
+        window = _window(src, dst, window)
+        cur = src
+        for i, (t, p) in enumerate(zip(parts, plan["parts"])):
+            target = dst if i >= last else None            # from the last out-of-place stage on, everything happens in dst
+            cur = t.apply(p, lo, hi, cur, target, window=window)
+        if dst is not None and cur is not dst:             # (no stage at all, or in-place stages on a caller's buffer)
+            cur = _buffer(cur, window, dst) if isinstance(cur, FlatWindows) else dst.copy_(cur.view_as(dst))
+        return cur
+
+    def __call__(self, x):
+        _lib.require_gpu(x)
+        rows = _rows(x.contiguous())
+        plan = self.plan(rows.size(0), x.shape[-1], x.device)
+        self.last_plan = plan
+        return _rows(self.apply(plan, 0, rows.size(0), rows.clone())).view(x.shape)
+
+
+def get_augment(augment_type, **kwargs):
+    """data_augmentation.py:347-378."""
+    if not augment_type or augment_type == 'none':
+        return None
+    if augment_type == 'additive':
+        if not kwargs['noise_dataset']:
+            raise RuntimeError('Noise dataset is needed for the additive noise')
+        return AdditiveNoiseAugment(kwargs['noise_dataset'], kwargs['additive_noise_snr_min'],
+                                    kwargs['additive_noise_snr_max'], kwargs['batchSize'], kwargs['additive_noise_sampling'])
+    if augment_type == 'time_dropout':
+        return TimeDropoutAugment(kwargs['t_ms'])
+    if augment_type == 'natural_reverb':
+        return NaturalReverb(ir_paths=kwargs['pathImpulseResponses'], p=kwargs['impulse_response_prob'],
+                             batchSize=kwargs['batchSize'], sr=kwargs['ir_sample_rate'], batch_wise=kwargs['ir_batch_wise'])
+    if augment_type in UNBUILT_TYPES:
+        raise NotImplementedError(unbuilt_message(augment_type))
+    raise RuntimeError(f'Unknown augment_type = {augment_type}')
+
+
+def augmentation_factory(args, noise_dataset=None, applied_on_noise=False):
+    """data_augmentation.py:381-442: None when no half is augmented or the type is none; one type gives its class, several give
+    CombinedTransforms; `applied_on_noise` reads --meta_aug_type / --meta_ir_batch_wise instead (the reverberated noise).  A
+    request that names an unbuilt type raises NotImplementedError before anything is built."""
+    if applied_on_noise:
+        augment_type = args.meta_aug_type
+        ir_batch_wise = args.meta_ir_batch_wise
+        if augment_type is not None:
+            print("Activating meta data augmentation with : %s" % augment_type)
+    else:
+        augment_type = args.augment_type
+        ir_batch_wise = args.ir_batch_wise
+        print("Activating data augmentation with : %s" % augment_type)
+
+    if not augment_type or augment_type == 'none' or list(augment_type) == ['none'] or \
+            not (args.augment_past or args.augment_future):
+        return None
+    if isinstance(augment_type, str):
+        augment_type = [augment_type]
+    if any(t in UNBUILT_TYPES for t in augment_type):
+        raise NotImplementedError(unbuilt_message(augment_type))
+
+    batchSize = args.nGPU * args.batchSizeGPU
+    additive_noise_sampling = "temporalsamespeaker" if args.temporal_additive_noise else "uniform"
+    aug_args = {"t_ms": args.t_ms,
+                "noise_dataset": noise_dataset,
+                "additive_noise_snr_min": args.min_snr_in_db,
+                "additive_noise_snr_max": args.max_snr_in_db,
+                "additive_noise_sampling": additive_noise_sampling,
+                "impulse_response_prob": args.impulse_response_prob,
+                "pathImpulseResponses": args.pathImpulseResponses,
+                "ir_sample_rate": args.ir_sample_rate,
+                "batchSize": batchSize,
+                "ir_batch_wise": ir_batch_wise}
+    if len(augment_type) > 1:
+        return CombinedTransforms(augment_type, **aug_args)
+    return get_augment(augment_type[0], **aug_args)

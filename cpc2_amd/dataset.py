@@ -12,7 +12,15 @@ by the library's own FLAC / WAV readers (cpc2_amd/audio.py).
 Signal-quality side files (per-file snr / c50 estimates, dataset.py:69-77,106-120,257-281) are read too and come out as
 the third element of a batch.  Frame-level phone labels (parseSeqLabels, dataset.py:97-100,242-245,267-269) replace the
 speaker label when given: a pack's labels go to the device once and a batch's [b, sizeWindow // step] labels are gathered there
-from the window offsets.  Not on this path: data augmentation (sox / WavAugment).
+from the window offsets.
+
+Augmentation (dataset.py:305-321; cpc2_amd/data_augmentation.py): `augmentation` is applied to the past half (`augment_past`),
+to the future half with draws of its own (`augment_future`), or once for both (`past_equal_future`).  The loader draws the
+numbers of a whole pack's windows on the host before the pack's first step -- window by window, past before future, the "plan"
+of the pack (`_AudioLoader.plans`) -- and uploads them with the window offsets; a batch is then built on the device as a
+[2, b, 1, W] buffer whose clean half is the gather and whose augmented half is written by the augmentation kernels, and is
+yielded as the transposed [b, 2, 1, W] view: sequence[:, 0] and sequence[:, 1] are both contiguous.  `transform` (PeakNorm, the
+noise data set's) is applied on the device too.  Labels, phone labels and signal quality are those of the clean windows.
 Without augmentation the reference yields past == future (dataset.py:308-321): batches are returned as an
 expanded [b, 2, 1, W] view whose two halves alias, which cpcStep(dedup=True) can exploit.
 """
@@ -256,6 +264,15 @@ def remove_artefacts(batches, seqLabel, sizeWindow, carry_shift=False):
     return out
 
 
+class PeakNorm(object):
+    """dataset.py:433-438: x / (max|x| + 1e-8) of a [C, L] window.  As an AudioBatchData `transform` it runs on the device
+    (cpc_augment_peak_norm, or inside the additive-noise kernel for the noise data set)."""
+
+    def __call__(self, x):
+        max_val = x.abs().max(dim=1, keepdim=True)[0]
+        return x / (max_val + 1e-8)
+
+
 class AudioBatchData:
     """dataset.py:23-408 (see the module docstring for what is and is not carried over)."""
 
@@ -263,8 +280,18 @@ class AudioBatchData:
                  MAX_SIZE_LOADED=4000000000, transform=None, augment_past=False, augment_future=False,
                  augmentation=None, keep_temporality=True, past_equal_future=False, signal_quality_path=None,
                  signal_quality_step=1600, signal_quality_mode=None, device=None):
-        if transform is not None or augment_past or augment_future or augmentation is not None:
-            raise NotImplementedError("audio augmentation is not on the MI355X feeder path")
+        if transform is not None and not isinstance(transform, PeakNorm):
+            raise NotImplementedError("the only window transform on the MI355X feeder path is PeakNorm")
+        if augmentation is not None and not all(hasattr(augmentation, name) for name in ("draw_one", "seal", "apply")):
+            raise NotImplementedError("augmentation must be a transform of cpc2_amd.data_augmentation (draw_one / seal / apply)")
+        self.transform = transform
+        self.augment_past = augment_past
+        self.augment_future = augment_future
+        self.augmentation = augmentation
+        self.past_equal_future = past_equal_future
+        if self.past_equal_future and not self.augment_past:         # dataset.py:85-87
+            raise ValueError("Can only apply the same transformation on past and future sequences,"
+                             "when past sequence is augmented. Here --augment_past = False")
         self.MAX_SIZE_LOADED = MAX_SIZE_LOADED
         self.dbPath = Path(path)
         self.sizeWindow = sizeWindow
@@ -451,21 +478,54 @@ class AudioBatchData:
         b = len(offsets)
         off = torch.tensor(offsets, dtype=torch.int64)
         if self.data.is_cuda:
-            off = off.to(self.device)
-            out = torch.empty(b, 1, self.sizeWindow, dtype=torch.float32, device=self.device)
-            check(_lib.load().cpc_window_gather(ptr(self.data), self.data.numel(), ptr(off), ptr(out), b, self.sizeWindow,
-                                                stream_ptr(self.device)), "window_gather")
-        else:
-            out = torch.stack([self.data[o:o + self.sizeWindow] for o in offsets]).view(b, 1, self.sizeWindow)
-        return out.unsqueeze(1).expand(b, 2, 1, self.sizeWindow)
+            return self.windows_from(off.to(self.device))
+        out = torch.stack([self.data[o:o + self.sizeWindow] for o in offsets])
+        if self.transform is not None:
+            out = self.transform(out)
+        return out.view(b, 1, self.sizeWindow).unsqueeze(1).expand(b, 2, 1, self.sizeWindow)
 
     def windows_from(self, off_dev):
         """The same batch from offsets that already are a device int64 tensor (the loader uploads a whole pack's offsets at once)."""
         b = off_dev.numel()
         out = torch.empty(b, 1, self.sizeWindow, dtype=torch.float32, device=self.device)
-        check(_lib.load().cpc_window_gather(ptr(self.data), self.data.numel(), ptr(off_dev), ptr(out), b, self.sizeWindow,
-                                            stream_ptr(self.device)), "window_gather")
+        self._clean_into(off_dev, out)
         return out.unsqueeze(1).expand(b, 2, 1, self.sizeWindow)
+
+    def _clean_into(self, off_dev, out):
+        """The unaugmented windows at `off_dev` (after `transform`) written into the [b, 1, W] buffer `out`."""
+        lib = _lib.load()
+        if self.transform is not None:
+            check(lib.cpc_augment_peak_norm(ptr(self.data), self.data.numel(), ptr(off_dev), ptr(out), off_dev.numel(),
+                                            self.sizeWindow, stream_ptr(self.device)), "augment_peak_norm")
+        else:
+            check(lib.cpc_window_gather(ptr(self.data), self.data.numel(), ptr(off_dev), ptr(out), off_dev.numel(),
+                                        self.sizeWindow, stream_ptr(self.device)), "window_gather")
+        return out
+
+    def augmented_halves(self):
+        """Which halves `augmentation` writes with draws of their own: (past, future) -- dataset.py:308-318."""
+        if self.augmentation is None:
+            return False, False
+        return bool(self.augment_past), bool(self.augment_future) and not self.past_equal_future
+
+    def augmented_from(self, off_dev, plans, lo, hi):
+        """The batch of dataset.py:308-321 for the windows at `off_dev`, rows [lo, hi) of the pack's plans (past, future):
+        a [2, b, 1, W] buffer seen as [b, 2, 1, W]."""
+        from .data_augmentation import FlatWindows
+        b, w = off_dev.numel(), self.sizeWindow
+        past, future = self.augmented_halves()
+        pair = torch.empty(1 if self.past_equal_future else 2, b, 1, w, dtype=torch.float32, device=self.device)
+        for half, (on, plan) in enumerate(zip((past, future), plans)):
+            if half >= pair.size(0):
+                break
+            if not on:
+                self._clean_into(off_dev, pair[half])
+                continue
+            src = FlatWindows(self.data, off_dev) if self.transform is None else self._clean_into(off_dev, torch.empty_like(pair[half]))
+            self.augmentation.apply(plan, lo, hi, src, pair[half])
+        if self.past_equal_future:
+            return pair[0].unsqueeze(1).expand(b, 2, 1, w)
+        return pair.transpose(0, 1)
 
     def getBaseSampler(self, type, batchSize, offset, batchSizePerGPU=None):
         n = self.data.numel()
@@ -517,12 +577,65 @@ class _AudioLoader:
     def __len__(self):
         return self.dataset.totSize // (self.dataset.sizeWindow * self.batchSize)
 
-    def __iter__(self):
+    def _pack_batches(self):
+        d = self.dataset
+        limit = d.data.numel() - d.sizeWindow
+        batches = [[o for o in batch if 0 <= o <= limit] for batch in self._sampler()]
+        return [batch for batch in batches if batch]
+
+    def pack_plan(self):
+        """The host side of the current pack: its batches of window offsets (the sampler's draws, windows that leave the pack
+        dropped) and, with augmentation, the plans of the past and of the future half -- drawn window by window in batch order,
+        past before future, as the reference's __getitem__ (dataset.py:308-318) would for these windows in this order.  A pure
+        function of the generators' states."""
+        d = self.dataset
+        batches = self._pack_batches()
+        past, future = d.augmented_halves()
+        plans = (None, None)
+        if past or future:
+            import gc
+            n = sum(len(batch) for batch in batches)
+            entries = ([], [])
+            draw, window = d.augmentation.draw_one, d.sizeWindow
+            # (the entries are tuples of numbers: nothing for the cyclic collector to find, and its passes over a growing list
+            #  -- in a process with torch's objects on the books -- cost four times what the draws do: paused for the loop)
+            collecting = gc.isenabled()
+            gc.disable()
+            try:
+                for _ in range(n):
+                    if past:
+                        entries[0].append(draw(window))
+                    if future:
+                        entries[1].append(draw(window))
+            finally:
+                if collecting:
+                    gc.enable()
+            plans = tuple(d.augmentation.seal(e, d.device) if on else None for e, on in zip(entries, (past, future)))
+        return batches, plans
+
+    def offsets(self):
+        """(the pack's flat device vector, a batch's window offsets) for every batch of every pack, nothing gathered: how
+        AdditiveNoiseAugment takes the noise windows."""
         d = self.dataset
         for loop in range(self.nLoops):
-            limit = d.data.numel() - d.sizeWindow
-            batches = [[o for o in batch if 0 <= o <= limit] for batch in self._sampler()]
-            batches = [batch for batch in batches if batch]
+            batches = self._pack_batches()
+            data = d.data
+            for batch in batches:
+                yield data, batch
+            if loop + 1 < self.nLoops or len(d.packageIndex) > 1:
+                d.loadNextPack()
+
+    def __iter__(self):
+        d = self.dataset
+        self.plans = []
+        augmenting = any(d.augmented_halves())
+        if augmenting and not d.data.is_cuda:
+            raise RuntimeError("cpc2_amd runs only on a GPU (HIP) device: augmented batches are built by kernels. "
+                               "There is no CPU fallback.")
+        for loop in range(self.nLoops):
+            batches, plans = self.pack_plan()
+            if augmenting:
+                self.plans.append({"batches": batches, "past": plans[0], "future": plans[1]})
             if d.data.is_cuda and batches:
                 # The whole pack's window offsets go to the device in ONE pinned, asynchronous copy and the speaker labels are looked
                 # up there (bucketize over the speaker table == dataset.py:254's bisect): a step of the loop then uploads nothing --
@@ -535,14 +648,20 @@ class _AudioLoader:
                 offs = host.to(d.device, non_blocking=True)
                 table = torch.tensor(d.speakerLabel, dtype=torch.int64).pin_memory().to(d.device, non_blocking=True)
                 labels = torch.bucketize(offs, table, right=True) - 1
+                row = 0
                 for i, batch in enumerate(batches):
                     off_dev, label = offs[i, :len(batch)], labels[i, :len(batch)]
                     if d.phoneSize > 0:                      # dataset.py:298-301: the phone labels replace the speaker's
                         label = d.phonemes_from(off_dev)
-                    if d.signal_quality_path is not None:    # dataset.py:327-330: a third element per sample
-                        yield d.windows_from(off_dev), label, torch.stack([d.getSignalQuality(o) for o in batch])
+                    if augmenting:                           # dataset.py:308-321 (the plan's rows follow the batches)
+                        sequence = d.augmented_from(off_dev, plans, row, row + len(batch))
+                        row += len(batch)
                     else:
-                        yield d.windows_from(off_dev), label
+                        sequence = d.windows_from(off_dev)
+                    if d.signal_quality_path is not None:    # dataset.py:327-330: a third element per sample
+                        yield sequence, label, torch.stack([d.getSignalQuality(o) for o in batch])
+                    else:
+                        yield sequence, label
             else:
                 for batch in batches:
                     if d.phoneSize > 0:

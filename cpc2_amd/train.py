@@ -962,10 +962,10 @@ def refuseUnsupported(args):
         raise SystemExit(f"--nGPU {args.nGPU}: this package runs one GPU per process (there is no DataParallel wrapper); run "
                          f"with --nGPU 1, or one process per GPU: python -m torch.distributed.run --nproc_per_node {args.nGPU} "
                          "-m cpc2_amd.train --distributed ...")
-    augmenting = args.augment_type is not None and list(args.augment_type) != ['none']
-    if (args.augment_past or args.augment_future) and augmenting:
-        raise NotImplementedError(f"--augment_past / --augment_future with --augment_type {' '.join(args.augment_type)}: audio "
-                                  "augmentation is not on the MI355X feeder path (only --augment_type none)")
+    from .data_augmentation import BUILT_TYPES, unbuilt_message
+    asked = list(args.augment_type) if args.augment_type is not None else []
+    if (args.augment_past or args.augment_future) and any(t not in BUILT_TYPES and t != 'none' for t in asked):
+        raise NotImplementedError(unbuilt_message(asked))
     if args.encoder_type in ("mfcc", "lfb"):
         raise NotImplementedError(f"--encoder_type {args.encoder_type}: only the raw-waveform encoder (--encoder_type cpc) is built")
     if args.cpc_mode == "bert":
@@ -997,12 +997,17 @@ def main(argv):
         --nGPU above 1 without --distributed is refused; --distributed reads the torch.distributed.run environment
         (init_distributed_mode) instead of SLURM's;
       * what refuseUnsupported lists is refused before any file is read (and again for the arguments of a resumed run);
+      * augmentation (train.py:356-419): the noise data set's keep_temporality follows the reference's test on
+        --naming_convention, and no convention counts as False (the reference crashes on None there); under --distributed
+        every rank uses the whole noise set (the reference shards the list after the data set is built, which changes nothing);
+        `additive` without --pathDBNoise raises before the speech data is loaded; validation data is never augmented;
       * no validation sequence is an error here (the reference builds no validation set and fails inside run());
       * logs that lack saveStep / logging_step (a hand-made run directory) get them from the command line;
       * audio files are decoded in this process: --n_process_loader is accepted and unused."""
     import os
     from . import feature_loader as fl
-    from .dataset import AudioBatchData, filterSeqs, findAllSeqs, shard_for_rank
+    from .data_augmentation import augmentation_factory
+    from .dataset import AudioBatchData, PeakNorm, filterSeqs, findAllSeqs, shard_for_rank
     args = parseArgs(argv)
     refuseUnsupported(args)
 
@@ -1069,10 +1074,33 @@ def main(argv):
         raise ValueError("No validation sequences: the 95 / 5 split (or --pathVal) left none, and every epoch validates. "
                          "Give more files, or --pathVal.")
 
+    # train.py:356-385: the noise data set (one speaker, PeakNorm, its own augmentation under --meta_aug)
+    noiseDataset = None
+    augmenting = args.augment_past or args.augment_future
+    if augmenting and args.augment_type and 'additive' in args.augment_type and args.pathDBNoise is None:
+        raise RuntimeError('Noise dataset is needed for the additive noise')
+    if args.pathDBNoise is not None and augmenting:
+        seqNoise, _ = findAllSeqs(args.pathDBNoise, extension=args.noise_extension, loadCache=True, speaker_level=0)
+        if args.pathSeqNoise is not None:
+            seqNoise = filterSeqs(args.pathSeqNoise, seqNoise)
+        if args.debug:
+            seqNoise = seqNoise[:100]
+        print(f'\nLoading noise data at {args.pathDBNoise}')
+        print("Loading the noise dataset")
+        noiseDataset = AudioBatchData(args.pathDBNoise, args.sizeWindow, seqNoise, None, 1, transform=PeakNorm(),
+                                      nProcessLoader=args.n_process_loader, MAX_SIZE_LOADED=args.max_size_loaded,
+                                      augment_future=False, augment_past=args.meta_aug,
+                                      augmentation=augmentation_factory(args, noiseDataset, applied_on_noise=True),
+                                      keep_temporality=(args.naming_convention or "").startswith("id_spkr_onset_offset"),
+                                      past_equal_future=args.meta_aug)
+
     print(f'\nLoading audio data at {args.pathDB}')
     print("Loading the training dataset")
+    augmentation = augmentation_factory(args, noiseDataset)      # (before the audio is read: its errors come first)
     trainDataset = AudioBatchData(args.pathDB, args.sizeWindow, seqTrain, None, len(speakers),
                                   nProcessLoader=args.n_process_loader, MAX_SIZE_LOADED=args.max_size_loaded,
+                                  augment_future=args.augment_future, augment_past=args.augment_past,
+                                  augmentation=augmentation,
                                   keep_temporality=args.samplingType == "temporalsamespeaker",
                                   signal_quality_path=args.signal_quality_path, signal_quality_step=args.signal_quality_step,
                                   signal_quality_mode=args.signal_quality_mode, past_equal_future=args.past_equal_future)

@@ -571,6 +571,32 @@ int cpc_probe_ctc(const float *logits, int b, int t, int k, const int64_t *targe
                   float *loss, float *dlogits, void *scratch, size_t scratch_bytes, cpc_stream_t stream);
 int cpc_probe_collapse(const int64_t *labels, int b, int t, int64_t *out, long ldo, int64_t *lengths, cpc_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Audio augmentation on device batches (cpc/data_augmentation.py; cpc2_amd/data_augmentation.py).  Every pointer is a DEVICE
+ * pointer.  An operand given as (vector, total, offsets) is read straight out of a flat vector: window i is
+ * vector[offsets[i] .. offsets[i] + window), zeros outside [0, total); with offsets == NULL the operand already is a
+ * [batch][window] buffer (total is then ignored).  No float atomics: two launches on the same inputs give the same bits.
+ * version 111.
+ * augment_additive: out[i] = peak(e(speech_i) + gain[i] * e(n_i)), e(w) = w / (sqrt(mean(w^2)) + 1e-8),
+ *   peak(m) = m / (max|m| + 1e-8); n_i = noise_i / (max|noise_i| + 1e-8) when noise_peak_norm (the noise data set's
+ *   PeakNorm), else noise_i.  One launch per batch; windows of up to 32768 samples are read from global memory once.
+ * augment_peak_norm: out[i] = w_i / (max|w_i| + 1e-8); out may be the source buffer.
+ * augment_fir: y_i[t] = sum_{k <= t, k < ir_len[i]} ir[ir_off[i] + k] * x_i[t - k] for t < window (the causal convolution cut
+ *   to the input length), then out[i] = y_i / (max|y_i| + 1e-8).  ir_len[i] == 0 leaves window i as it is apart from that
+ *   normalisation; taps beyond `window` or beyond ir_total are never read.  x is a [batch][window] buffer and must not be out.
+ *   scratch: cpc_augment_fir_scratch_bytes(batch, window).
+ * augment_time_dropout: x[i][start[i] .. start[i] + length[i]) = 0 (clipped to the window), in place; nothing else is written.
+ * ------------------------------------------------------------------------------------------ */
+int cpc_augment_additive(const float *speech, long speech_total, const long *speech_off, const float *noise, long noise_total,
+                         const long *noise_off, int noise_peak_norm, const float *gain, float *out, int batch, int window,
+                         cpc_stream_t stream);
+int cpc_augment_peak_norm(const float *src, long src_total, const long *src_off, float *out, int batch, int window,
+                          cpc_stream_t stream);
+size_t cpc_augment_fir_scratch_bytes(int batch, int window);
+int cpc_augment_fir(const float *x, const float *ir, long ir_total, const long *ir_off, const int *ir_len, float *out,
+                    void *scratch, size_t scratch_bytes, int batch, int window, cpc_stream_t stream);
+int cpc_augment_time_dropout(float *x, const long *start, const long *length, int batch, int window, cpc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
