@@ -261,7 +261,8 @@ class NaturalReverb(_Transform):
     batchSize consecutive windows, then a new one is drawn (:312-317; the first one when the transform is built).
 
     The responses are the .wav files under ir_paths (findAllSeqs, no cache), mixed to mono and loaded once to the device as one
-    flat vector with an offsets table.  A file whose rate is not `sr` is refused: there is no resampler here.
+    flat vector with an offsets table.  A file whose rate is not `sr` is refused: nothing is resampled here
+    (cpc2_amd.eval.utils.adjust_sample_rate converts a directory beforehand).
 
     Entry: index of the response, or -1 for a skipped convolution.  Plan: ir_index [n] i64, ir_off [n] i64, ir_len [n] i32."""
 
@@ -285,7 +286,8 @@ class NaturalReverb(_Transform):
             wav, rate = audio.load(path)
             if rate != sr:
                 raise ValueError(f"impulse response {path} is sampled at {rate} Hz, not at --ir_sample_rate {sr}: responses "
-                                 "are not resampled here, convert the file")
+                                 "are not resampled here, convert the file.  `python -m cpc2_amd.eval.utils.adjust_sample_rate "
+                                 f"{ir_paths} OUT_DIR --out_sample_rate {sr} --recursive` converts the whole directory")
             responses.append(wav.float().mean(dim=0))
         self.ir_len = np.array([r.numel() for r in responses], dtype=np.int64)
         self.ir_off = np.concatenate([[0], np.cumsum(self.ir_len)[:-1]]).astype(np.int64)

@@ -45,7 +45,7 @@ int cpc_version(void);          /* 100 x major + minor; 105 = the entry points o
                                   * cpc_recurrent_backward_calls, cpc_side_tail_wait); 107 = cpc_abx_dtw / cpc_abx_counts;
                                   * 108 = cpc_kmeans_scratch_bytes / cpc_kmeans_assign / cpc_kmeans_distances / cpc_kmeans_accumulate;
                                   * 109 = cpc_probe_xent / cpc_probe_head_backward / cpc_probe_ctc / cpc_probe_collapse (+ scratch queries);
-                                  * 110 = cpc_abx_dtw_units (+ scratch query) */
+                                  * 110 = cpc_abx_dtw_units (+ scratch query); 111 = cpc_augment_*; 112 = cpc_resample_* */
 const char *cpc_last_error(void);
 
 /* In-situ kernel timing for bench.py: when enabled, the launchers bracket each launch of the named
@@ -596,6 +596,32 @@ size_t cpc_augment_fir_scratch_bytes(int batch, int window);
 int cpc_augment_fir(const float *x, const float *ir, long ir_total, const long *ir_off, const int *ir_len, float *out,
                     void *scratch, size_t scratch_bytes, int batch, int window, cpc_stream_t stream);
 int cpc_augment_time_dropout(float *x, const long *start, const long *length, int batch, int window, cpc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Sample-rate conversion (torchaudio's sinc_interp_hann resampler, the transform of the reference's
+ * cpc/eval/utils/adjust_sample_rate.py; cpc2_amd/audio.py: resample, resample_pack, save_wav).  version 112.
+ *   g = gcd(orig_freq, new_freq), o = orig_freq / g, n = new_freq / g, base = min(o, n) * rolloff,
+ *   w = ceil(lowpass_filter_width * o / base), taps = 2 w + o,
+ *   h[p][j] = sinc(t) * cos(t pi / (2 width))^2 * base / o with t = clamp((-p / n + (j - w) / o) * base, -width, +width),
+ *   y[f n + p] = sum_j h[p][j] * xp[f o + j], xp = x with w zeros in front and w + o zeros behind; a signal of L samples
+ *   gives ceil(n L / o).
+ * resample_plan: o, n, w, taps of a pair of rates (host; nothing is launched).
+ * resample_table_host: fills table_host[p * taps + j] (HOST memory, n * taps floats; capacity = the floats it holds), computed
+ *   in double and rounded once to f32.  The caller copies it to the device and passes it to cpc_resample.
+ * resample: `count` signals in one launch.  Signal i is x[in_off[i] .. in_off[i] + in_len[i]) of a flat device vector of
+ *   x_total floats and leaves y[out_off[i] .. out_off[i] + ceil(n in_len[i] / o)); nothing else of y is written and a signal never
+ *   reads outside its own samples (zeros there).  in_off, in_len, out_off: int64 DEVICE tables; max_len: the largest in_len
+ *   (host value: it sizes the grid; longer signals would be cut).  A signal whose table entry leaves x is skipped.  All sample
+ *   indices are 64-bit.  Each output is one f32 fmaf chain over j ascending: the bits do not depend on the pack or the tiling.
+ *   Refused (CPC_ERR_INVALID): a reduced ratio whose 2 w + 2 o exceeds a workgroup's 8192-float signal segment.
+ * resample_to_pcm16: q[i] = (int16) clamp(rint(32768 * y[i]), -32768, 32767), ties to even; *clamped (a device counter the
+ *   caller zeroes) is increased by the number of samples the clamp changed.
+ * ------------------------------------------------------------------------------------------ */
+int cpc_resample_plan(int orig_freq, int new_freq, int lowpass_filter_width, double rolloff, int *o, int *n, int *w, int *taps);
+int cpc_resample_table_host(int orig_freq, int new_freq, int lowpass_filter_width, double rolloff, float *table_host, long capacity);
+int cpc_resample(const float *x, long x_total, const long *in_off, const long *in_len, int count, long max_len, const float *table,
+                 int o, int n, int w, float *y, long y_total, const long *out_off, cpc_stream_t stream);
+int cpc_resample_to_pcm16(const float *y, long count, int16_t *q, unsigned long long *clamped, cpc_stream_t stream);
 
 #ifdef __cplusplus
 }
