@@ -137,6 +137,10 @@ SIGNATURES = {
     "cpc_resample_table_host": (c_int, [c_int, c_int, c_int, ctypes.c_double, c_ptr, c_long]),
     "cpc_resample": (c_int, [c_ptr, c_long, c_ptr, c_ptr, c_int, c_long, c_ptr, c_int, c_int, c_int, c_ptr, c_long, c_ptr, c_ptr]),
     "cpc_resample_to_pcm16": (c_int, [c_ptr, c_long, c_ptr, c_ptr, c_ptr]),
+    "cpc_text_format_f32": (c_int, [c_ptr, c_long, c_ptr, c_ptr, c_ptr]),
+    "cpc_text_format_i64": (c_int, [c_ptr, c_long, c_ptr, c_ptr, c_ptr]),
+    "cpc_text_row_bytes": (c_int, [c_ptr, c_long, c_int, c_ptr, c_ptr, c_ptr]),
+    "cpc_text_pack": (c_int, [c_ptr, c_ptr, c_long, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_long, c_ptr]),
 }
 
 _lib = None

@@ -206,8 +206,9 @@ def _plan(n_samples, chunk, strict, downsampling, drop_short_rest):
     return spans
 
 
-def _extract(featureMaker, seq, spans, group, seqNorm):
-    """Run the spans, `group` equal-length ones per model call, in file order; [1, frames, dim] on the host."""
+def _extract(featureMaker, seq, spans, group, seqNorm, to_host=True):
+    """Run the spans, `group` equal-length ones per model call, in file order; [1, frames, dim] on the host (to_host False: left
+    on the model's device)."""
     wave = seq.reshape(-1).to(_model_device(featureMaker))             # the file goes to the device once
     pieces = []
     i = 0
@@ -224,7 +225,8 @@ def _extract(featureMaker, seq, spans, group, seqNorm):
                 row = row.unsqueeze(0)
                 if seqNorm:
                     row = seqNormalization(row)
-                pieces.append((row[:, -span.tail:] if span.tail else row).cpu())
+                piece = row[:, -span.tail:] if span.tail else row
+                pieces.append(piece.cpu() if to_host else piece)
             i = j
     return torch.cat(pieces, dim=1)
 
@@ -239,6 +241,14 @@ def buildFeature(featureMaker, seqPath, strict=False, maxSizeSeq=64000, seqNorm=
     seq = _load(seqPath)
     spans = _plan(seq.size(1), maxSizeSeq, strict, featureMaker.getDownsamplingFactor(), drop_short_rest=False)
     return _extract(featureMaker, seq, spans, 1, seqNorm)
+
+
+def buildFeature_device(featureMaker, seqPath, strict=False, maxSizeSeq=64000, seqNorm=False):
+    """buildFeature with the result left on the model's device, for consumers that work on it there (the text kernels of
+    cpc2_amd.text behind eval/build_zeroSpeech_features.py): the same spans, the same values."""
+    seq = _load(seqPath)
+    spans = _plan(seq.size(1), maxSizeSeq, strict, featureMaker.getDownsamplingFactor(), drop_short_rest=False)
+    return _extract(featureMaker, seq, spans, 1, seqNorm, to_host=False)
 
 
 def buildFeature_batch(featureMaker, seqPath, strict=False, maxSizeSeq=8000, seqNorm=False, batch_size=8):

@@ -45,7 +45,8 @@ int cpc_version(void);          /* 100 x major + minor; 105 = the entry points o
                                   * cpc_recurrent_backward_calls, cpc_side_tail_wait); 107 = cpc_abx_dtw / cpc_abx_counts;
                                   * 108 = cpc_kmeans_scratch_bytes / cpc_kmeans_assign / cpc_kmeans_distances / cpc_kmeans_accumulate;
                                   * 109 = cpc_probe_xent / cpc_probe_head_backward / cpc_probe_ctc / cpc_probe_collapse (+ scratch queries);
-                                  * 110 = cpc_abx_dtw_units (+ scratch query); 111 = cpc_augment_*; 112 = cpc_resample_* */
+                                  * 110 = cpc_abx_dtw_units (+ scratch query); 111 = cpc_augment_*; 112 = cpc_resample_*;
+                                  * 113 = cpc_text_* */
 const char *cpc_last_error(void);
 
 /* In-situ kernel timing for bench.py: when enabled, the launchers bracket each launch of the named
@@ -622,6 +623,28 @@ int cpc_resample_table_host(int orig_freq, int new_freq, int lowpass_filter_widt
 int cpc_resample(const float *x, long x_total, const long *in_off, const long *in_len, int count, long max_len, const float *table,
                  int o, int n, int w, float *y, long y_total, const long *out_off, cpc_stream_t stream);
 int cpc_resample_to_pcm16(const float *y, long count, int16_t *q, unsigned long long *clamped, cpc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Decimal text of a device matrix (the `fea` lines of the reference's cpc/eval/build_zeroSpeech_features.py;
+ * cpc2_amd/text.py: format_rows).  version 113.
+ *   row r of the text = prefix[r] ' ' v(r, 0) ' ' v(r, 1) ... v(r, cols - 1) '\n'; without prefixes a row starts at its first value.
+ * text_format_f32: value i of `count` floats -> slots[3 i .. 3 i + 3) (24 bytes, the text from byte 0 on, zeros behind it) and
+ *   len[i] (1 .. 23).  The text is CPython's repr(float(v)) byte for byte: the shortest decimal string that reads back as the
+ *   double equal to v, the closest among the shortest, an exact tie to the even digit; positional with the first digit's decimal
+ *   exponent in [-4, 16) ("0.0001", "1.0", "1000000000000000.0"), else d[.ddd]e+XX / e-XX; "-0.0", "inf", "-inf", "nan".
+ *   Integer arithmetic throughout (csrc/text_digits.h).
+ * text_format_i64: the same slots for int64 values as plain decimal integers (at most 20 bytes).
+ * text_row_bytes: row_bytes[r] = the bytes of row r: its texts, a blank or the newline behind each, and with prefixes
+ *   (prefix_off: int64 DEVICE table of rows + 1 offsets into `prefix`; NULL: none) the prefix and the blank behind it.  The caller's
+ *   exclusive scan of row_bytes is row_off; its total out_total.
+ * text_pack: writes the rows to out[row_off[r] ..).  A row whose offsets do not fit out_total is not written.  All offsets are
+ *   64-bit; 1 <= cols < 2^26.
+ * ------------------------------------------------------------------------------------------ */
+int cpc_text_format_f32(const float *x, long count, unsigned long long *slots, unsigned char *len, cpc_stream_t stream);
+int cpc_text_format_i64(const long *x, long count, unsigned long long *slots, unsigned char *len, cpc_stream_t stream);
+int cpc_text_row_bytes(const unsigned char *len, long rows, int cols, const long *prefix_off, long *row_bytes, cpc_stream_t stream);
+int cpc_text_pack(const unsigned long long *slots, const unsigned char *len, long rows, int cols, const unsigned char *prefix,
+                  const long *prefix_off, const long *row_off, unsigned char *out, long out_total, cpc_stream_t stream);
 
 #ifdef __cplusplus
 }
