@@ -1032,6 +1032,7 @@ struct EncLayout {
     unsigned short *dUp;    long dUplane, dUrows;         // scratch: dU of the current layer (largest: layer 1)
 };
 
+constexpr int kEncBackwardMinLength = 400;
 constexpr int NORM_BWD_BLOCKS = 2048;   // 8 per CU: the row loop is a load -> use chain, only occupancy hides its latency
 constexpr int CONV0_BWD_BLOCKS = 768;
 
@@ -1043,12 +1044,20 @@ static bool use_planes(int H) { return H % 256 == 0; }
 static int enc_layout(EncLayout &e, int N, int length, int H, void *saved, void *scratch)
 {
     CPC_REQUIRE(supported_hidden(H), "encoder: hidden size %d not supported (32, 64, 128, 256, 512)", H);
-    CPC_REQUIRE(N > 0 && length >= 400, "encoder: need n_windows > 0 and length >= 400 (got %d, %d)", N, length);
+    // Any length that leaves a frame (159 samples on, like the reference's Conv1d stack: the non-strict rest of a file is fed on its
+    // own, feature_loader.py).  Nothing below depends on a minimum: a layer's data rows and halo fit its R rows for every length
+    // (k == 2 s: s (L_out + 2) = s (floor((L_in + 2 p) / s) + 1) > L_in + 2 p), the row kernels decide every row by its (sample, frame)
+    // and the products take M >= 1.  (Until the feature readers were held to the reference's outputs this line asked for 400
+    // samples, a round figure from the first version of this file that no kernel needed.  What it did hide: the frame rule
+    // below in C's truncating division gives 154 .. 158 samples ONE frame -- (3 - 4) / 2 + 1 -- where the reference raises;
+    // a negative span is no frame.)
+    CPC_REQUIRE(N > 0 && length >= 1, "encoder: need n_windows > 0 and length > 0 (got %d, %d)", N, length);
     e.H = H; e.N = N;
     e.L[0] = length;
     for (int i = 0; i < 5; ++i) {
-        e.L[i + 1] = (e.L[i] + 2 * kConv[i].p - kConv[i].k) / kConv[i].s + 1;
-        CPC_REQUIRE(e.L[i + 1] >= 1, "encoder: input too short");
+        const int span = e.L[i] + 2 * kConv[i].p - kConv[i].k;
+        e.L[i + 1] = span >= 0 ? span / kConv[i].s + 1 : 0;
+        CPC_REQUIRE(e.L[i + 1] >= 1, "encoder: %d samples leave no frame (159 is the shortest input)", length);
     }
     for (int i = 1; i < 5; ++i) e.Rv[i] = e.L[i + 1] + 2;
     e.Rv[0] = 0;
@@ -1238,6 +1247,10 @@ static int encoder_backward(const float *x, const float *const *prm, const float
                             const float *x2 = nullptr, int n_first = 0)
 {
     CPC_REQUIRE(x2 == nullptr || (n_first > 0 && n_first < N), "encoder: the first batch must hold 1 .. n_windows - 1 windows (got %d of %d)", n_first, N);
+    // the forward pass takes every length that leaves a frame (feature extraction, under no_grad).  The backward is verified from 400
+    // samples on; below, the plane-fed weight-gradient product (gemm_tn_planes: >= 64 reduction rows, N (L_out + 2) of conv4) would
+    // refuse one- and two-frame inputs half-way through unless 16-22 windows came together -- refused here, by name, before any launch
+    CPC_REQUIRE(length >= kEncBackwardMinLength, "encoder_backward: inputs shorter than %d samples are forward-only (got %d)", kEncBackwardMinLength, length);
     EncLayout e;
     CPC_TRY(enc_layout(e, N, length, H, saved, scratch));
 
@@ -1362,7 +1375,11 @@ static int encoder_backward(const float *x, const float *const *prm, const float
 extern "C" int cpc_encoder_frames(int length)
 {
     int l = length;
-    for (int i = 0; i < 5; ++i) l = (l + 2 * cpc::kConv[i].p - cpc::kConv[i].k) / cpc::kConv[i].s + 1;
+    for (int i = 0; i < 5; ++i) {
+        const int span = l + 2 * cpc::kConv[i].p - cpc::kConv[i].k;
+        if (span < 0) return 0;                 // (158 samples or fewer: no frame)
+        l = span / cpc::kConv[i].s + 1;
+    }
     return l;
 }
 

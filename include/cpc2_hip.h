@@ -177,6 +177,8 @@ int cpc_channelnorm_backward(const float *x, const float *w, const float *dy, co
  *   saved    activations kept for backward (cpc_encoder_saved_bytes)
  *   scratch  temporaries (cpc_encoder_scratch_bytes; same query serves forward and backward)
  *   grads    20 pointers, same order/shapes as params; overwritten (not accumulated)
+ * Lengths: the forward pass takes every length that leaves a frame, i.e. 159 samples on (cpc_encoder_frames(158) == 0, and the
+ * size queries return 0 below 159); the backward passes take 400 samples on and refuse shorter inputs (CPC_ERR_INVALID).
  * ------------------------------------------------------------------------------------------ */
 int cpc_encoder_frames(int length);
 size_t cpc_encoder_saved_bytes(int n_windows, int length, int hidden);

@@ -344,8 +344,14 @@ def test_encoder_vs_reference_golden(golden):
 
 # (256, 44, 20480): conv1's product has more than 160 tiles and does not split K -> ChannelNorm + ReLU + split in its epilogue
 # (256, 43, 19800): the same with frame counts that are no multiple of the tile (990 per window: tiles straddle windows, the last is partial)
+# lengths 159 .. 399: one and two frames, what the non-strict rest of a file feeds on its own (feature_loader.buildFeature); 159 is
+# the shortest input the reference's Conv1d stack takes.  Forward only: the backward refuses them by name
+_SHORT_ENCODER_INPUTS = [(hidden, n, length) for hidden in (32, 256, 512)
+                         for n, length in ((1, 159), (3, 160), (1, 319), (2, 320), (1, 399))] + [(64, 1, 159), (128, 2, 319)]
+
+
 @pytest.mark.parametrize("hidden,n,length", [(256, 3, 20480), (64, 2, 3300), (512, 2, 4800), (128, 1, 20480), (256, 44, 20480),
-                                             (256, 43, 19800)])
+                                             (256, 43, 19800)] + _SHORT_ENCODER_INPUTS)
 def test_encoder_vs_oracle_fp64(hidden, n, length):
     params = synth.encoder_params(hidden, seed=5)
     enc = load_encoder(hidden, params)
@@ -357,6 +363,11 @@ def test_encoder_vs_oracle_fp64(hidden, n, length):
     out = enc(x.to(DEV))
     assert tuple(out.shape) == tuple(ref.shape)
     assert_close(out, ref, 2e-5, "encoder output")
+    if length < 400:
+        assert tuple(out.shape) == (n, hidden, 1 if length < 319 else 2)
+        with pytest.raises(ValueError, match="encoder_backward: inputs shorter than 400 samples are forward-only"):
+            (out * gout.to(DEV)).sum().backward()
+        return
     (out * gout.to(DEV)).sum().backward()
     # Many windows: the gradients below a layer are conditioned by that layer's ReLU decisions.  Of ~6e7 pre-activations a
     # handful lie within fp32 rounding of zero and fall the other way in ANY fp32 evaluation than in fp64; each such decision
@@ -646,6 +657,33 @@ def test_gru_vs_oracle_fp64(hid, layers, n, t_len):
     assert_close(xd.grad, x64.grad, 1e-4, "gru dx")
     for name, p in ar.named_parameters():
         assert_close(p.grad, p64["gAR." + name].grad, 1e-4, f"gru grad {name}")
+
+
+# What feature extraction feeds the context network for a rest of 159 .. 399 samples: one window (or a few) of one or two frames
+@pytest.mark.parametrize("t_len", [1, 2])
+@pytest.mark.parametrize("n", [1, 3])
+@pytest.mark.parametrize("mode,hid,layers", [("GRU", 32, 1), ("GRU", 256, 1), ("GRU", 512, 2), ("LSTM", 32, 1), ("LSTM", 256, 2),
+                                             ("LSTM", 512, 1), ("RNN", 32, 2), ("RNN", 256, 1), ("RNN", 512, 1),
+                                             ("transformer", 64, 1), ("transformer", 256, 1), ("transformer", 512, 1)])
+def test_context_networks_on_one_and_two_frames_vs_oracle_fp64(mode, hid, layers, n, t_len):
+    x = synth.features((n, t_len, hid), 10, relu=True)
+    if mode == "transformer":
+        params = synth.transformer_params(hid, hid, 128, 81)
+        net = load_transformer(hid, hid, 128, params).eval()
+        ref = O.transformer_layer_forward(x.double(), to64(params), "gAR.0.", size_seq=128)
+        tol = 2e-5
+    else:
+        make, fwd = {"GRU": (synth.gru_params, O.gru_forward), **_RECURRENT}[mode]
+        params = make(hid, hid, layers, 9)
+        net = cpc2_amd.CPCAR(hid, hid, False, layers, mode=mode)
+        net.load_state_dict({k[len("gAR."):]: v for k, v in params.items()})
+        net = net.to(DEV).eval()
+        ref = fwd(x.double(), to64(params), layers, "gAR.baseNet.")[0]
+        tol = 1e-5
+    with torch.no_grad():
+        out = net(x.to(DEV))
+    assert tuple(out.shape) == (n, t_len, hid)
+    assert_close(out, ref, tol, f"{mode} on {t_len} frame(s)")
 
 
 _GRU_FORMS_SCRIPT = """
@@ -1542,7 +1580,9 @@ def test_build_feature_on_real_audio_vs_oracle():
         assert feats.shape == ref.shape == (1, 400 + 400 + 359, 64)
         assert_close(feats, ref, 5e-5, f"features get_encoded={get_encoded}")
     strict = buildFeature(FeatureModule(model, False).eval(), path, strict=True, maxSizeSeq=64000)
-    assert strict.shape[1] == wav.shape[1] // 160 - 1 or strict.shape[1] == wav.shape[1] // 160
+    # two whole chunks, then the last 64 000 samples of which the frames the rest covers are kept
+    assert wav.shape[1] // 64000 == 2 and (wav.shape[1] % 64000) // 160 == 359
+    assert strict.shape == (1, 400 + 400 + 359, 64)
 
 
 def test_checkpoint_roundtrip_in_reference_layout(tmp_path):
