@@ -40,11 +40,8 @@ SIGNATURES = {
     "cpc_encoder_frames": (c_int, [c_int]),
     "cpc_encoder_saved_bytes": (c_size_t, [c_int, c_int, c_int]),
     "cpc_encoder_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "cpc_encoder_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_float, c_ptr]),
-    "cpc_encoder_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_float, c_ptr]),
-    "cpc_encoder_backward_deferred": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_float, c_ptr]),
-    "cpc_encoder_forward2": (c_int, [c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_float, c_ptr]),
-    "cpc_encoder_backward2": (c_int, [c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_float, c_int, c_ptr]),
+    "cpc_encoder_forward": (c_int, [c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_float, c_ptr]),
+    "cpc_encoder_backward": (c_int, [c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_float, c_int, c_ptr]),
     "cpc_coop_launches": (c_long, []),
     "cpc_coop_comm_buffers": (c_int, []),
     "cpc_coop_set_policy": (c_int, [c_int]),
@@ -53,25 +50,22 @@ SIGNATURES = {
     "cpc_gru_saved_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "cpc_gru_scratch_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "cpc_gru_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr]),
-    "cpc_gru_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr]),
-    "cpc_gru_backward_deferred": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr]),
+    "cpc_gru_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_int, c_ptr]),
     "cpc_side_tail_join": (c_int, [c_ptr]),
     "cpc_side_tail_wait": (c_int, [c_ptr]),
     "cpc_lstm_saved_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "cpc_lstm_scratch_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "cpc_lstm_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr]),
-    "cpc_lstm_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr]),
-    "cpc_lstm_backward_deferred": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr]),
+    "cpc_lstm_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_int, c_ptr]),
     "cpc_rnn_saved_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "cpc_rnn_scratch_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "cpc_rnn_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr]),
-    "cpc_rnn_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr]),
+    "cpc_rnn_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_int, c_ptr]),
     "cpc_transformer_param_count": (c_int, []),
     "cpc_transformer_saved_bytes": (c_size_t, [c_int] * 7),
     "cpc_transformer_scratch_bytes": (c_size_t, [c_int] * 7),
     "cpc_transformer_forward": (c_int, [c_ptr] * 5 + [c_int] * 7 + [c_float, ctypes.c_ulonglong, c_ptr]),
-    "cpc_transformer_backward": (c_int, [c_ptr] * 7 + [c_int] * 7 + [c_float, ctypes.c_ulonglong, c_ptr]),
-    "cpc_transformer_backward_deferred": (c_int, [c_ptr] * 7 + [c_int] * 7 + [c_float, ctypes.c_ulonglong, c_ptr]),
+    "cpc_transformer_backward": (c_int, [c_ptr] * 7 + [c_int] * 7 + [c_float, ctypes.c_ulonglong, c_int, c_ptr]),
     "cpc_mt_create": (c_ptr, [ctypes.c_uint32]),
     "cpc_mt_destroy": (None, [c_ptr]),
     "cpc_mt_seed": (c_int, [c_ptr, ctypes.c_uint32]),
@@ -97,12 +91,9 @@ SIGNATURES = {
     "cpc_infonce_scratch_bytes": (c_size_t, [c_int] * 6),
     "cpc_infonce_logits_offset": (c_size_t, [c_int] * 6),
     "cpc_infonce_perm_offset": (c_size_t, [c_int] * 6),
-    "cpc_infonce_forward": (c_int, [c_ptr] * 9 + [c_int] * 6 + [c_ptr]),
-    "cpc_infonce_backward": (c_int, [c_ptr] * 11 + [c_int] * 6 + [c_ptr]),
-    "cpc_infonce_backward_deferred": (c_int, [c_ptr] * 11 + [c_int] * 6 + [c_ptr]),
+    "cpc_infonce_forward": (c_int, [c_ptr] * 9 + [c_int] * 7 + [c_ptr]),
+    "cpc_infonce_backward": (c_int, [c_ptr] * 11 + [c_int] * 8 + [c_ptr]),
     "cpc_infonce_join": (c_int, [c_ptr]),
-    "cpc_infonce_forward_cw": (c_int, [c_ptr] * 9 + [c_int] * 6 + [c_ptr]),
-    "cpc_infonce_backward_cw": (c_int, [c_ptr] * 11 + [c_int] * 7 + [c_ptr]),
     "cpc_infonce_forward_pred": (c_int, [c_ptr] * 8 + [c_int] * 5 + [c_ptr]),
     "cpc_infonce_backward_pred": (c_int, [c_ptr] * 9 + [c_int] * 5 + [c_ptr]),
     "cpc_flac_info": (c_int, [ctypes.c_char_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int),
@@ -191,6 +182,11 @@ def check(status, what=""):
 
 def stream_ptr(device):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def device_index(device):
+    """The index of a cuda device: its own, or the current device's when it carries none ("cuda")."""
+    return device.index if device.index is not None else torch.cuda.current_device()
 
 
 def require_gpu(*tensors):

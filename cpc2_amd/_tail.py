@@ -1,14 +1,14 @@
-"""Deferred parameter-gradient work (cpc2_hip.h: cpc_gru_backward_deferred, cpc_encoder_backward_deferred,
-cpc_transformer_backward_deferred + cpc_side_tail_join): the bookkeeping the autograd Functions of model.py / transformers.py share."""
+"""Deferred parameter-gradient work (cpc2_hip.h: cpc_gru_backward, cpc_lstm_backward, cpc_encoder_backward and
+cpc_transformer_backward with deferred = 1, + cpc_side_tail_join): the bookkeeping the autograd Functions of model.py / transformers.py share."""
 import os
 
 import torch
 
 from . import _lib
-from ._lib import check, stream_ptr
+from ._lib import check, device_index, stream_ptr
 
 # --------------------------------------------------------------------------- deferred parameter-gradient work
-# cpc_gru_backward_deferred / cpc_encoder_backward_deferred leave work that only finishes PARAMETER gradients on a stream of the
+# The backward entry points called with deferred = 1 leave work that only finishes PARAMETER gradients on a stream of the
 # library's, under the kernels the backward pass enqueues next.  Whoever reads those gradients sits behind join_tail(): the end of
 # the backward pass (autograd callback), DataParallelContext's all-reduces, FlatAdam.step.
 _tail = {}              # device index -> [tensors the side stream still uses, one tuple per deferred backward]
@@ -20,13 +20,13 @@ def join_tail(device):
     device = torch.device(device)
     if device.type != "cuda":
         return
-    idx = device.index if device.index is not None else torch.cuda.current_device()
+    idx = device_index(device)
     if _tail.pop(idx, None) is not None:
         check(_lib.load().cpc_side_tail_join(stream_ptr(device)), "side_tail_join")
 
 
 def _keep_for_tail(device, tensors):
-    idx = device.index if device.index is not None else torch.cuda.current_device()
+    idx = device_index(device)
     _tail.setdefault(idx, []).append(tensors)
     # one callback per deferred call (join_tail is idempotent): an entry left behind by a backward pass that raised must not keep
     # the next pass from queueing its own
@@ -36,7 +36,7 @@ def _keep_for_tail(device, tensors):
 def _tail_tag(name, device):
     """Scratch tag of a deferred backward call: distinct for every call that is pending on the device at the same time (the side
     stream still reads the earlier calls' buffers until the join empties the list)."""
-    idx = device.index if device.index is not None else torch.cuda.current_device()
+    idx = device_index(device)
     return (name, len(_tail.get(idx, ())))
 
 

@@ -239,7 +239,7 @@ class NegativeSampler:
             if aevents[aslot] is not None:
                 with _lib.host_wait("sampler_buffer_event"):
                     _sleep_until(aevents[aslot])
-            dev_index = device.index if device.index is not None else torch.cuda.current_device()
+            dev_index = _lib.device_index(device)
             ab, at, aw, ann = ashape
             if fixup is not None:
                 (mt, left, nxt), consumed = fixup
@@ -286,7 +286,7 @@ def _packed_view(tensors):
     return torch.as_strided(first, (k,) + tuple(first.shape), (first.numel(),) + tuple(first.stride()))
 
 
-# ---- the deferred backward (cpc2_hip.h, cpc_infonce_backward_deferred) --------------------------------------------------------
+# ---- the deferred backward (cpc2_hip.h, cpc_infonce_backward with deferred = 1) -----------------------------------------------
 # The criterion's dz and predictor weight gradients are produced on a stream of the library's while the context network's
 # backward runs; whoever consumes them has to sit behind join_deferred().  Nothing but the caller can promise that, so the
 # deferral is an EXPLICIT opt-in of the caller's, never something a tensor attribute switches on by travelling through
@@ -309,8 +309,7 @@ def join_deferred(device):
     device = torch.device(device)
     if device.type != "cuda":
         return
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    if _deferred.pop(idx, None) is not None:
+    if _deferred.pop(_lib.device_index(device), None) is not None:
         check(_lib.load().cpc_infonce_join(stream_ptr(device)), "infonce_join")
 
 
@@ -496,7 +495,6 @@ class _InfoNCEFn(torch.autograd.Function):
         # c holds the t frames of the sequence, or only the W = t - k the criterion uses (criterion.py:296: cFeature[:, :windowSize])
         if z.shape != (b, t, dim_enc) or wpred.shape[2] != dim_ar or tc not in (t, t - k):
             raise ValueError(f"shape mismatch c={tuple(c.shape)} z={tuple(z.shape)} W={tuple(wpred.shape)}")
-        ctx.cw = tc != t
         if ext_idx.dtype != torch.int32 or ext_idx.numel() != b * n_neg * (t - k):
             raise ValueError("ext_idx must be int32 [b, W, n_neg]")
         if weights is not None and weights.numel() != b * (t - k):
@@ -510,9 +508,8 @@ class _InfoNCEFn(torch.autograd.Function):
         acc = torch.empty(k, dtype=torch.float32, device=c.device)
         saved = torch.empty(nsaved, dtype=torch.uint8, device=c.device)
         sc = scratch(nscratch, c.device)
-        fwd = lib.cpc_infonce_forward_cw if ctx.cw else lib.cpc_infonce_forward
-        check(fwd(ptr(c), ptr(z), ptr(wpred), ptr(ext_idx), ptr(w), ptr(losses), ptr(acc),
-                  ptr(saved), ptr(sc), b, t, k, dim_ar, dim_enc, n_neg, stream_ptr(c.device)), "infonce_forward")
+        check(lib.cpc_infonce_forward(ptr(c), ptr(z), ptr(wpred), ptr(ext_idx), ptr(w), ptr(losses), ptr(acc),
+                                      ptr(saved), ptr(sc), b, t, tc, k, dim_ar, dim_enc, n_neg, stream_ptr(c.device)), "infonce_forward")
         ctx.save_for_backward(c, z, wpred, ext_idx, w, saved)
         ctx.param_refs = wk
         ctx.dims = (b, t, k, dim_ar, dim_enc, n_neg)
@@ -547,31 +544,17 @@ class _InfoNCEFn(torch.autograd.Function):
         nscratch = lib.cpc_infonce_scratch_bytes(b, t, k, dim_ar, dim_enc, n_neg)
         # (the weight gradients may only be late when nothing reads them before the end of the backward pass: written in place
         #  into the flat gradient buffer.  A private buffer is added to .grad by autograd as soon as this function returns.)
-        if defer and direct:
+        defer = defer and direct
+        if defer:
             join_deferred(c.device)            # (one pending backward per device)
-            sc = scratch(nscratch, c.device, tag="infonce_deferred")
-            if ctx.cw:
-                check(lib.cpc_infonce_backward_cw(ptr(c), ptr(z), ptr(wpred), ptr(ext_idx), ptr(w), ptr(dlosses), ptr(saved),
-                                                  ptr(sc), ptr(dc), ptr(dz), ptr(dw), b, t, k, dim_ar, dim_enc, n_neg, 1,
-                                                  stream_ptr(c.device)), "infonce_backward_cw")
-            else:
-                check(lib.cpc_infonce_backward_deferred(ptr(c), ptr(z), ptr(wpred), ptr(ext_idx), ptr(w), ptr(dlosses), ptr(saved),
-                                                        ptr(sc), ptr(dc), ptr(dz), ptr(dw), b, t, k, dim_ar, dim_enc, n_neg,
-                                                        stream_ptr(c.device)), "infonce_backward_deferred")
-            idx = c.device.index if c.device.index is not None else torch.cuda.current_device()
-            _deferred[idx] = (c, z, wpred, ext_idx, w, dlosses, saved, sc, dz_out, dw)
+        sc = scratch(nscratch, c.device, tag="infonce_deferred") if defer else scratch(nscratch, c.device)
+        check(lib.cpc_infonce_backward(ptr(c), ptr(z), ptr(wpred), ptr(ext_idx), ptr(w), ptr(dlosses), ptr(saved), ptr(sc), ptr(dc),
+                                       ptr(dz), ptr(dw), b, t, c.shape[1], k, dim_ar, dim_enc, n_neg, int(defer), stream_ptr(c.device)),
+              "infonce_backward")
+        if defer:
+            _deferred[_lib.device_index(c.device)] = (c, z, wpred, ext_idx, w, dlosses, saved, sc, dz_out, dw)
             device = c.device
             torch.autograd.Variable._execution_engine.queue_callback(lambda: join_deferred(device))
-        else:
-            sc = scratch(nscratch, c.device)
-            if ctx.cw:
-                check(lib.cpc_infonce_backward_cw(ptr(c), ptr(z), ptr(wpred), ptr(ext_idx), ptr(w), ptr(dlosses), ptr(saved),
-                                                  ptr(sc), ptr(dc), ptr(dz), ptr(dw), b, t, k, dim_ar, dim_enc, n_neg, 0,
-                                                  stream_ptr(c.device)), "infonce_backward_cw")
-            else:
-                check(lib.cpc_infonce_backward(ptr(c), ptr(z), ptr(wpred), ptr(ext_idx), ptr(w), ptr(dlosses), ptr(saved),
-                                               ptr(sc), ptr(dc), ptr(dz), ptr(dw), b, t, k, dim_ar, dim_enc, n_neg,
-                                               stream_ptr(c.device)), "infonce_backward")
         if not direct:
             gw = list(dw.unbind(0))
         return (dc, dz_out, None, None, None, None) + tuple(gw)
@@ -870,7 +853,7 @@ class CPCUnsupersivedCriterion(BaseCriterion):
                 c = f32c(cFeature)
                 wpred = torch.stack([f32c(p.weight.detach()) for p in self.wPrediction.predictors], dim=0)
                 check(lib.cpc_infonce_forward(ptr(c), ptr(z), ptr(wpred), ptr(extIdx), None, ptr(losses), ptr(acc), ptr(saved),
-                                              ptr(sc), b, t, k, dim_ar, dim_enc, n_neg, stream_ptr(z.device)), "infonce_forward")
+                                              ptr(sc), b, t, t, k, dim_ar, dim_enc, n_neg, stream_ptr(z.device)), "infonce_forward")
             else:
                 preds = [f32c(p) for p in preds]
                 check(lib.cpc_infonce_forward_pred(_lib.ptr_array(preds), ptr(z), ptr(extIdx), None, ptr(losses), ptr(acc),

@@ -226,14 +226,16 @@ int planes_tn_reduce(const float *slabs, int S, int M, int N, float *C, long ldc
 
 int gemm_mode();        // gemm_f32.hip: 0 exact bf16 split (six products), 1 f32 MFMA, 2 three products (opt-in, cpc_gemm_set_mode)
 
-// infonce.hip: start what a deferred criterion backward (cpc_infonce_backward_deferred) left to do, on the library's side
+// infonce.hip: start what a deferred criterion backward (cpc_infonce_backward, deferred != 0) left to do, on the library's side
 // stream, ordered behind what `st` holds now; no-op when nothing is pending.  Called by the context networks' backward entry
 // points right behind their first kernel.
 int infonce_deferred_mark(hipStream_t st);      // the point of `st` the side stream waits for (first call after the backward wins)
 int infonce_deferred_start(hipStream_t st);
-// work of a backward entry point that nothing on its stream needs (weight gradients): on the library's side stream, joined later
+// side_stream.hip: the library's one side stream per device (created on first use, apart from `caller`)
+int side_stream_get(hipStream_t caller, hipStream_t *out);
+// work of a backward entry point that nothing on its stream needs (weight gradients): on that stream, joined later
 int side_tail_begin(hipStream_t st, hipStream_t *side_stream);
-int side_tail_end();
+int side_tail_end();                      // CPC_ERR_INVALID unless a side_tail_begin has run on this device
 int side_tail_join(hipStream_t st);
 int side_tail_wait(hipStream_t st);       // `st` waits for the tail, which stays pending (a later side_tail_join still joins)
 // rowops.hip: a non-blocking stream of default priority that demonstrably runs BESIDE avoid[0 .. n) (not on their hardware queues)

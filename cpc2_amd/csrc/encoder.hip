@@ -1133,11 +1133,18 @@ static int enc_layout(EncLayout &e, int N, int length, int H, void *saved, void 
     return CPC_OK;
 }
 
-// x2 / n_first: windows n_first .. N - 1 come from x2 (nullptr: all N from x)
-static int encoder_forward(const float *x, const float *const *prm, float *z, void *saved, void *scratch, int N,
-                           int length, int H, float eps, hipStream_t st, const float *x2 = nullptr, int n_first = 0)
+// x2 / n_first: windows n_first .. N - 1 come from x2 (nullptr: all N from x, and n_first says so)
+static int enc_check_split(const float *x2, int n_first, int N)
 {
+    CPC_REQUIRE(x2 != nullptr || n_first == N, "encoder: one input batch holds all n_windows windows (n_first %d of %d)", n_first, N);
     CPC_REQUIRE(x2 == nullptr || (n_first > 0 && n_first < N), "encoder: the first batch must hold 1 .. n_windows - 1 windows (got %d of %d)", n_first, N);
+    return CPC_OK;
+}
+
+static int encoder_forward(const float *x, const float *x2, int n_first, const float *const *prm, float *z, void *saved, void *scratch,
+                           int N, int length, int H, float eps, hipStream_t st)
+{
+    CPC_TRY(enc_check_split(x2, n_first, N));
     EncLayout e;
     CPC_TRY(enc_layout(e, N, length, H, saved, scratch));
 
@@ -1242,11 +1249,10 @@ static int encoder_forward(const float *x, const float *const *prm, float *z, vo
 // defer_small: the passes of layers 1-4 that only produce parameter gradients from what a big kernel has left behind -- the two-stage
 // column sums of dgamma / dbeta / dbias and the sum of the weight-gradient product's K-split slabs, eight to ten launches of 5-10 us
 // that nothing on `st` needs -- run on the library's side stream (side_tail_*), each layer with buffers of its own
-static int encoder_backward(const float *x, const float *const *prm, const float *dz, void *saved, void *scratch,
-                            float *const *grads, int N, int length, int H, float eps, hipStream_t st, bool defer_small = false,
-                            const float *x2 = nullptr, int n_first = 0)
+static int encoder_backward(const float *x, const float *x2, int n_first, const float *const *prm, const float *dz, void *saved,
+                            void *scratch, float *const *grads, int N, int length, int H, float eps, bool defer_small, hipStream_t st)
 {
-    CPC_REQUIRE(x2 == nullptr || (n_first > 0 && n_first < N), "encoder: the first batch must hold 1 .. n_windows - 1 windows (got %d of %d)", n_first, N);
+    CPC_TRY(enc_check_split(x2, n_first, N));
     // the forward pass takes every length that leaves a frame (feature extraction, under no_grad).  The backward is verified from 400
     // samples on; below, the plane-fed weight-gradient product (gemm_tn_planes: >= 64 reduction rows, N (L_out + 2) of conv4) would
     // refuse one- and two-frame inputs half-way through unless 16-22 windows came together -- refused here, by name, before any launch
@@ -1423,36 +1429,17 @@ extern "C" int cpc_encoder_saved_layout(int n_windows, int length, int hidden, i
     return CPC_OK;
 }
 
-extern "C" int cpc_encoder_forward(const float *x, const float *const *params, float *z, void *saved, void *scratch,
-                                   int n_windows, int length, int hidden, float eps, cpc_stream_t stream)
+extern "C" int cpc_encoder_forward(const float *x_first, const float *x_rest, int n_first, const float *const *params, float *z, void *saved,
+                                   void *scratch, int n_windows, int length, int hidden, float eps, cpc_stream_t stream)
 {
-    return cpc::encoder_forward(x, params, z, saved, scratch, n_windows, length, hidden, eps, static_cast<hipStream_t>(stream));
+    return cpc::encoder_forward(x_first, x_rest, n_first, params, z, saved, scratch, n_windows, length, hidden, eps,
+                                static_cast<hipStream_t>(stream));
 }
 
-extern "C" int cpc_encoder_backward(const float *x, const float *const *params, const float *dz, void *saved, void *scratch,
-                                    float *const *grads, int n_windows, int length, int hidden, float eps, cpc_stream_t stream)
+extern "C" int cpc_encoder_backward(const float *x_first, const float *x_rest, int n_first, const float *const *params, const float *dz,
+                                    void *saved, void *scratch, float *const *grads, int n_windows, int length, int hidden, float eps,
+                                    int deferred, cpc_stream_t stream)
 {
-    return cpc::encoder_backward(x, params, dz, saved, scratch, grads, n_windows, length, hidden, eps,
-                                 static_cast<hipStream_t>(stream));
-}
-
-extern "C" int cpc_encoder_forward2(const float *x_first, const float *x_rest, int n_first, const float *const *params, float *z, void *saved,
-                                    void *scratch, int n_windows, int length, int hidden, float eps, cpc_stream_t stream)
-{
-    return cpc::encoder_forward(x_first, params, z, saved, scratch, n_windows, length, hidden, eps, static_cast<hipStream_t>(stream), x_rest, n_first);
-}
-
-extern "C" int cpc_encoder_backward2(const float *x_first, const float *x_rest, int n_first, const float *const *params, const float *dz,
-                                     void *saved, void *scratch, float *const *grads, int n_windows, int length, int hidden, float eps,
-                                     int deferred, cpc_stream_t stream)
-{
-    return cpc::encoder_backward(x_first, params, dz, saved, scratch, grads, n_windows, length, hidden, eps,
-                                 static_cast<hipStream_t>(stream), deferred != 0, x_rest, n_first);
-}
-
-extern "C" int cpc_encoder_backward_deferred(const float *x, const float *const *params, const float *dz, void *saved, void *scratch,
-                                             float *const *grads, int n_windows, int length, int hidden, float eps, cpc_stream_t stream)
-{
-    return cpc::encoder_backward(x, params, dz, saved, scratch, grads, n_windows, length, hidden, eps,
-                                 static_cast<hipStream_t>(stream), true);
+    return cpc::encoder_backward(x_first, x_rest, n_first, params, dz, saved, scratch, grads, n_windows, length, hidden, eps,
+                                 deferred != 0, static_cast<hipStream_t>(stream));
 }

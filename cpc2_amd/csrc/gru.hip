@@ -951,25 +951,11 @@ extern "C" int cpc_gru_forward(const float *x, const float *const *params, const
 }
 
 extern "C" int cpc_gru_backward(const float *x, const float *const *params, const float *dout, void *saved, void *scratch,
-                                float *dx, float *const *grads, int n, int t, int dim_in, int hidden, int layers,
+                                float *dx, float *const *grads, int n, int t, int dim_in, int hidden, int layers, int deferred,
                                 cpc_stream_t stream)
 {
     cpc::coop_count_backward_call();
     CPC_TRY(cpc::coop_error_take("cpc_gru_backward"));      // a time-out of an earlier cooperative launch surfaces here
     return cpc::rec_backward<GruCell>(x, params, dout, saved, scratch, dx, grads, n, t, dim_in, hidden, layers,
-                                      static_cast<hipStream_t>(stream), false);
+                                      static_cast<hipStream_t>(stream), deferred != 0);
 }
-
-extern "C" int cpc_gru_backward_deferred(const float *x, const float *const *params, const float *dout, void *saved, void *scratch,
-                                         float *dx, float *const *grads, int n, int t, int dim_in, int hidden, int layers,
-                                         cpc_stream_t stream)
-{
-    cpc::coop_count_backward_call();
-    CPC_TRY(cpc::coop_error_take("cpc_gru_backward_deferred"));
-    return cpc::rec_backward<GruCell>(x, params, dout, saved, scratch, dx, grads, n, t, dim_in, hidden, layers,
-                                      static_cast<hipStream_t>(stream), true);
-}
-
-
-extern "C" int cpc_side_tail_join(cpc_stream_t stream) { return cpc::side_tail_join(static_cast<hipStream_t>(stream)); }
-extern "C" int cpc_side_tail_wait(cpc_stream_t stream) { return cpc::side_tail_wait(static_cast<hipStream_t>(stream)); }

@@ -1127,16 +1127,15 @@ static int nce_launch_fwd(NceArgs &a, const NceLayout &l, float *losses, float *
 }
 
 // The reference lists depend on the indices only, the kernels before the gather do not need them: they are built
-// on a stream of the library's own (one per device, created on first use), forked from and joined to the caller's
-// stream with events -- no host synchronisation, and nothing of it outlives the call on the caller's stream.
+// on the library's side stream (side_stream.hip: one per device, shared with the side_tail_* work of the other backward
+// entry points), forked from and joined to the caller's stream with events -- no host synchronisation, and nothing of it
+// outlives the call on the caller's stream.
 struct NceSide {
-    hipStream_t stream = nullptr;
+    hipStream_t stream = nullptr;       // side_stream_get's: the criterion owns only the events and the state below
     hipEvent_t fork = nullptr, join = nullptr;
-    // deferred form of the backward (cpc_infonce_backward_deferred): `mid` = the fused backward kernel has run on the caller's
+    // deferred form of the backward (cpc_infonce_backward, deferred != 0): `mid` = the fused backward kernel has run on the caller's
     // stream, `late` = dz and the predictor weight gradients are complete on the side stream; `pending` until cpc_infonce_join
     hipEvent_t mid = nullptr, late = nullptr;
-    hipEvent_t tail_fork = nullptr, tail = nullptr;     // side_tail_*: work of another backward entry point finishing on this stream
-    bool tail_pending = false;
     std::atomic<bool> pending{false};
     // what is left to launch of the pending backward (infonce_deferred_start): it is started by the NEXT backward entry point
     // called on the caller's stream (the context network's, right behind its first kernel) or, failing that, by the join
@@ -1155,17 +1154,11 @@ static int nce_side(NceSide **out, hipStream_t caller)
     std::lock_guard<std::mutex> lk(mu);
     NceSide &sd = sides[dev];
     if (sd.stream == nullptr) {
-        // DEFAULT priority, deliberately.  A lowest-priority stream looked right for work that runs beside the caller's, and costs
-        // nothing in a single-process run -- but in a process that has also initialised RCCL every kernel of the step ran ~45 %
-        // slower (7.7 against 5.3 ms per step with one rank; found by bisection, profiles/r03_dist_priority_bisect.txt).
-        // ... and on a hardware queue of its own: tested against the caller's stream (stream_create_apart, rowops.hip)
-        CPC_TRY(stream_create_apart(&caller, 1, &sd.stream));
+        CPC_TRY(side_stream_get(caller, &sd.stream));
         CPC_CHECK_HIP(hipEventCreateWithFlags(&sd.fork, hipEventDisableTiming));
         CPC_CHECK_HIP(hipEventCreateWithFlags(&sd.join, hipEventDisableTiming));
         CPC_CHECK_HIP(hipEventCreateWithFlags(&sd.mid, hipEventDisableTiming));
         CPC_CHECK_HIP(hipEventCreateWithFlags(&sd.late, hipEventDisableTiming));
-        CPC_CHECK_HIP(hipEventCreateWithFlags(&sd.tail_fork, hipEventDisableTiming));
-        CPC_CHECK_HIP(hipEventCreateWithFlags(&sd.tail, hipEventDisableTiming));
     }
     *out = &sd;
     return CPC_OK;
@@ -1250,14 +1243,12 @@ static int nce_launch_bwd(NceArgs &a, const NceLayout &l, float *dz, hipStream_t
 // that slice (cpcStep: the context network then only runs the W steps whose output is used)
 static int infonce_forward(const float *c, const float *z, const float *wpred, const int32_t *ext, const float *weights,
                            float *losses, float *acc, void *saved, void *scratch, int b, int T, int K, int Har, int Henc,
-                           int Nneg, hipStream_t st, int c_frames = 0)
+                           int Nneg, int c_frames, hipStream_t st)
 {
     NceLayout l;
     CPC_TRY(nce_layout(l, b, T, K, Har, Henc, Nneg, saved, scratch));
-    if (c_frames != 0) {
-        CPC_REQUIRE(c_frames == T || c_frames == l.W, "infonce: the context holds %d frames per window (expected %d or %d)", c_frames, T, l.W);
-        l.Pr = c_frames;
-    }
+    CPC_REQUIRE(c_frames == T || c_frames == l.W, "infonce: the context holds %d frames per window (expected %d or %d)", c_frames, T, l.W);
+    l.Pr = c_frames;
     RowMap none{};
     // all K predictors in one GEMM: P[(b,t)][k*Henc + e] = sum_a c[b,t,a] * W_k[e][a]     (criterion.py:163)
     CPC_TRY(gemm_nt(c, Har, wpred, Har, l.P, (long)K * Henc, nullptr, (long)b * l.Pr, K * Henc, Har, none, st));
@@ -1272,14 +1263,12 @@ static int infonce_forward(const float *c, const float *z, const float *wpred, c
 
 static int infonce_backward(const float *c, const float *z, const float *wpred, const int32_t *ext, const float *weights,
                             const float *dlosses, void *saved, void *scratch, float *dc, float *dz, float *dwpred, int b, int T,
-                            int K, int Har, int Henc, int Nneg, hipStream_t st, bool defer, int c_frames = 0)
+                            int K, int Har, int Henc, int Nneg, int c_frames, bool defer, hipStream_t st)
 {
     NceLayout l;
     CPC_TRY(nce_layout(l, b, T, K, Har, Henc, Nneg, saved, scratch));
-    if (c_frames != 0) {
-        CPC_REQUIRE(c_frames == T || c_frames == l.W, "infonce: the context holds %d frames per window (expected %d or %d)", c_frames, T, l.W);
-        l.Pr = c_frames;
-    }
+    CPC_REQUIRE(c_frames == T || c_frames == l.W, "infonce: the context holds %d frames per window (expected %d or %d)", c_frames, T, l.W);
+    l.Pr = c_frames;
     NceArgs a{};
     nce_common(a, l, z, ext, weights);
     for (int k = 0; k < K; ++k) { a.Pk[k] = l.P + (size_t)k * Henc; a.dPk[k] = l.dP + (size_t)k * Henc; }
@@ -1335,55 +1324,6 @@ int infonce_deferred_start(hipStream_t st)
                     0, side->stream));
     CPC_CHECK_HIP(hipEventRecord(side->late, side->stream));
     side->started = true;
-    return CPC_OK;
-}
-
-// ---- "tail" work of a backward entry point on the library's side stream: ordered behind what `st` holds now (and behind whatever
-// the side stream already has queued); whoever reads its results waits at side_tail_join
-int side_tail_begin(hipStream_t st, hipStream_t *side_stream)
-{
-    NceSide *side = nullptr;
-    CPC_TRY(nce_side(&side, st));
-    CPC_CHECK_HIP(hipEventRecord(side->tail_fork, st));
-    CPC_CHECK_HIP(hipStreamWaitEvent(side->stream, side->tail_fork, 0));
-    *side_stream = side->stream;
-    return CPC_OK;
-}
-int side_tail_end()
-{
-    NceSide *side = nullptr;
-    CPC_TRY(nce_side(&side, nullptr));
-    CPC_CHECK_HIP(hipEventRecord(side->tail, side->stream));
-    side->tail_pending = true;
-    return CPC_OK;
-}
-int side_tail_join(hipStream_t st)
-{
-    NceSide *side = nullptr;
-    CPC_TRY(nce_side(&side, st));
-    if (side->tail_pending) {
-        ProfScope held(PROF_SIDE_WAIT, st);          // (bench.py: how long `st` stands still here)
-        CPC_CHECK_HIP(hipStreamWaitEvent(st, side->tail, 0));
-        side->tail_pending = false;
-    }
-    return CPC_OK;
-}
-
-int side_stream_peek(hipStream_t caller, hipStream_t *out)
-{
-    NceSide *side = nullptr;
-    CPC_TRY(nce_side(&side, caller));
-    *out = side->stream;
-    return CPC_OK;
-}
-
-// the same wait WITHOUT taking the tail off the books: a helper stream (the data-parallel exchange's) orders itself behind the tail
-// while the caller's stream goes on; whoever reuses the tail's buffers still joins with side_tail_join
-int side_tail_wait(hipStream_t st)
-{
-    NceSide *side = nullptr;
-    CPC_TRY(nce_side(&side, st));
-    if (side->tail_pending) CPC_CHECK_HIP(hipStreamWaitEvent(st, side->tail, 0));
     return CPC_OK;
 }
 
@@ -1477,55 +1417,22 @@ extern "C" size_t cpc_infonce_scratch_bytes(int b, int t, int k, int dim_ar, int
 }
 
 extern "C" int cpc_infonce_forward(const float *c, const float *z, const float *wpred, const int32_t *ext_idx, const float *weights,
-                                   float *losses, float *acc, void *saved, void *scratch, int b, int t, int k, int dim_ar,
+                                   float *losses, float *acc, void *saved, void *scratch, int b, int t, int c_frames, int k, int dim_ar,
                                    int dim_enc, int n_neg, cpc_stream_t stream)
 {
-    return cpc::infonce_forward(c, z, wpred, ext_idx, weights, losses, acc, saved, scratch, b, t, k, dim_ar, dim_enc, n_neg,
+    return cpc::infonce_forward(c, z, wpred, ext_idx, weights, losses, acc, saved, scratch, b, t, k, dim_ar, dim_enc, n_neg, c_frames,
                                 static_cast<hipStream_t>(stream));
 }
 
 extern "C" int cpc_infonce_backward(const float *c, const float *z, const float *wpred, const int32_t *ext_idx, const float *weights,
                                     const float *dlosses, void *saved, void *scratch, float *dc, float *dz, float *dwpred, int b,
-                                    int t, int k, int dim_ar, int dim_enc, int n_neg, cpc_stream_t stream)
+                                    int t, int c_frames, int k, int dim_ar, int dim_enc, int n_neg, int deferred, cpc_stream_t stream)
 {
     return cpc::infonce_backward(c, z, wpred, ext_idx, weights, dlosses, saved, scratch, dc, dz, dwpred, b, t, k, dim_ar, dim_enc,
-                                 n_neg, static_cast<hipStream_t>(stream), false);
-}
-
-extern "C" int cpc_infonce_backward_deferred(const float *c, const float *z, const float *wpred, const int32_t *ext_idx,
-                                             const float *weights, const float *dlosses, void *saved, void *scratch, float *dc,
-                                             float *dz, float *dwpred, int b, int t, int k, int dim_ar, int dim_enc, int n_neg,
-                                             cpc_stream_t stream)
-{
-    return cpc::infonce_backward(c, z, wpred, ext_idx, weights, dlosses, saved, scratch, dc, dz, dwpred, b, t, k, dim_ar, dim_enc,
-                                 n_neg, static_cast<hipStream_t>(stream), true);
-}
-
-extern "C" int cpc_infonce_forward_cw(const float *c, const float *z, const float *wpred, const int32_t *ext_idx, const float *weights,
-                                      float *losses, float *acc, void *saved, void *scratch, int b, int t, int k, int dim_ar,
-                                      int dim_enc, int n_neg, cpc_stream_t stream)
-{
-    return cpc::infonce_forward(c, z, wpred, ext_idx, weights, losses, acc, saved, scratch, b, t, k, dim_ar, dim_enc, n_neg,
-                                static_cast<hipStream_t>(stream), t - k);
-}
-
-extern "C" int cpc_infonce_backward_cw(const float *c, const float *z, const float *wpred, const int32_t *ext_idx, const float *weights,
-                                       const float *dlosses, void *saved, void *scratch, float *dc, float *dz, float *dwpred, int b,
-                                       int t, int k, int dim_ar, int dim_enc, int n_neg, int deferred, cpc_stream_t stream)
-{
-    return cpc::infonce_backward(c, z, wpred, ext_idx, weights, dlosses, saved, scratch, dc, dz, dwpred, b, t, k, dim_ar, dim_enc,
-                                 n_neg, static_cast<hipStream_t>(stream), deferred != 0, t - k);
+                                 n_neg, c_frames, deferred != 0, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int cpc_infonce_join(cpc_stream_t stream) { return cpc::infonce_join(static_cast<hipStream_t>(stream)); }
-extern "C" int cpc_side_stream(cpc_stream_t caller, cpc_stream_t *out)
-{
-    CPC_REQUIRE(out != nullptr, "cpc_side_stream: null output");
-    hipStream_t st = nullptr;
-    CPC_TRY(cpc::side_stream_peek(static_cast<hipStream_t>(caller), &st));
-    *out = st;
-    return CPC_OK;
-}
 
 extern "C" int cpc_infonce_forward_pred(const float *const *pred, const float *z, const int32_t *ext_idx, const float *weights,
                                         float *losses, float *acc, void *saved, void *scratch, int b, int t, int k, int dim_enc,

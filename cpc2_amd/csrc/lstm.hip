@@ -576,23 +576,13 @@ extern "C" int cpc_lstm_forward(const float *x, const float *const *params, cons
 }
 
 extern "C" int cpc_lstm_backward(const float *x, const float *const *params, const float *dout, void *saved, void *scratch,
-                                 float *dx, float *const *grads, int n, int t, int dim_in, int hidden, int layers,
+                                 float *dx, float *const *grads, int n, int t, int dim_in, int hidden, int layers, int deferred,
                                  cpc_stream_t stream)
 {
     cpc::coop_count_backward_call();
     CPC_TRY(cpc::coop_error_take("cpc_lstm_backward"));      // a time-out of an earlier cooperative launch surfaces here
     return cpc::rec_backward<LstmCell<4>>(x, params, dout, saved, scratch, dx, grads, n, t, dim_in, hidden, layers,
-                                          static_cast<hipStream_t>(stream), false);
-}
-
-extern "C" int cpc_lstm_backward_deferred(const float *x, const float *const *params, const float *dout, void *saved, void *scratch,
-                                          float *dx, float *const *grads, int n, int t, int dim_in, int hidden, int layers,
-                                          cpc_stream_t stream)
-{
-    cpc::coop_count_backward_call();
-    CPC_TRY(cpc::coop_error_take("cpc_lstm_backward_deferred"));
-    return cpc::rec_backward<LstmCell<4>>(x, params, dout, saved, scratch, dx, grads, n, t, dim_in, hidden, layers,
-                                          static_cast<hipStream_t>(stream), true);
+                                          static_cast<hipStream_t>(stream), deferred != 0);
 }
 
 extern "C" size_t cpc_rnn_saved_bytes(int n, int t, int dim_in, int hidden, int layers)
@@ -615,9 +605,10 @@ extern "C" int cpc_rnn_forward(const float *x, const float *const *params, const
 }
 
 extern "C" int cpc_rnn_backward(const float *x, const float *const *params, const float *dout, void *saved, void *scratch,
-                                float *dx, float *const *grads, int n, int t, int dim_in, int hidden, int layers,
+                                float *dx, float *const *grads, int n, int t, int dim_in, int hidden, int layers, int deferred,
                                 cpc_stream_t stream)
 {
+    CPC_REQUIRE(deferred == 0, "cpc_rnn_backward: the RNN cell has no deferred form (deferred = %d)", deferred);
     cpc::coop_count_backward_call();
     CPC_TRY(cpc::coop_error_take("cpc_rnn_backward"));      // a time-out of an earlier cooperative launch surfaces here
     return cpc::rec_backward<LstmCell<1>>(x, params, dout, saved, scratch, dx, grads, n, t, dim_in, hidden, layers,

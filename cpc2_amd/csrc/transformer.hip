@@ -1063,7 +1063,7 @@ static int transformer_forward(const float *x, const float *const *prm, float *o
 
 static int transformer_backward(const float *x, const float *const *prm, const float *dout, void *saved, void *scratch, float *dx,
                                 float *const *grads, int N, int S, int D, int Dout, int SS, int layers, int nc, float p_drop,
-                                uint64_t seed, hipStream_t st, bool defer_tail = false)
+                                uint64_t seed, bool defer_tail, hipStream_t st)
 {
     TrLayout L;
     CPC_TRY(tr_layout(L, N, S, D, Dout, SS, layers, nc, saved, scratch));
@@ -1221,17 +1221,9 @@ extern "C" int cpc_transformer_forward(const float *x, const float *const *param
 
 extern "C" int cpc_transformer_backward(const float *x, const float *const *params, const float *dout, void *saved, void *scratch,
                                         float *dx, float *const *grads, int n, int s, int d_model, int d_out, int size_seq,
-                                        int layers, int n_classifiers, float dropout_p, unsigned long long seed, cpc_stream_t stream)
+                                        int layers, int n_classifiers, float dropout_p, unsigned long long seed, int deferred,
+                                        cpc_stream_t stream)
 {
     return cpc::transformer_backward(x, params, dout, saved, scratch, dx, grads, n, s, d_model, d_out, size_seq, layers, n_classifiers, dropout_p,
-                                     seed, static_cast<hipStream_t>(stream));
-}
-
-extern "C" int cpc_transformer_backward_deferred(const float *x, const float *const *params, const float *dout, void *saved, void *scratch,
-                                                 float *dx, float *const *grads, int n, int s, int d_model, int d_out, int size_seq,
-                                                 int layers, int n_classifiers, float dropout_p, unsigned long long seed,
-                                                 cpc_stream_t stream)
-{
-    return cpc::transformer_backward(x, params, dout, saved, scratch, dx, grads, n, s, d_model, d_out, size_seq, layers, n_classifiers, dropout_p,
-                                     seed, static_cast<hipStream_t>(stream), true);
+                                     seed, deferred != 0, static_cast<hipStream_t>(stream));
 }

@@ -83,7 +83,7 @@ _ENC_GEOMETRY = ((10, 5, 3), (8, 4, 2), (4, 2, 1), (4, 2, 1), (4, 2, 1))
 
 class _EncoderFn(torch.autograd.Function):
     """relu(norm_i(conv_i(.))) x5 in one call; returns the channel-LAST output [N, T, H].  x2: None, or a second batch of
-    windows that follows x (cpc_encoder_forward2: train.py:99's cat([past, future]) without the copy)."""
+    windows that follows x (cpc_encoder_forward's x_rest: train.py:99's cat([past, future]) without the copy)."""
 
     @staticmethod
     def forward(ctx, x, x2, eps, defer_tail, *params):
@@ -107,12 +107,8 @@ class _EncoderFn(torch.autograd.Function):
         z = torch.empty(n, frames, hidden, dtype=torch.float32, device=x.device)
         saved = torch.empty(nsaved, dtype=torch.uint8, device=x.device)
         sc = scratch(nscratch, x.device)
-        if x2 is None:
-            check(lib.cpc_encoder_forward(ptr(x), ptr_array(params), ptr(z), ptr(saved), ptr(sc), n, length, hidden,
-                                          eps, stream_ptr(x.device)), "encoder_forward")
-        else:
-            check(lib.cpc_encoder_forward2(ptr(x), ptr(x2), n_first, ptr_array(params), ptr(z), ptr(saved), ptr(sc), n, length, hidden,
-                                           eps, stream_ptr(x.device)), "encoder_forward2")
+        check(lib.cpc_encoder_forward(ptr(x), ptr(x2), n_first, ptr_array(params), ptr(z), ptr(saved), ptr(sc), n, length, hidden,
+                                      eps, stream_ptr(x.device)), "encoder_forward")
         ctx.save_for_backward(x, x2, saved, *params)
         ctx.eps = eps
         ctx.dims = (n, length, hidden, n_first)
@@ -131,15 +127,8 @@ class _EncoderFn(torch.autograd.Function):
         defer = ctx.defer_tail and _all_in_place(ctx.param_refs[4:], grads[4:])
         # (deferred: a scratch buffer of its own -- the side stream outlives this call)
         sc = scratch(nscratch, x.device, tag=_tail_tag("enc_tail", x.device)) if defer else scratch(nscratch, x.device)
-        if x2 is not None:
-            check(lib.cpc_encoder_backward2(ptr(x), ptr(x2), n_first, ptr_array(params), ptr(dz), ptr(saved), ptr(sc), ptr_array(grads),
-                                            n, length, hidden, ctx.eps, int(defer), stream_ptr(x.device)), "encoder_backward2")
-        elif defer:
-            check(lib.cpc_encoder_backward_deferred(ptr(x), ptr_array(params), ptr(dz), ptr(saved), ptr(sc), ptr_array(grads),
-                                                    n, length, hidden, ctx.eps, stream_ptr(x.device)), "encoder_backward_deferred")
-        else:
-            check(lib.cpc_encoder_backward(ptr(x), ptr_array(params), ptr(dz), ptr(saved), ptr(sc), ptr_array(grads),
-                                           n, length, hidden, ctx.eps, stream_ptr(x.device)), "encoder_backward")
+        check(lib.cpc_encoder_backward(ptr(x), ptr(x2), n_first, ptr_array(params), ptr(dz), ptr(saved), ptr(sc), ptr_array(grads),
+                                       n, length, hidden, ctx.eps, int(defer), stream_ptr(x.device)), "encoder_backward")
         if defer:
             _keep_for_tail(x.device, (x, x2, saved, params, dz, sc))  # (not `grads`: see _RecurrentFn.backward)
         return (None, None, None, None) + tuple(grads)
@@ -171,7 +160,7 @@ class CPCEncoder(nn.Module):
 
     def deferred_weight_gradients(self):
         """Context manager around the FORWARD call (see _TailScope): the backward of a forward pass made inside may leave the small
-        passes that finish conv1-4's parameter gradients on the library's side stream (cpc_encoder_backward_deferred)."""
+        passes that finish conv1-4's parameter gradients on the library's side stream (cpc_encoder_backward, deferred = 1)."""
         return _TailScope(self)
 
     def _param_list(self):
@@ -205,7 +194,7 @@ class _RecurrentFn(torch.autograd.Function):
         x = f32c(x)
         ctx.param_refs = params
         ctx.kind = kind
-        ctx.defer_tail = bool(defer_tail) and kind != "rnn"        # (there is no cpc_rnn_backward_deferred)
+        ctx.defer_tail = bool(defer_tail) and kind != "rnn"        # (cpc_rnn_backward has no deferred form)
         params = tuple(f32c(p) for p in params)
         n, t, dim_in = x.shape
         hidden = params[1].shape[1]
@@ -239,18 +228,17 @@ class _RecurrentFn(torch.autograd.Function):
         dx = grad_home_view(ctx.dx_home, x) if need_dx else None
         grads = grad_buffers(ctx.param_refs)
         kind = ctx.kind
-        # The deferred form (cpc2_hip.h, cpc_gru_backward_deferred / cpc_lstm_backward_deferred): every layer's weight gradients finish
+        # The deferred form (cpc2_hip.h, cpc_gru_backward / cpc_lstm_backward with deferred = 1): every layer's weight gradients finish
         # on a stream of the library's while the encoder's backward runs.  Only inside the caller's scope
         # (CPCAR.deferred_weight_gradients: nothing reads these gradients before the backward pass has ended) and only when every
         # one of them is written IN PLACE into the flat gradient buffer -- a private buffer would be added to .grad by autograd the
         # moment this function returns.
         defer = ctx.defer_tail and _all_in_place(ctx.param_refs, grads)
-        entry = f"{kind}_backward_deferred" if defer else f"{kind}_backward"
         nscratch = getattr(lib, f"cpc_{kind}_scratch_bytes")(n, t, dim_in, hidden, n_layers)
         # (deferred: a buffer of its own -- the side stream outlives this call)
         sc = scratch(nscratch, x.device, tag=_tail_tag(f"{kind}_tail", x.device)) if defer else scratch(nscratch, x.device)
-        check(getattr(lib, f"cpc_{entry}")(ptr(x), ptr_array(params), ptr(dout), ptr(saved), ptr(sc), ptr(dx), ptr_array(grads),
-                                           n, t, dim_in, hidden, n_layers, stream_ptr(x.device)), entry)
+        check(getattr(lib, f"cpc_{kind}_backward")(ptr(x), ptr_array(params), ptr(dout), ptr(saved), ptr(sc), ptr(dx), ptr_array(grads),
+                                                   n, t, dim_in, hidden, n_layers, int(defer), stream_ptr(x.device)), f"{kind}_backward")
         if defer:
             # alive until the join.  NOT `grads`: autograd adopts a returned gradient as .grad only while nobody else holds it -- with a
             # second reference it CLONES it on the spot (the flat buffer's not yet written bytes) and the clone becomes .grad
@@ -276,7 +264,7 @@ class CPCAR(nn.Module):
 
     def deferred_weight_gradients(self):
         """Context manager around the FORWARD call: the backward of a forward pass made inside may leave layer 0's weight gradients
-        on the library's side stream until the end of the backward pass (cpc_gru_backward_deferred).  The caller promises that
+        on the library's side stream until the end of the backward pass (cpc_gru_backward, deferred = 1).  The caller promises that
         nothing reads those gradients earlier -- no wrapper whose reducer copies a gradient the moment autograd has accumulated it
         (DistributedDataParallel / DataParallel around the model), no tensor hook on them; cpcStep opens it for the bare model."""
         return _TailScope(self)

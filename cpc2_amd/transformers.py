@@ -108,20 +108,15 @@ class _TransformerFn(torch.autograd.Function):
         l0 = [(p, g) for p, g in zip(ctx.param_refs[:per], grads[:per]) if p is not None]
         # the deferred form (cpc2_hip.h): inside the caller's scope (TransformerLayer.deferred_weight_gradients) and with every
         # gradient of layer 0 written in place into the flat gradient buffer (model.py, _RecurrentFn.backward)
-        if ctx.defer_tail and _all_in_place([p for p, _g in l0], [g for _p, g in l0]):
-            # a buffer of its own, and one PER PENDING CALL: the side stream reads it after this call has returned, and a second
-            # TransformerLayer of the same context network (nLevelsGRU >= 2) runs its backward before the join
-            sc = scratch(nscratch, x.device, tag=_tail_tag("tr_tail", x.device))
-            check(lib.cpc_transformer_backward_deferred(ptr(x), ptr_array(params), ptr(dout), ptr(saved), ptr(sc), ptr(dx),
-                                                        ptr_array(grads), n, s, d_model, d_out, size_seq, n_layers, n_classifiers,
-                                                        dropout_p, seed, stream_ptr(x.device)), "transformer_backward_deferred")
+        defer = ctx.defer_tail and _all_in_place([p for p, _g in l0], [g for _p, g in l0])
+        # (deferred: a buffer of its own, and one PER PENDING CALL: the side stream reads it after this call has returned, and a
+        #  second TransformerLayer of the same context network (nLevelsGRU >= 2) runs its backward before the join)
+        sc = scratch(nscratch, x.device, tag=_tail_tag("tr_tail", x.device)) if defer else scratch(nscratch, x.device)
+        check(lib.cpc_transformer_backward(ptr(x), ptr_array(params), ptr(dout), ptr(saved), ptr(sc), ptr(dx), ptr_array(grads),
+                                           n, s, d_model, d_out, size_seq, n_layers, n_classifiers, dropout_p, seed, int(defer),
+                                           stream_ptr(x.device)), "transformer_backward")
+        if defer:
             _keep_for_tail(x.device, (x, saved, params, dout, sc))
-        else:
-            sc = scratch(nscratch, x.device)
-            check(lib.cpc_transformer_backward(ptr(x), ptr_array(params), ptr(dout), ptr(saved), ptr(sc), ptr(dx), ptr_array(grads),
-                                               n, s, d_model, d_out, size_seq, n_layers, n_classifiers, dropout_p, seed,
-                                               stream_ptr(x.device)),
-                  "transformer_backward")
         return (dx, None, None, None, None, None, None) + tuple(grads)
 
 

@@ -41,12 +41,13 @@ enum cpc_status {
     CPC_ERR_WORKSPACE = -3 /* workspace / scratch too small */
 };
 
-int cpc_version(void);          /* 100 x major + minor; 105 = the entry points of round 5 (cpc_encoder_forward2 / backward2, cpc_coop_set_policy,
+int cpc_version(void);          /* 100 x major + minor; 105 = the entry points of round 5 (cpc_coop_set_policy,
                                   * cpc_recurrent_backward_calls, cpc_side_tail_wait); 107 = cpc_abx_dtw / cpc_abx_counts;
                                   * 108 = cpc_kmeans_scratch_bytes / cpc_kmeans_assign / cpc_kmeans_distances / cpc_kmeans_accumulate;
                                   * 109 = cpc_probe_xent / cpc_probe_head_backward / cpc_probe_ctc / cpc_probe_collapse (+ scratch queries);
                                   * 110 = cpc_abx_dtw_units (+ scratch query); 111 = cpc_augment_*; 112 = cpc_resample_*;
-                                  * 113 = cpc_text_* */
+                                  * 113 = cpc_text_*;
+                                  * 114 = one forward and one backward entry point per op: x_rest / n_first, c_frames, `deferred` */
 const char *cpc_last_error(void);
 
 /* In-situ kernel timing for bench.py: when enabled, the launchers bracket each launch of the named
@@ -86,7 +87,7 @@ long cpc_coop_launches(void);
 /* Granule buffers the cooperative kernels' launches hold right now: one per (device, stream) that launched one lately, at most
  * eight -- the one unused for longest is freed when a ninth stream comes (diagnostics / tests). */
 int cpc_coop_comm_buffers(void);
-/* Calls of the recurrent backward entry points (cpc_gru_backward*, cpc_lstm_backward*, cpc_rnn_backward; cooperative or streaming
+/* Calls of the recurrent backward entry points (cpc_gru_backward, cpc_lstm_backward, cpc_rnn_backward; cooperative or streaming
  * kernels alike) by this process so far: what "the recurrent backward of this step has been issued" is decided by. */
 long cpc_recurrent_backward_calls(void);
 /* Process-wide policy for those kernels: 0 (default) = cooperative wherever they fit, 1 = the streaming (non-cooperative) kernels
@@ -168,7 +169,10 @@ int cpc_channelnorm_backward(const float *x, const float *w, const float *dy, co
 /* ------------------------------------------------------------------------------------------
  * CPCEncoder (model.py:63-108): five strided Conv1d (k,s,p) = (10,5,3),(8,4,2),(4,2,1)x3, each
  * followed by ChannelNorm (model.py:52-60) and ReLU.
- *   x        [n_windows, 1, length]                     raw waveform
+ *   x_first  [n_first, 1, length]                       raw waveform: windows 0 .. n_first - 1
+ *   x_rest   [n_windows - n_first, 1, length] or NULL   windows n_first .. n_windows - 1 -- TWO input batches without concatenating
+ *            them: train.py:99's cat([past, future]) as two pointers (only the first layer reads the waveform), 1 <= n_first <
+ *            n_windows.  NULL: one input batch, and then n_first must equal n_windows
  *   params   20 pointers in state-dict order: for i in 0..4:
  *              conv{i}.weight [H, Cin, k], conv{i}.bias [H],
  *              batchNorm{i}.weight [1,H,1], batchNorm{i}.bias [1,H,1]
@@ -183,28 +187,15 @@ int cpc_channelnorm_backward(const float *x, const float *w, const float *dy, co
 int cpc_encoder_frames(int length);
 size_t cpc_encoder_saved_bytes(int n_windows, int length, int hidden);
 size_t cpc_encoder_scratch_bytes(int n_windows, int length, int hidden);
-int cpc_encoder_forward(const float *x, const float *const *params, float *z, void *saved,
-                        void *scratch, int n_windows, int length, int hidden, float eps,
-                        cpc_stream_t stream);
-int cpc_encoder_backward(const float *x, const float *const *params, const float *dz, void *saved,
-                         void *scratch, float *const *grads, int n_windows, int length, int hidden,
-                         float eps, cpc_stream_t stream);
-/* Deferred form of the same backward: the small passes of conv1-4 that only finish parameter gradients (the column sums of
- * dgamma / dbeta / dbias, the sum of each weight-gradient product's K-split slabs) run on a stream of the library's; the gradients
- * of conv1-4 and their norms may then not be read (nor x, saved, scratch reused) until cpc_side_tail_join(stream') -- see
- * cpc_gru_backward_deferred.  conv0's gradients are complete on `stream` as before. */
-int cpc_encoder_backward_deferred(const float *x, const float *const *params, const float *dz, void *saved,
-                         void *scratch, float *const *grads, int n_windows, int length, int hidden,
-                         float eps, cpc_stream_t stream);
-/* The same encoder over TWO input batches without concatenating them: windows 0 .. n_first - 1 are x_first [n_first, 1, length],
- * windows n_first .. n_windows - 1 are x_rest [n_windows - n_first, 1, length] -- train.py:99's cat([past, future]) as two pointers
- * (only the first layer reads the waveform).  Everything else as cpc_encoder_forward / cpc_encoder_backward; deferred != 0 selects
- * the deferred form of the backward (cpc_encoder_backward_deferred). */
-int cpc_encoder_forward2(const float *x_first, const float *x_rest, int n_first, const float *const *params, float *z, void *saved,
-                         void *scratch, int n_windows, int length, int hidden, float eps, cpc_stream_t stream);
-int cpc_encoder_backward2(const float *x_first, const float *x_rest, int n_first, const float *const *params, const float *dz,
-                          void *saved, void *scratch, float *const *grads, int n_windows, int length, int hidden, float eps,
-                          int deferred, cpc_stream_t stream);
+int cpc_encoder_forward(const float *x_first, const float *x_rest, int n_first, const float *const *params, float *z, void *saved,
+                        void *scratch, int n_windows, int length, int hidden, float eps, cpc_stream_t stream);
+/* deferred != 0: the small passes of conv1-4 that only finish parameter gradients (the column sums of dgamma / dbeta / dbias, the
+ * sum of each weight-gradient product's K-split slabs) run on a stream of the library's; the gradients of conv1-4 and their norms
+ * may then not be read (nor x, saved, scratch reused) until cpc_side_tail_join(stream') -- see cpc_gru_backward.  conv0's
+ * gradients are complete on `stream` as before. */
+int cpc_encoder_backward(const float *x_first, const float *x_rest, int n_first, const float *const *params, const float *dz,
+                         void *saved, void *scratch, float *const *grads, int n_windows, int length, int hidden, float eps,
+                         int deferred, cpc_stream_t stream);
 /* Inspection (tests only; the layout of `saved` is otherwise private): what the forward pass keeps of layer 0..4 --
  * the ChannelNorm of model.py:52-60 as (xhat, rstd) (layers 1..4) and, at hidden 256 / 512, the layer's ReLU'd output as the
  * next layer's input planes (layers 0..3).  out[10]:
@@ -229,18 +220,15 @@ size_t cpc_gru_scratch_bytes(int n, int t, int dim_in, int hidden, int layers);
 int cpc_gru_forward(const float *x, const float *const *params, const float *h0, float *out,
                     float *h_last, void *saved, void *scratch, int n, int t, int dim_in, int hidden,
                     int layers, cpc_stream_t stream);
-int cpc_gru_backward(const float *x, const float *const *params, const float *dout, void *saved,
-                     void *scratch, float *dx, float *const *grads, int n, int t, int dim_in,
-                     int hidden, int layers, cpc_stream_t stream);
-/* Deferred form of the same backward: on return `dx` is ordered on `stream`; the parameter gradients of every layer (weight_ih,
- * weight_hh and the two biases: two weight-gradient products and two column sums per layer that nothing in a backward pass needs
- * before the optimiser) are produced on a stream of the library's, beside the next layer's recurrent kernel and what the caller
- * enqueues on `stream` next, and NOTHING may read them (nor reuse x, saved, scratch, dout) until cpc_side_tail_join(stream') has been called for the
+/* deferred != 0: on return `dx` is ordered on `stream`; the parameter gradients of every layer (weight_ih, weight_hh and the two
+ * biases: two weight-gradient products and two column sums per layer that nothing in a backward pass needs before the optimiser)
+ * are produced on a stream of the library's, beside the next layer's recurrent kernel and what the caller enqueues on `stream`
+ * next, and NOTHING may read them (nor reuse x, saved, scratch, dout) until cpc_side_tail_join(stream') has been called for the
  * stream' that will -- it makes stream' wait for them (a no-op when nothing is pending; one such tail per device).  For callers
  * that write gradients in place and read them only at the end of the backward pass (cpc2_amd: FlatAdam's flat buffer). */
-int cpc_gru_backward_deferred(const float *x, const float *const *params, const float *dout, void *saved,
-                              void *scratch, float *dx, float *const *grads, int n, int t, int dim_in,
-                              int hidden, int layers, cpc_stream_t stream);
+int cpc_gru_backward(const float *x, const float *const *params, const float *dout, void *saved,
+                     void *scratch, float *dx, float *const *grads, int n, int t, int dim_in,
+                     int hidden, int layers, int deferred, cpc_stream_t stream);
 int cpc_side_tail_join(cpc_stream_t stream);
 /* `stream` waits for the same work, which STAYS pending: for a stream that only consumes the finished gradients (the data-parallel
  * exchange's helper stream) while the caller's stream goes on; the buffers of the deferred calls are released by cpc_side_tail_join. */
@@ -259,16 +247,14 @@ size_t cpc_lstm_scratch_bytes(int n, int t, int dim_in, int hidden, int layers);
 int cpc_lstm_forward(const float *x, const float *const *params, const float *h0, const float *c0,
                      float *out, float *h_last, float *c_last, void *saved, void *scratch, int n,
                      int t, int dim_in, int hidden, int layers, cpc_stream_t stream);
+/* deferred != 0: as for cpc_gru_backward (the layers' weight gradients on the library's stream until cpc_side_tail_join). */
 int cpc_lstm_backward(const float *x, const float *const *params, const float *dout, void *saved,
                       void *scratch, float *dx, float *const *grads, int n, int t, int dim_in,
-                      int hidden, int layers, cpc_stream_t stream);
-/* Deferred form: as cpc_gru_backward_deferred (layer 0's weight gradients on the library's stream until cpc_side_tail_join). */
-int cpc_lstm_backward_deferred(const float *x, const float *const *params, const float *dout, void *saved,
-                      void *scratch, float *dx, float *const *grads, int n, int t, int dim_in,
-                      int hidden, int layers, cpc_stream_t stream);
+                      int hidden, int layers, int deferred, cpc_stream_t stream);
 
 /* CPCAR with mode="RNN" (model.py:174-176 -> torch.nn.RNN, tanh): weight_ih [H, in], weight_hh [H, H],
- * bias_ih [H], bias_hh [H]; arguments as for the GRU. */
+ * bias_ih [H], bias_hh [H]; arguments as for the GRU, except that this cell has no deferred backward: `deferred` must be 0
+ * (CPC_ERR_INVALID otherwise). */
 size_t cpc_rnn_saved_bytes(int n, int t, int dim_in, int hidden, int layers);
 size_t cpc_rnn_scratch_bytes(int n, int t, int dim_in, int hidden, int layers);
 int cpc_rnn_forward(const float *x, const float *const *params, const float *h0, float *out,
@@ -276,7 +262,7 @@ int cpc_rnn_forward(const float *x, const float *const *params, const float *h0,
                     int layers, cpc_stream_t stream);
 int cpc_rnn_backward(const float *x, const float *const *params, const float *dout, void *saved,
                      void *scratch, float *dx, float *const *grads, int n, int t, int dim_in,
-                     int hidden, int layers, cpc_stream_t stream);
+                     int hidden, int layers, int deferred, cpc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Transformer autoregressive network (arMode="transformer", cpc/transformers.py:10-134,176-187):
@@ -303,17 +289,13 @@ size_t cpc_transformer_scratch_bytes(int n, int s, int d_model, int d_out, int s
 int cpc_transformer_forward(const float *x, const float *const *params, float *out, void *saved,
                             void *scratch, int n, int s, int d_model, int d_out, int size_seq, int layers,
                             int n_classifiers, float dropout_p, unsigned long long seed, cpc_stream_t stream);
+/* deferred != 0 (see cpc_gru_backward): with one classifier, every parameter gradient of layer 0 -- seven weight-gradient
+ * products with their bias sums, the LayerNorms' and Krelpos' column sums -- is produced on the library's stream after this call
+ * has returned; `dx` and the gradients of layers 1.. are ordered on `stream`.  cpc_side_tail_join before anything reads them. */
 int cpc_transformer_backward(const float *x, const float *const *params, const float *dout, void *saved,
                              void *scratch, float *dx, float *const *grads, int n, int s, int d_model,
                              int d_out, int size_seq, int layers, int n_classifiers, float dropout_p,
-                             unsigned long long seed, cpc_stream_t stream);
-/* Deferred form (see cpc_gru_backward_deferred): with one classifier, every parameter gradient of layer 0 -- seven weight-gradient
- * products with their bias sums, the LayerNorms' and Krelpos' column sums -- is produced on the library's stream after this call
- * has returned; `dx` and the gradients of layers 1.. are ordered on `stream`.  cpc_side_tail_join before anything reads them. */
-int cpc_transformer_backward_deferred(const float *x, const float *const *params, const float *dout, void *saved,
-                             void *scratch, float *dx, float *const *grads, int n, int s, int d_model,
-                             int d_out, int size_seq, int layers, int n_classifiers, float dropout_p,
-                             unsigned long long seed, cpc_stream_t stream);
+                             unsigned long long seed, int deferred, cpc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Negative-index sampler of CPCUnsupersivedCriterion.sampleClean (criterion.py:247-266), HOST
@@ -373,14 +355,17 @@ int cpc_negidx_expand(const uint32_t *raw, int32_t *ext_idx, int batch, int seq_
  * 237-286, PredictionNetwork.forward :152-173): K predictions W_k c_t, scored by dot product / H
  * against 1 positive z[b, t+k] + n_neg gathered negatives, cross-entropy vs class 0.
  * The gathered candidate tensors of the reference are never materialised.
- *   c        [b, T, dim_ar]   context (only t < W = T-K is used)
+ *   c        [b, c_frames, dim_ar]   context.  c_frames = T: the whole sequence (only t < W = T-K is used; criterion.py:296
+ *            slices `cFeature[:, :windowSize]` itself), or c_frames = W when the caller hands over ONLY the W frames it uses: a
+ *            causal context network that keeps no state across calls need not compute the k frames behind them
+ *            (cpc2_amd.train.cpcStep runs it on W steps).  Any other c_frames: CPC_ERR_INVALID.  z stays [b, T, dim_enc]
  *   z        [b, T, dim_enc]  encoder targets
  *   wpred    [K, dim_enc, dim_ar] packed nn.Linear weights (predictors.k.weight)
  *   ext_idx  [b, W, n_neg] int32 rows of z.view(b*T, dim_enc): cpc_negidx_sample_host with
  *            time_major = 1 (same values as the reference's [b, n_neg, W] order, transposed)
  *   weights  [b*W] per-sample loss weights or NULL (ones)        (criterion.py:334-340)
  *   losses   [K]  mean_i(w_i * CE_i);  acc [K] = #(argmax == 0) / (b*W)
- * backward: dlosses [K] upstream gradient -> dc [b,T,dim_ar], dz [b,T,dim_enc],
+ * backward: dlosses [K] upstream gradient -> dc [b,c_frames,dim_ar], dz [b,T,dim_enc],
  *           dwpred [K,dim_enc,dim_ar]  (all overwritten; dz is summed per row in a fixed order, so it
  *           is identical from run to run)
  * ------------------------------------------------------------------------------------------ */
@@ -398,33 +383,18 @@ size_t cpc_infonce_perm_offset(int b, int t, int k, int dim_ar, int dim_enc, int
  *  reported by the next cpc_async_error_check(stream) -- criterion.py:264-268's gather has no such check.) */
 int cpc_infonce_forward(const float *c, const float *z, const float *wpred, const int32_t *ext_idx,
                         const float *weights, float *losses, float *acc, void *saved, void *scratch,
-                        int b, int t, int k, int dim_ar, int dim_enc, int n_neg, cpc_stream_t stream);
+                        int b, int t, int c_frames, int k, int dim_ar, int dim_enc, int n_neg, cpc_stream_t stream);
+/* deferred != 0: on return only `dc` -- what the context network's backward (cpc/model.py:158-207 under autograd) needs next -- is
+ * ordered on `stream`; `dz` and `dwpred` are produced on a stream of the library's, beside whatever the caller enqueues on `stream`
+ * afterwards, and NOTHING may read them (nor reuse c, z, ext_idx, saved, scratch) until cpc_infonce_join(stream') has been called
+ * for the stream' that will: it makes stream' wait for them (a no-op when nothing is pending; one deferred backward may be pending
+ * per device).  The context network's backward is latency-bound and leaves the chip idle; the criterion's dz is a memory-bound sum
+ * over ~1 GB -- together they take the time of the longer one. */
 int cpc_infonce_backward(const float *c, const float *z, const float *wpred, const int32_t *ext_idx,
                          const float *weights, const float *dlosses, void *saved, void *scratch,
-                         float *dc, float *dz, float *dwpred, int b, int t, int k, int dim_ar,
-                         int dim_enc, int n_neg, cpc_stream_t stream);
-/* Deferred form of the same backward.  On return only `dc` -- what the context network's backward (cpc/model.py:158-207 under
- * autograd) needs next -- is ordered on `stream`; `dz` and `dwpred` are produced on a stream of the library's, beside whatever
- * the caller enqueues on `stream` afterwards, and NOTHING may read them (nor reuse c, z, ext_idx, saved, scratch) until
- * cpc_infonce_join(stream') has been called for the stream' that will: it makes stream' wait for them (a no-op when nothing is
- * pending; one deferred backward may be pending per device).  The context network's backward is latency-bound and leaves the
- * chip idle; the criterion's dz is a memory-bound sum over ~1 GB -- together they take the time of the longer one. */
-int cpc_infonce_backward_deferred(const float *c, const float *z, const float *wpred, const int32_t *ext_idx,
-                                  const float *weights, const float *dlosses, void *saved, void *scratch,
-                                  float *dc, float *dz, float *dwpred, int b, int t, int k, int dim_ar,
-                                  int dim_enc, int n_neg, cpc_stream_t stream);
+                         float *dc, float *dz, float *dwpred, int b, int t, int c_frames, int k, int dim_ar,
+                         int dim_enc, int n_neg, int deferred, cpc_stream_t stream);
 int cpc_infonce_join(cpc_stream_t stream);
-/* The same criterion when the caller hands over ONLY the W = t - k context frames it uses: c and dc are [b, t - k, dim_ar] (z stays
- * [b, t, dim_enc]).  criterion.py:296 slices `cFeature[:, :windowSize]` itself; a causal context network that keeps no state across
- * calls need not compute the k frames behind it (cpc2_amd.train.cpcStep runs it on W steps and calls these).  deferred != 0: the
- * deferred form of the backward (cpc_infonce_backward_deferred). */
-int cpc_infonce_forward_cw(const float *c, const float *z, const float *wpred, const int32_t *ext_idx,
-                           const float *weights, float *losses, float *acc, void *saved, void *scratch,
-                           int b, int t, int k, int dim_ar, int dim_enc, int n_neg, cpc_stream_t stream);
-int cpc_infonce_backward_cw(const float *c, const float *z, const float *wpred, const int32_t *ext_idx,
-                            const float *weights, const float *dlosses, void *saved, void *scratch,
-                            float *dc, float *dz, float *dwpred, int b, int t, int k, int dim_ar,
-                            int dim_enc, int n_neg, int deferred, cpc_stream_t stream);
 
 /* The same criterion when the K predictions come from predictor MODULES instead of linear maps
  * (rnnMode="transformer": criterion.py:136-143; the predictions are produced by cpc_transformer_*):

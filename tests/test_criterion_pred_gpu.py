@@ -292,11 +292,11 @@ def test_pred_and_linear_families_agree_at_full_batch():
     scr = torch.empty(lib.cpc_infonce_scratch_bytes(b, t_len, k, h, h, nn), dtype=torch.uint8, device=DEV)
     lin_losses, lin_acc = torch.empty(k, device=DEV), torch.empty(k, device=DEV)
     _lib.check(lib.cpc_infonce_forward(_lib.ptr(cd), _lib.ptr(z2), _lib.ptr(wpred), _lib.ptr(ext_tm), None, _lib.ptr(lin_losses),
-                                       _lib.ptr(lin_acc), _lib.ptr(saved), _lib.ptr(scr), b, t_len, k, h, h, nn, st), "fwd")
+                                       _lib.ptr(lin_acc), _lib.ptr(saved), _lib.ptr(scr), b, t_len, t_len, k, h, h, nn, st), "fwd")
     dc, dz, dw = torch.empty_like(cd), torch.full_like(z2, float("nan")), torch.empty_like(wpred)
     ones = torch.ones(k, device=DEV)
     _lib.check(lib.cpc_infonce_backward(_lib.ptr(cd), _lib.ptr(z2), _lib.ptr(wpred), _lib.ptr(ext_tm), None, _lib.ptr(ones), _lib.ptr(saved),
-                                        _lib.ptr(scr), _lib.ptr(dc), _lib.ptr(dz), _lib.ptr(dw), b, t_len, k, h, h, nn, st), "bwd")
+                                        _lib.ptr(scr), _lib.ptr(dc), _lib.ptr(dz), _lib.ptr(dw), b, t_len, t_len, k, h, h, nn, 0, st), "bwd")
     torch.cuda.synchronize()
     _lib.check(lib.cpc_async_error_check(st), "async errors")
     assert_close(losses, lin_losses, 1e-5, "losses, _pred family vs linear family", kind="2 families: losses")

@@ -407,7 +407,7 @@ def test_encoder_vs_oracle_fp64(hidden, n, length):
 
 @pytest.mark.parametrize("hidden,n,n_first", [(256, 5, 2), (64, 3, 1), (512, 4, 3)])
 def test_encoder_over_two_input_batches_equals_the_concatenated_call(hidden, n, n_first):
-    """cpc_encoder_forward2 / cpc_encoder_backward2: windows 0 .. n_first - 1 from one buffer, the rest from another (train.py:99's
+    """cpc_encoder_forward / cpc_encoder_backward with x_rest: windows 0 .. n_first - 1 from one buffer, the rest from another (train.py:99's
     cat([past, future]) as two pointers; only conv0's kernels read the waveform): output and every gradient are those of the
     concatenated call, bit for bit."""
     params = synth.encoder_params(hidden, seed=5)
@@ -439,7 +439,7 @@ def _kernel_relu_decisions(hidden, params, x, windows=None):
     z = torch.empty(n, frames, hidden, device=DEV)
     saved = torch.zeros(lib.cpc_encoder_saved_bytes(n, length, hidden), dtype=torch.uint8, device=DEV)
     scratch = torch.empty(lib.cpc_encoder_scratch_bytes(n, length, hidden), dtype=torch.uint8, device=DEV)
-    _lib.check(lib.cpc_encoder_forward(_lib.ptr(xd), _lib.ptr_array(plist), _lib.ptr(z), _lib.ptr(saved), _lib.ptr(scratch), n, length,
+    _lib.check(lib.cpc_encoder_forward(_lib.ptr(xd), None, n, _lib.ptr_array(plist), _lib.ptr(z), _lib.ptr(saved), _lib.ptr(scratch), n, length,
                                        hidden, 1e-5, _lib.stream_ptr(xd.device)), "encoder_forward")
     masks = []
     for layer in range(4):
@@ -539,7 +539,7 @@ frames = lib.cpc_encoder_frames(length)
 z = torch.empty(n, frames, hidden, device=dev)
 saved = torch.zeros(lib.cpc_encoder_saved_bytes(n, length, hidden), dtype=torch.uint8, device=dev)
 scratch = torch.empty(lib.cpc_encoder_scratch_bytes(n, length, hidden), dtype=torch.uint8, device=dev)
-_lib.check(lib.cpc_encoder_forward(_lib.ptr(x), _lib.ptr_array(params), _lib.ptr(z), _lib.ptr(saved), _lib.ptr(scratch), n, length,
+_lib.check(lib.cpc_encoder_forward(_lib.ptr(x), None, n, _lib.ptr_array(params), _lib.ptr(z), _lib.ptr(saved), _lib.ptr(scratch), n, length,
                                    hidden, 1e-5, _lib.stream_ptr(dev)), "encoder_forward")
 torch.cuda.synchronize()
 out = {{"z": z.cpu()}}
@@ -1157,7 +1157,7 @@ def test_criterion_at_full_batch_vs_oracle_module_call(golden, h, nn):
 @pytest.mark.parametrize("deferred", [0, 1])
 @pytest.mark.parametrize("h,nn", [(256, 128), (512, 256)])
 def test_criterion_at_full_batch_vs_oracle_step_form(h, nn, deferred):
-    """The form cpcStep runs (cpc_infonce_forward_cw / backward_cw: the context handed over as its W frames; deferred = 1: dz and
+    """The form cpcStep runs (cpc_infonce_forward / backward with c_frames = W: the context handed over as its W frames; deferred = 1: dz and
     the predictor gradients on the library's side stream, joined afterwards) at b = 64 against the sparse fp64 oracle, with a
     non-uniform gradient of the losses."""
     lib = _lib.load()
@@ -1172,11 +1172,11 @@ def test_criterion_at_full_batch_vs_oracle_step_form(h, nn, deferred):
     saved = torch.empty(lib.cpc_infonce_saved_bytes(b, t_len, k, h, h, nn), dtype=torch.uint8, device=DEV)
     scr = torch.empty(lib.cpc_infonce_scratch_bytes(b, t_len, k, h, h, nn), dtype=torch.uint8, device=DEV)
     losses, acc = torch.empty(k, device=DEV), torch.empty(k, device=DEV)
-    _lib.check(lib.cpc_infonce_forward_cw(_lib.ptr(cw), _lib.ptr(zd), _lib.ptr(wpred), _lib.ptr(ext), None, _lib.ptr(losses), _lib.ptr(acc),
-                                          _lib.ptr(saved), _lib.ptr(scr), b, t_len, k, h, h, nn, st), "fwd")
+    _lib.check(lib.cpc_infonce_forward(_lib.ptr(cw), _lib.ptr(zd), _lib.ptr(wpred), _lib.ptr(ext), None, _lib.ptr(losses), _lib.ptr(acc),
+                                       _lib.ptr(saved), _lib.ptr(scr), b, t_len, w_len, k, h, h, nn, st), "fwd")
     dc, dz, dw = torch.full_like(cw, float("nan")), torch.full_like(zd, float("nan")), torch.full_like(wpred, float("nan"))
-    _lib.check(lib.cpc_infonce_backward_cw(_lib.ptr(cw), _lib.ptr(zd), _lib.ptr(wpred), _lib.ptr(ext), None, _lib.ptr(dld), _lib.ptr(saved),
-                                           _lib.ptr(scr), _lib.ptr(dc), _lib.ptr(dz), _lib.ptr(dw), b, t_len, k, h, h, nn, deferred, st), "bwd")
+    _lib.check(lib.cpc_infonce_backward(_lib.ptr(cw), _lib.ptr(zd), _lib.ptr(wpred), _lib.ptr(ext), None, _lib.ptr(dld), _lib.ptr(saved),
+                                        _lib.ptr(scr), _lib.ptr(dc), _lib.ptr(dz), _lib.ptr(dw), b, t_len, w_len, k, h, h, nn, deferred, st), "bwd")
     if deferred:
         _lib.check(lib.cpc_infonce_join(st), "join")
     torch.cuda.synchronize()
@@ -1830,7 +1830,7 @@ def test_training_steps_are_reproducible_bit_for_bit():
 
 @pytest.mark.parametrize("form", ["context", "strict", "dedup"])
 def test_deferred_criterion_backward_gives_the_same_step_bit_for_bit(monkeypatch, form):
-    """cpc_infonce_backward_deferred + cpc_infonce_join (dz and the predictor weight gradients on the library's side stream,
+    """cpc_infonce_backward with deferred = 1 + cpc_infonce_join (dz and the predictor weight gradients on the library's side stream,
     beside the recurrent backward; joined where autograd sums the encoder output's gradient) runs the SAME kernels as the
     immediate form: every gradient and the parameters after two steps are equal bit for bit -- with cpcStep's default (context
     network on the b context windows: the criterion differentiates with respect to the target half of split_windows), with the
@@ -2148,7 +2148,8 @@ def test_criterion_backward_is_deferred_only_inside_the_callers_scope(monkeypatc
 
 
 def test_recurrent_weight_gradients_are_deferred_only_inside_the_callers_scope(monkeypatch):
-    """cpc_gru_backward_deferred / cpc_encoder_backward_deferred (parameter-gradient work on the library's side stream):
+    """cpc_gru_backward / cpc_lstm_backward / cpc_encoder_backward with deferred = 1 (parameter-gradient work on the library's side
+    stream; counted below: the calls whose `deferred` argument, the one in front of the stream, is non-zero):
     (1) cpcStep on the bare model defers them, and every gradient of the step is bit-identical to the immediate form's;
     (2) model called directly (the reference's train.py), or a tensor hook on one of those weights: not deferred;
     (3) two GRU layers: layer 1's gradients on the caller's stream, layer 0's deferred -- same bits again."""
@@ -2166,18 +2167,20 @@ def test_recurrent_weight_gradients_are_deferred_only_inside_the_callers_scope(m
         label = torch.zeros(b, dtype=torch.long, device=DEV)
         lib = _lib.load()
         calls, enc_calls = [], []
-        rec_name = "cpc_gru_backward_deferred" if mode == "GRU" else "cpc_lstm_backward_deferred"
-        real, real_enc = getattr(lib, rec_name), lib.cpc_encoder_backward_deferred
+        rec_name = "cpc_gru_backward" if mode == "GRU" else "cpc_lstm_backward"
+        real, real_enc = getattr(lib, rec_name), lib.cpc_encoder_backward
 
         def spy(*a):
-            calls.append(1)
+            if a[-2]:
+                calls.append(1)
             return real(*a)
 
         def spy_enc(*a):
-            enc_calls.append(1)
+            if a[-2]:
+                enc_calls.append(1)
             return real_enc(*a)
         monkeypatch.setattr(lib, rec_name, spy)
-        monkeypatch.setattr(lib, "cpc_encoder_backward_deferred", spy_enc)
+        monkeypatch.setattr(lib, "cpc_encoder_backward", spy_enc)
 
         def grads(how):
             crit.seed(5)
@@ -2211,12 +2214,12 @@ def test_recurrent_weight_gradients_are_deferred_only_inside_the_callers_scope(m
         assert n_hooked2 == (1, 0) and len(touched) == 2 and touched[1] > 0
         assert torch.equal(g_step, g_hooked2)
         monkeypatch.setattr(lib, rec_name, real)
-        monkeypatch.setattr(lib, "cpc_encoder_backward_deferred", real_enc)
+        monkeypatch.setattr(lib, "cpc_encoder_backward", real_enc)
 
 
 @pytest.mark.parametrize("n_layers", [1, 2, 3])
 def test_transformer_parameter_gradients_are_deferred_inside_the_callers_scope(monkeypatch, n_layers):
-    """cpc_transformer_backward_deferred (arMode='transformer': the layer's seven weight-gradient products, bias sums and column sums
+    """cpc_transformer_backward with deferred = 1 (arMode='transformer': the layer's seven weight-gradient products, bias sums and column sums
     on the library's side stream): cpcStep on the bare model defers, the model called directly does not, every gradient of the step
     is the same bit for bit -- in training mode (dropout on, same seed) and with the criterion's own deferred backward beside it.
     nLevelsGRU >= 2 (round-4 advisor finding): every TransformerLayer of the nn.Sequential defers on its own, the side stream
@@ -2239,12 +2242,13 @@ def test_transformer_parameter_gradients_are_deferred_inside_the_callers_scope(m
     label = torch.zeros(b, dtype=torch.long, device=DEV)
     lib = _lib.load()
     calls = []
-    real = lib.cpc_transformer_backward_deferred
+    real = lib.cpc_transformer_backward
 
     def spy(*a):
-        calls.append(1)
+        if a[-2]:                                          # (`deferred`, the argument in front of the stream)
+            calls.append(1)
         return real(*a)
-    monkeypatch.setattr(lib, "cpc_transformer_backward_deferred", spy)
+    monkeypatch.setattr(lib, "cpc_transformer_backward", spy)
 
     def grads(how):
         crit.seed(5)
@@ -2267,7 +2271,7 @@ def test_transformer_parameter_gradients_are_deferred_inside_the_callers_scope(m
         g_direct, n_direct = grads("direct")
         assert (n_step, n_direct) == (n_layers, 0)
         assert torch.equal(g_step, g_direct) and float(g_step.abs().max()) > 0
-    monkeypatch.setattr(lib, "cpc_transformer_backward_deferred", real)
+    monkeypatch.setattr(lib, "cpc_transformer_backward", real)
 
 
 def test_seeded_backward_of_the_summed_losses_is_the_plain_one():
@@ -2330,7 +2334,7 @@ def test_criterion_index_range_is_checked_on_the_device():
         losses, acc = torch.empty(k, device=DEV), torch.empty(k, device=DEV)
         idx = idx.to(DEV)
         _lib.check(lib.cpc_infonce_forward(_lib.ptr(c), _lib.ptr(z), _lib.ptr(wpred), _lib.ptr(idx), None, _lib.ptr(losses), _lib.ptr(acc),
-                                           _lib.ptr(saved), _lib.ptr(scr), b, t, k, h, h, nn, st), "fwd")
+                                           _lib.ptr(saved), _lib.ptr(scr), b, t, t, k, h, h, nn, st), "fwd")
         return losses.cpu(), lib.cpc_async_error_check(st)
     clean, rc = forward(ext)
     assert rc == 0
@@ -2346,8 +2350,8 @@ def test_criterion_index_range_is_checked_on_the_device():
 
 
 def test_infonce_backward_deferred_c_entry_matches_the_immediate_one():
-    """The C entry points themselves: deferred + join on the calling stream == cpc_infonce_backward, bit for bit; a second join
-    is a no-op."""
+    """The C entry point itself: cpc_infonce_backward with deferred = 1 + join on the calling stream == deferred = 0, bit for bit; a
+    second join is a no-op."""
     from cpc2_amd import _lib
     lib = _lib.load()
     b, t, k, h, nn = 4, 128, 12, 256, 32
@@ -2361,16 +2365,15 @@ def test_infonce_backward_deferred_c_entry_matches_the_immediate_one():
     nsaved = lib.cpc_infonce_saved_bytes(b, t, k, h, h, nn)
     nscr = lib.cpc_infonce_scratch_bytes(b, t, k, h, h, nn)
     outs = []
-    for deferred in (False, True):
+    for deferred in (0, 1):
         saved = torch.empty(nsaved, dtype=torch.uint8, device=DEV)
         scr = torch.empty(nscr, dtype=torch.uint8, device=DEV)
         losses, acc = torch.empty(k, device=DEV), torch.empty(k, device=DEV)
         _lib.check(lib.cpc_infonce_forward(_lib.ptr(c), _lib.ptr(z), _lib.ptr(wpred), _lib.ptr(ext), None, _lib.ptr(losses), _lib.ptr(acc),
-                                           _lib.ptr(saved), _lib.ptr(scr), b, t, k, h, h, nn, st), "fwd")
+                                           _lib.ptr(saved), _lib.ptr(scr), b, t, t, k, h, h, nn, st), "fwd")
         dc, dz, dw = torch.empty_like(c), torch.empty_like(z), torch.empty_like(wpred)
-        fn = lib.cpc_infonce_backward_deferred if deferred else lib.cpc_infonce_backward
-        _lib.check(fn(_lib.ptr(c), _lib.ptr(z), _lib.ptr(wpred), _lib.ptr(ext), None, _lib.ptr(dl), _lib.ptr(saved), _lib.ptr(scr),
-                      _lib.ptr(dc), _lib.ptr(dz), _lib.ptr(dw), b, t, k, h, h, nn, st), "bwd")
+        _lib.check(lib.cpc_infonce_backward(_lib.ptr(c), _lib.ptr(z), _lib.ptr(wpred), _lib.ptr(ext), None, _lib.ptr(dl), _lib.ptr(saved),
+                                            _lib.ptr(scr), _lib.ptr(dc), _lib.ptr(dz), _lib.ptr(dw), b, t, t, k, h, h, nn, deferred, st), "bwd")
         if deferred:
             _lib.check(lib.cpc_infonce_join(st), "join")
             _lib.check(lib.cpc_infonce_join(st), "join again")
@@ -2379,6 +2382,63 @@ def test_infonce_backward_deferred_c_entry_matches_the_immediate_one():
     for name, a, bb in zip(("dc", "dz", "dwpred"), outs[0], outs[1]):
         assert torch.equal(a, bb), name
     assert float(outs[0][1].abs().max()) > 0
+
+
+def test_unified_entry_points_refuse_inconsistent_arguments():
+    """The arguments that replaced the sibling entry points are checked before anything is launched: each call below returns
+    CPC_ERR_INVALID (ValueError) with a message of its own and leaves its poisoned outputs untouched."""
+    lib = _lib.load()
+    st = _lib.stream_ptr(torch.device(DEV))
+    nan = float("nan")
+    # encoder: hidden 32, two windows of 400 samples
+    hidden, n, length = 32, 2, 400
+    params = [v.to(DEV).contiguous() for v in synth.encoder_params(hidden, seed=5).values()]
+    x = synth.audio_windows(n, length, seed=6).to(DEV)
+    z = torch.full((n, lib.cpc_encoder_frames(length), hidden), nan, device=DEV)
+    nsaved, nscr = lib.cpc_encoder_saved_bytes(n, length, hidden), lib.cpc_encoder_scratch_bytes(n, length, hidden)
+    assert nsaved > 0 and nscr > 0
+    saved, scr = torch.empty(nsaved, dtype=torch.uint8, device=DEV), torch.empty(nscr, dtype=torch.uint8, device=DEV)
+
+    def encoder(x_rest, n_first):
+        _lib.check(lib.cpc_encoder_forward(_lib.ptr(x), _lib.ptr(x_rest), n_first, _lib.ptr_array(params), _lib.ptr(z), _lib.ptr(saved),
+                                           _lib.ptr(scr), n, length, hidden, 1e-5, st), "encoder_forward")
+    with pytest.raises(ValueError, match="one input batch"):
+        encoder(None, 1)                                   # x_rest = NULL and n_first != n_windows
+    with pytest.raises(ValueError, match="first batch"):
+        encoder(x[1:], 0)                                  # x_rest set, no window in the first batch
+    with pytest.raises(ValueError, match="first batch"):
+        encoder(x[1:], n)                                  # x_rest set, every window in the first batch
+    # criterion: a context of t - 1 frames is neither the sequence nor the W frames the criterion uses
+    b, t, k, nn, dim = 2, 20, 4, 8, 32
+    g = torch.Generator().manual_seed(3)
+    c, zc = torch.randn(b, t, dim, generator=g).to(DEV), torch.randn(b, t, dim, generator=g).to(DEV)
+    wpred = (0.05 * torch.randn(k, dim, dim, generator=g)).to(DEV)
+    ext = torch.randint(0, b * t, (b * (t - k) * nn,), generator=g, dtype=torch.int32).to(DEV)
+    nsaved, nscr = lib.cpc_infonce_saved_bytes(b, t, k, dim, dim, nn), lib.cpc_infonce_scratch_bytes(b, t, k, dim, dim, nn)
+    assert nsaved > 0 and nscr > 0
+    csaved, cscr = torch.empty(nsaved, dtype=torch.uint8, device=DEV), torch.empty(nscr, dtype=torch.uint8, device=DEV)
+    losses, acc = torch.full((k,), nan, device=DEV), torch.full((k,), nan, device=DEV)
+    with pytest.raises(ValueError, match=f"holds {t - 1} frames"):
+        _lib.check(lib.cpc_infonce_forward(_lib.ptr(c), _lib.ptr(zc), _lib.ptr(wpred), _lib.ptr(ext), None, _lib.ptr(losses), _lib.ptr(acc),
+                                           _lib.ptr(csaved), _lib.ptr(cscr), b, t, t - 1, k, dim, dim, nn, st), "infonce_forward")
+    # RNN: one layer, n = 2, t = 4 -- the cell has no deferred backward
+    rn, rt = 2, 4
+    rparams = [torch.zeros(s, device=DEV) for s in ((hidden, hidden), (hidden, hidden), (hidden,), (hidden,))]
+    rx, dout = torch.zeros(rn, rt, hidden, device=DEV), torch.zeros(rn, rt, hidden, device=DEV)
+    nsaved, nscr = lib.cpc_rnn_saved_bytes(rn, rt, hidden, hidden, 1), lib.cpc_rnn_scratch_bytes(rn, rt, hidden, hidden, 1)
+    assert nsaved > 0 and nscr > 0
+    rsaved, rscr = torch.zeros(nsaved, dtype=torch.uint8, device=DEV), torch.empty(nscr, dtype=torch.uint8, device=DEV)
+    dx = torch.full_like(rx, nan)
+    rgrads = [torch.full_like(p, nan) for p in rparams]
+    calls = lib.cpc_recurrent_backward_calls()
+    with pytest.raises(ValueError, match="RNN"):
+        _lib.check(lib.cpc_rnn_backward(_lib.ptr(rx), _lib.ptr_array(rparams), _lib.ptr(dout), _lib.ptr(rsaved), _lib.ptr(rscr), _lib.ptr(dx),
+                                        _lib.ptr_array(rgrads), rn, rt, hidden, hidden, 1, 1, st), "rnn_backward")
+    assert lib.cpc_recurrent_backward_calls() == calls
+    torch.cuda.synchronize()
+    # nothing was launched: every output still holds its poison
+    for out in [z, losses, acc, dx] + rgrads:
+        assert bool(torch.isnan(out).all())
 
 
 def test_train_step_with_signal_quality_files(tmp_path):

@@ -105,14 +105,14 @@ def measure_main(hidden, steps, out):
 
     def twice(ctx, dz):
         ret = orig(ctx, dz)
-        xx, saved, *params = ctx.saved_tensors
-        n, length, hid = ctx.dims
+        xx, x2, saved, *params = ctx.saved_tensors
+        n, length, hid, n_first = ctx.dims
         arena = _lib.scratch(lib.cpc_encoder_scratch_bytes(n, length, hid), xx.device)
-        g1 = [g.clone() for g in ret[2:]]
-        g2 = [torch.empty_like(g) for g in ret[2:]]
+        g1 = [g.clone() for g in ret[4:]]
+        g2 = [torch.empty_like(g) for g in ret[4:]]
         dzc = dz.contiguous()
-        _lib.check(lib.cpc_encoder_backward(ptr(xx), ptr_array(params), ptr(dzc), ptr(saved), ptr(arena), ptr_array(g2), n, length,
-                                            hid, ctx.eps, stream_ptr(xx.device)), "second run")
+        _lib.check(lib.cpc_encoder_backward(ptr(xx), ptr(x2), n_first, ptr_array(params), ptr(dzc), ptr(saved), ptr(arena), ptr_array(g2),
+                                            n, length, hid, ctx.eps, 0, stream_ptr(xx.device)), "second run")
         tape.append(torch.stack([(a != b).sum() for a, b in zip(g1, g2)]))      # on-stream, read at the end
         return ret
 
