@@ -10,7 +10,9 @@
 // kernels fused with the residual add, and the ReLU+dropout elementwise pair.
 //
 // Dropout (p = 0.1 in training mode, transformers.py:16,112) uses a counter-based hash keyed by (seed, element
-// index): statistically equivalent to torch's, not stream-identical (parity is checked with p = 0).
+// index): statistically equivalent to torch's, not stream-identical (parity with the reference is checked with p = 0;
+// training mode in fp64 under the same masks rebuilt on the host: tests/test_transformer_dropout_gpu.py).  Mask layout: attention element ((n*8 + h)*chunks + c)*SS*SS + i*SS + j under
+// the layer's seed (seed + 0x1000*l), FFN activation element row*2048 + col under that seed ^ 0xFF.
 #include "common.h"
 #include "rowcfg.h"
 

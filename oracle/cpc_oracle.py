@@ -177,13 +177,17 @@ def relpos_bias(q, krelpos):
     return qp.reshape(b, s + 1, s)[:, 1:, :]
 
 
-def transformer_layer_forward(x, p, prefix, n_heads=8, size_seq=None, n_classifiers=1, pre_out=None):
-    """One TransformerLayer (transformers.py:119-134) in eval mode (dropout off).
+def transformer_layer_forward(x, p, prefix, n_heads=8, size_seq=None, n_classifiers=1, pre_out=None, drop=None):
+    """One TransformerLayer (transformers.py:119-134) in eval mode (dropout off), or with dropout under GIVEN masks.
     x [N, S, D] with S == sizeSeq (the training window).
     n_classifiers > 1: MultiClassifierTransformerHead (transformers.py:137-158): lin2 emits n_classifiers
     residual branches, output [N, S, n_classifiers, Dout].
     pre_out (test infrastructure): a list that receives the feed-forward net's pre-activations [N, S, dff] (detached) -- an
-    element within fp32 rounding of zero is a ReLU decision an fp32 evaluation may take the other way (see encoder_forward)."""
+    element within fp32 rounding of zero is a ReLU decision an fp32 evaluation may take the other way (see encoder_forward).
+    drop (test infrastructure): (att_mask, ffn_mask), the dropout multipliers (1 / (1 - p) or 0) of training mode in the
+    kernels' layout (oracle/dropmask.py): att_mask [n * n_heads * chunks, SS, SS] in the order (n_i * n_heads + h) * chunks + c
+    multiplies the softmax output (transformers.py:16, :67), ffn_mask [n * chunks * SS, dff] multiplies relu(lin1)
+    (transformers.py:112-116); chunks = the blocks of size_seq frames per sample, rows counted with the padding."""
     n, s, d = x.shape
     dk = d // n_heads
     if size_seq is not None and size_seq != s:
@@ -191,9 +195,15 @@ def transformer_layer_forward(x, p, prefix, n_heads=8, size_seq=None, n_classifi
         # the layer input is the same thing); the rows of the padding are dropped (:69)
         pad = (-s) % size_seq
         xp = torch.cat([x, torch.zeros(n, pad, d, dtype=x.dtype)], dim=1) if pad else x
-        blocks = xp.reshape(n * ((s + pad) // size_seq), size_seq, d)
+        chunks = (s + pad) // size_seq
+        blocks = xp.reshape(n * chunks, size_seq, d)
+        if drop is not None:
+            # block b = n_i * chunks + c: its heads' masks sit at (n_i * n_heads + h) * chunks + c, its FFN rows are contiguous
+            att_m, ffn_m = drop
+            att_m = att_m.view(n, n_heads, chunks, size_seq, size_seq).transpose(1, 2).reshape(n * chunks * n_heads, size_seq, size_seq)
+            drop = (att_m, ffn_m.view(n * chunks * size_seq, -1))
         out = transformer_layer_forward(blocks, p, prefix, n_heads=n_heads, size_seq=size_seq, n_classifiers=n_classifiers,
-                                        pre_out=pre_out)
+                                        pre_out=pre_out, drop=drop)
         return out.reshape((n, s + pad) + tuple(out.shape[2:]))[:, :s]
 
     def split(v):   # trans_ (transformers.py:89-91)
@@ -208,6 +218,8 @@ def transformer_layer_forward(x, p, prefix, n_heads=8, size_seq=None, n_classifi
         scores = scores + relpos_bias(q, p[key])
     mask = torch.triu(torch.full((s, s), float("-inf"), dtype=x.dtype), diagonal=1)
     att = torch.softmax(scores / math.sqrt(dk) + mask, dim=2)
+    if drop is not None:
+        att = att * drop[0].to(x.dtype).view(n * n_heads, s, s)
     y = (att @ v).view(n, n_heads, s, dk).transpose(1, 2).reshape(n, s, d)
     y = y @ p[f"{prefix}multihead.Wo.weight"].t()
     y = layer_norm(x + y, p[f"{prefix}ln_multihead.weight"], p[f"{prefix}ln_multihead.bias"])
@@ -215,6 +227,8 @@ def transformer_layer_forward(x, p, prefix, n_heads=8, size_seq=None, n_classifi
     if pre_out is not None:
         pre_out.append(ff.detach())
     ff = torch.relu(ff)
+    if drop is not None:
+        ff = ff * drop[1].to(x.dtype).view(n, s, -1)
     ff = ff @ p[f"{prefix}ffnetwork.lin2.weight"].t() + p[f"{prefix}ffnetwork.lin2.bias"]
     if n_classifiers > 1:            # transformers.py:153-158
         ff = ff.view(n, s, n_classifiers, d)

@@ -21,6 +21,7 @@ from cpc2_amd.criterion import _InfoNCEPredFn
 from cpc2_amd.train import buildOptimizer, cpcStep
 from oracle import cpc_oracle as O
 from oracle import synth
+from oracle.settle import settle_relu_decisions as _settle_relu_decisions
 from oracle.mt19937 import MT19937, negative_indices
 
 pytestmark = pytest.mark.gpu
@@ -314,35 +315,6 @@ def _multihead_once(p, k, prefix="wPrediction.predictor."):
             cache["c"], cache["out"] = c, O.transformer_layer_forward(c, p, f"{prefix}0.", n_classifiers=k)
         return cache["out"][:, :, i]
     return [(lambda c, i=i: pred(c, i)) for i in range(k)]
-
-
-RELU_MARGIN = 1e-5
-
-
-def _settle_relu_decisions(p, prefix, c_w, n_classifiers=1):
-    """Move every ReLU decision of the transformer's feed-forward net on the input c_w out of reach of fp32 rounding.
-
-    A one-layer predictor at these shapes evaluates 3 * 116 * 2048 pre-activations y lin1^T + b of size O(1); the smallest of
-    them in magnitude are ~1e-7 and below, i.e. inside the rounding error of their fp32 evaluation (a 256- or 512-term dot
-    product: a few 1e-7).  The kernel may then take relu'(pre) the other way than the fp64 oracle, and the gradients below that
-    unit differ by a WHOLE TERM -- measured on the parameters of synth seed 85 at d_model 256: pre = +3.6e-8 at (0, 70, unit
-    1466), the kernel's dx differs from the oracle's by 5.7e-3 of its scale at frame (0, 70) alone, and the oracle with that one
-    decision flipped reproduces the kernel's dx to 5e-7 -- which says nothing about the arithmetic under test (the encoder's
-    tests take the decisions from the kernel for the same reason: oracle.encoder_forward, masks).  Here the parameters are
-    made unambiguous instead, judged by the ORACLE's numbers alone: while a pre-activation lies within RELU_MARGIN = 1e-5 of
-    zero (30 x the rounding error), lin1.bias of its unit is raised by 3 RELU_MARGIN -- in the fp32 parameters both sides
-    load."""
-    bias = p[f"{prefix}ffnetwork.lin1.bias"]
-    for _ in range(50):
-        pre = []
-        with torch.no_grad():
-            O.transformer_layer_forward(c_w.double(), {n: v.double() for n, v in p.items() if n.startswith(prefix)}, prefix,
-                                        n_classifiers=n_classifiers, pre_out=pre)
-        near = (pre[0].abs() < RELU_MARGIN).reshape(-1, pre[0].shape[-1]).any(dim=0)
-        if not bool(near.any()):
-            return
-        bias[near] += 3 * RELU_MARGIN
-    raise AssertionError(f"{prefix}: the ReLU decisions did not settle")
 
 
 def _module_criterion(kind, h, k, nn, t_len, c_w=None, **kw):

@@ -1313,8 +1313,9 @@ def test_transformer_vs_oracle_fp64(d_model, size_seq, s, n):
 
 
 def test_transformer_dropout_training_mode():
-    """p = 0.1 in training mode: masks come from a hash (not torch's stream), so only properties are checked:
-    deterministic for a fixed seed, different from eval, finite gradients, E[out] close to eval output."""
+    """p = 0.1 in training mode: masks come from a hash (not torch's stream); properties only -- deterministic for a fixed
+    seed, different from eval, finite gradients.  The values are held to the fp64 oracle under the rebuilt masks by
+    tests/test_transformer_dropout_gpu.py."""
     params = synth.transformer_params(64, 64, 32, 91)
     net = load_transformer(64, 64, 32, params)
     x = synth.features((4, 32, 64), 92, relu=True).to(DEV).requires_grad_(True)
