@@ -43,6 +43,11 @@ struct cpc_mt19937 {
     hipEvent_t done = nullptr;
     int stream_device = -1;
     bool device_pending = false;      // `done` has been recorded and nobody has waited for it yet
+    // the draw ahead (cpc2_hip.h: the invariant): the state in front of it, the words it drew and how many of them callers took.
+    // Written by the worker's job and by the entry points, which wait for the worker first: never both at once.
+    uint32_t base_mt[624];
+    int base_left = 1, base_next = 0;
+    size_t drawn = 0, taken = 0;
 };
 
 namespace {
@@ -86,6 +91,24 @@ void draw(cpc_mt19937 *g, uint32_t *dst, size_t n)
         pos += take;
     }
 }
+
+// Put the generator behind exactly the words that were taken of the draw ahead (no-op when all were: a full hit redraws nothing)
+// and forget that draw.  Worker idle, or on the worker.
+void rebase(cpc_mt19937 *g)
+{
+    if (g->taken != g->drawn) {
+        std::memcpy(g->mt, g->base_mt, sizeof(g->mt));
+        g->left = g->base_left;
+        g->next = g->base_next;
+        g->tmp.resize(4096);
+        for (size_t done = 0; done < g->taken;) {
+            const size_t take = std::min<size_t>(4096, g->taken - done);
+            draw(g, g->tmp.data(), take);
+            done += take;
+        }
+    }
+    g->drawn = g->taken = 0;
+}
 }  // namespace
 
 extern "C" cpc_mt19937 *cpc_mt_create(uint32_t seed)
@@ -126,13 +149,6 @@ int join_job(cpc_mt19937 *g)
     return st;
 }
 
-// wait for the job in flight without taking its status (the next cpc_negidx_wait still reports it)
-void wait_idle(cpc_mt19937 *g)
-{
-    std::unique_lock<std::mutex> lk(g->mu);
-    g->cv.wait(lk, [g] { return !g->busy; });
-}
-
 void submit(cpc_mt19937 *g, std::function<int()> job)
 {
     std::unique_lock<std::mutex> lk(g->mu);
@@ -161,6 +177,14 @@ hipError_t worker_stream(cpc_mt19937 *g, int device, cpc_stream_t caller_stream)
     g->stream_device = device;
     return e;
 }
+
+// What every synchronous entry point that reads or moves the generator does first: wait for the worker (and, host-blocking, for
+// a device draw nobody took: its buffers' copy has no release event of its own), then stand behind the words taken.
+void settle(cpc_mt19937 *g)
+{
+    cpc_negidx_wait(g);
+    rebase(g);
+}
 }  // namespace
 
 extern "C" void cpc_mt_destroy(cpc_mt19937 *g)
@@ -181,7 +205,8 @@ extern "C" void cpc_mt_destroy(cpc_mt19937 *g)
 extern "C" int cpc_mt_seed(cpc_mt19937 *g, uint32_t seed)
 {
     if (g == nullptr) { cpc::set_error("cpc_mt_seed: null generator"); return CPC_ERR_INVALID; }
-    (void)join_job(g);
+    cpc_negidx_wait(g);
+    g->drawn = g->taken = 0;          // (a draw ahead is forgotten: the state is overwritten anyway)
     g->mt[0] = seed;
     for (int i = 1; i < N; ++i) g->mt[i] = 1812433253u * (g->mt[i - 1] ^ (g->mt[i - 1] >> 30)) + (uint32_t)i;
     g->left = 1;
@@ -192,7 +217,7 @@ extern "C" int cpc_mt_seed(cpc_mt19937 *g, uint32_t seed)
 extern "C" int cpc_mt_get_state(const cpc_mt19937 *g, uint32_t *mt624, int *left, int *next)
 {
     if (g == nullptr || mt624 == nullptr) { cpc::set_error("cpc_mt_get_state: null argument"); return CPC_ERR_INVALID; }
-    wait_idle(const_cast<cpc_mt19937 *>(g));               // (a draw in flight owns the generator until it is done)
+    settle(const_cast<cpc_mt19937 *>(g));
     std::memcpy(mt624, g->mt, sizeof(g->mt));
     if (left) *left = g->left;
     if (next) *next = g->next;
@@ -205,7 +230,8 @@ extern "C" int cpc_mt_set_state(cpc_mt19937 *g, const uint32_t *mt624, int left,
         cpc::set_error("cpc_mt_set_state: invalid state (left=%d next=%d)", left, next);
         return CPC_ERR_INVALID;
     }
-    wait_idle(g);
+    cpc_negidx_wait(g);
+    g->drawn = g->taken = 0;
     std::memcpy(g->mt, mt624, sizeof(g->mt));
     g->left = left;
     g->next = next;
@@ -293,19 +319,24 @@ extern "C" int cpc_negidx_stream(cpc_mt19937 *g, cpc_stream_t *out)
     return CPC_OK;
 }
 
-// The same hand-over WITHOUT blocking the host on the device: waits for the worker's host part (the draw and the enqueue of
-// copy + expansion), then makes `stream` wait for the event behind them.
-extern "C" int cpc_negidx_wait_on(cpc_mt19937 *g, cpc_stream_t stream)
+// The hand-over of a draw ahead WITHOUT blocking the host on the device: waits for the worker's host part (the draw and the enqueue
+// of copy + expansion), makes `stream` wait for the event behind them, and counts `words` more of the words drawn as taken.
+extern "C" int cpc_negidx_take(cpc_mt19937 *g, size_t words, cpc_stream_t stream)
 {
-    if (g == nullptr) { cpc::set_error("cpc_negidx_wait_on: null generator"); return CPC_ERR_INVALID; }
+    if (g == nullptr) { cpc::set_error("cpc_negidx_take: null generator"); return CPC_ERR_INVALID; }
     const int st = join_job(g);
+    if (words > g->drawn - g->taken) {
+        cpc::set_error("cpc_negidx_take: %zu words, %zu of the %zu drawn ahead are left", words, g->drawn - g->taken, g->drawn);
+        return CPC_ERR_INVALID;
+    }
     if (g->device_pending) {
         g->device_pending = false;
         if (hipStreamWaitEvent(static_cast<hipStream_t>(stream), g->done, 0) != hipSuccess && st == CPC_OK) {
-            cpc::set_error("cpc_negidx_wait_on: hipStreamWaitEvent failed");
+            cpc::set_error("cpc_negidx_take: hipStreamWaitEvent failed");
             return CPC_ERR_HIP;
         }
     }
+    g->taken += words;
     return st;
 }
 
@@ -314,7 +345,7 @@ extern "C" int cpc_negidx_sample_host(cpc_mt19937 *g, int batch, int seq_len, in
 {
     const int st = check_args(g, batch, seq_len, window, n_neg, ext_idx_host);
     if (st != CPC_OK) return st;
-    cpc_negidx_wait(g);      // an asynchronous sample (if any) owns the generator until it is done
+    settle(g);
     return sample_impl(g, batch, seq_len, window, n_neg, time_major, ext_idx_host, batch_idx_host_opt, seq_idx_host_opt);
 }
 
@@ -323,16 +354,8 @@ extern "C" int cpc_negidx_sample_host(cpc_mt19937 *g, int batch, int seq_len, in
 extern "C" int cpc_mt_draw_host(cpc_mt19937 *g, uint32_t *raw_host, size_t n)
 {
     if (g == nullptr || raw_host == nullptr) { cpc::set_error("cpc_mt_draw_host: null argument"); return CPC_ERR_INVALID; }
-    cpc_negidx_wait(g);
+    settle(g);
     draw(g, raw_host, n);
-    return CPC_OK;
-}
-
-extern "C" int cpc_mt_draw_host_async(cpc_mt19937 *g, uint32_t *raw_host, size_t n)
-{
-    if (g == nullptr || raw_host == nullptr) { cpc::set_error("cpc_mt_draw_host_async: null argument"); return CPC_ERR_INVALID; }
-    cpc_negidx_wait(g);
-    submit(g, [=] { draw(g, raw_host, n); return (int)CPC_OK; });
     return CPC_OK;
 }
 
@@ -341,7 +364,7 @@ extern "C" int cpc_negidx_expand(const uint32_t *raw, int32_t *ext_idx, int batc
                                  cpc_stream_t stream) __attribute__((weak));
 
 // draw on the worker thread, upload from the (pinned) staging buffer on the worker's stream and -- ext_dev != nullptr -- expand
-// there too; `done` is recorded behind it: cpc_negidx_wait (host) / cpc_negidx_wait_on (a stream) hand the result over
+// there too; `done` is recorded behind it: cpc_negidx_wait (host) / cpc_negidx_take (a stream) hand the result over
 static int device_job(cpc_mt19937 *g, uint32_t *raw_host, uint32_t *raw_dev, int32_t *ext_dev, size_t n, int device,
                       int batch, int seq_len, int window, int n_neg, cpc_stream_t caller_stream, const char *who)
 {
@@ -356,61 +379,28 @@ static int device_job(cpc_mt19937 *g, uint32_t *raw_host, uint32_t *raw_dev, int
     return e != hipSuccess ? (int)CPC_ERR_HIP : rc;
 }
 
-extern "C" int cpc_mt_draw_device_async(cpc_mt19937 *g, uint32_t *raw_host, uint32_t *raw_dev, size_t n, int device,
-                                        cpc_stream_t caller_stream)
+// The draw ahead: the NEXT call's 2 * batch * n_neg * window words, drawn on the worker thread while the caller goes on.  With
+// raw_dev / ext_dev the worker also uploads and EXPANDS them on its stream (cpc_negidx_expand): step i + 1's index tensor is
+// complete on the device before step i has ended, and nothing of the sampler is left on the training stream.  Both NULL: words
+// into raw_host, no HIP call.  The worker first settles the draw ahead before this one (rebase) and notes where this one starts.
+extern "C" int cpc_negidx_draw_ahead(cpc_mt19937 *g, uint32_t *raw_host, uint32_t *raw_dev, int32_t *ext_dev, int device,
+                                     int batch, int seq_len, int window, int n_neg, cpc_stream_t caller_stream)
 {
-    if (g == nullptr || raw_host == nullptr || raw_dev == nullptr) { cpc::set_error("cpc_mt_draw_device_async: null argument"); return CPC_ERR_INVALID; }
-    cpc_negidx_wait(g);
-    submit(g, [=] { return device_job(g, raw_host, raw_dev, nullptr, n, device, 0, 0, 0, 0, caller_stream, "cpc_mt_draw_device_async"); });
-    return CPC_OK;
-}
-
-// The same, and the worker also EXPANDS the words into extIdx on its stream (cpc_negidx_expand): step i + 1's index tensor is
-// complete on the device before step i has ended, and nothing of the sampler is left on the training stream.
-extern "C" int cpc_mt_draw_expand_device_async(cpc_mt19937 *g, uint32_t *raw_host, uint32_t *raw_dev, int32_t *ext_dev, int device,
-                                               int batch, int seq_len, int window, int n_neg, cpc_stream_t caller_stream)
-{
-    if (g == nullptr || raw_host == nullptr || raw_dev == nullptr || ext_dev == nullptr || batch < 1 || seq_len < 2 || window < 1 || n_neg < 1) {
-        cpc::set_error("cpc_mt_draw_expand_device_async: bad argument");
+    if (g == nullptr || raw_host == nullptr || (raw_dev == nullptr) != (ext_dev == nullptr) || batch < 1 || seq_len < 2 || window < 1 || n_neg < 1) {
+        cpc::set_error("cpc_negidx_draw_ahead: bad argument");
         return CPC_ERR_INVALID;
     }
-    if (cpc_negidx_expand == nullptr) { cpc::set_error("cpc_mt_draw_expand_device_async: built without the device kernels"); return CPC_ERR_HIP; }
+    if (raw_dev != nullptr && cpc_negidx_expand == nullptr) { cpc::set_error("cpc_negidx_draw_ahead: built without the device kernels"); return CPC_ERR_HIP; }
     const size_t n = 2 * (size_t)batch * n_neg * window;
-    cpc_negidx_wait(g);
-    submit(g, [=] { return device_job(g, raw_host, raw_dev, ext_dev, n, device, batch, seq_len, window, n_neg, caller_stream,
-                                      "cpc_mt_draw_expand_device_async"); });
-    return CPC_OK;
-}
-
-// The same draw ahead, preceded ON THE WORKER by a repositioning of the generator: state (mt624, left, next) is restored and
-// `skip_words` outputs are generated and dropped.  For a draw ahead whose words were used only in part (the call that followed was
-// smaller: its 2 n words are a PREFIX of the 2 n' drawn, the stream being one sequence whatever it is cut into): the generator
-// has to stand behind the words that WERE consumed before the next draw, and the caller does not wait for that.
-extern "C" int cpc_mt_redraw_expand_device_async(cpc_mt19937 *g, const uint32_t *restore_mt624, int restore_left, int restore_next,
-                                                 size_t skip_words, uint32_t *raw_host, uint32_t *raw_dev, int32_t *ext_dev, int device,
-                                                 int batch, int seq_len, int window, int n_neg, cpc_stream_t caller_stream)
-{
-    if (g == nullptr || restore_mt624 == nullptr || raw_host == nullptr || raw_dev == nullptr || ext_dev == nullptr || batch < 1 || seq_len < 2 ||
-        window < 1 || n_neg < 1 || restore_left < 1 || restore_left > N || restore_next < 0 || restore_next > N ||
-        (restore_left > 1 && restore_next + restore_left - 1 != N)) {
-        cpc::set_error("cpc_mt_redraw_expand_device_async: bad argument");
-        return CPC_ERR_INVALID;
-    }
-    if (cpc_negidx_expand == nullptr) { cpc::set_error("cpc_mt_redraw_expand_device_async: built without the device kernels"); return CPC_ERR_HIP; }
-    const size_t n = 2 * (size_t)batch * n_neg * window;
-    std::vector<uint32_t> st(restore_mt624, restore_mt624 + N);
     cpc_negidx_wait(g);
     submit(g, [=] {
-        std::memcpy(g->mt, st.data(), sizeof(g->mt));
-        g->left = restore_left;
-        g->next = restore_next;
-        g->tmp.resize(4096);
-        for (size_t done = 0; done < skip_words;) {
-            const size_t take = std::min<size_t>(4096, skip_words - done);
-            draw(g, g->tmp.data(), take);
-            done += take;
-        }
-        return device_job(g, raw_host, raw_dev, ext_dev, n, device, batch, seq_len, window, n_neg, caller_stream, "cpc_mt_redraw_expand_device_async");
+        rebase(g);
+        std::memcpy(g->base_mt, g->mt, sizeof(g->mt));
+        g->base_left = g->left;
+        g->base_next = g->next;
+        g->drawn = n;
+        if (raw_dev == nullptr) { draw(g, raw_host, n); return (int)CPC_OK; }
+        return device_job(g, raw_host, raw_dev, ext_dev, n, device, batch, seq_len, window, n_neg, caller_stream, "cpc_negidx_draw_ahead");
     });
     return CPC_OK;
 }
@@ -422,7 +412,7 @@ extern "C" int cpc_negidx_sample_host_async(cpc_mt19937 *g, int batch, int seq_l
 {
     const int st = check_args(g, batch, seq_len, window, n_neg, ext_idx_host);
     if (st != CPC_OK) return st;
-    cpc_negidx_wait(g);
+    settle(g);
     submit(g, [=] { return sample_impl(g, batch, seq_len, window, n_neg, time_major, ext_idx_host, nullptr, nullptr); });
     return CPC_OK;
 }

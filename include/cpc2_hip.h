@@ -47,7 +47,8 @@ int cpc_version(void);          /* 100 x major + minor; 105 = the entry points o
                                   * 109 = cpc_probe_xent / cpc_probe_head_backward / cpc_probe_ctc / cpc_probe_collapse (+ scratch queries);
                                   * 110 = cpc_abx_dtw_units (+ scratch query); 111 = cpc_augment_*; 112 = cpc_resample_*;
                                   * 113 = cpc_text_*;
-                                  * 114 = one forward and one backward entry point per op: x_rest / n_first, c_frames, `deferred` */
+                                  * 114 = one forward and one backward entry point per op: x_rest / n_first, c_frames, `deferred`;
+                                  * 115 = the library owns the sampler's draw ahead: cpc_negidx_draw_ahead / cpc_negidx_take */
 const char *cpc_last_error(void);
 
 /* In-situ kernel timing for bench.py: when enabled, the launchers bracket each launch of the named
@@ -326,26 +327,25 @@ int cpc_negidx_wait(cpc_mt19937 *g);
  * device reduces them (% batch, % (T-1) + 1), applies the time offset and writes the time-major extIdx.
  * Integer-exact: cpc_negidx_expand(raw) == cpc_negidx_sample_host(time_major = 1). */
 int cpc_mt_draw_host(cpc_mt19937 *g, uint32_t *raw_host, size_t n);
-int cpc_mt_draw_host_async(cpc_mt19937 *g, uint32_t *raw_host, size_t n);
-/* ... and uploaded by the worker on its own stream (raw_host pinned): raw_dev holds the words once
- * cpc_negidx_wait returns, so no copy sits on the training stream. */
-int cpc_mt_draw_device_async(cpc_mt19937 *g, uint32_t *raw_host, uint32_t *raw_dev, size_t n, int device,
-                             cpc_stream_t caller_stream);
-/* ... and expanded there too (cpc_negidx_expand on the worker's stream): the two torch.randint calls AND the index arithmetic of
- * criterion.py:247-266 for step i + 1, done while step i runs.  The worker is ONE thread per generator with ONE stream, made on its
- * first device job apart from `caller_stream`'s hardware queue (cpc_stream_create_apart); an event is recorded behind the job.
- * ext_dev [batch * window * n_neg] may be read by the host's device work after cpc_negidx_wait (blocks the host until the device
- * has it) or, without blocking the host on the device, by everything enqueued on `stream` after cpc_negidx_wait_on(g, stream). */
-int cpc_mt_draw_expand_device_async(cpc_mt19937 *g, uint32_t *raw_host, uint32_t *raw_dev, int32_t *ext_dev, int device,
-                                    int batch, int seq_len, int window, int n_neg, cpc_stream_t caller_stream);
-/* ... preceded on the worker by a repositioning of the generator: the state (mt624, left, next) is restored and skip_words outputs
- * are generated and dropped.  For a draw ahead of which a SMALLER call used only a prefix (its 2 n words are the first 2 n of the
- * stream whatever it is cut into): the generator has to stand behind the consumed words before the next draw, and the caller does
- * not wait for that. */
-int cpc_mt_redraw_expand_device_async(cpc_mt19937 *g, const uint32_t *restore_mt624, int restore_left, int restore_next,
-                                      size_t skip_words, uint32_t *raw_host, uint32_t *raw_dev, int32_t *ext_dev, int device,
-                                      int batch, int seq_len, int window, int n_neg, cpc_stream_t caller_stream);
-int cpc_negidx_wait_on(cpc_mt19937 *g, cpc_stream_t stream);
+/* The draw AHEAD: the next call's 2*n words, drawn by the worker while the caller goes on.  The library keeps where the generator
+ * stood in front of that draw, how many words it drew and how many of them callers took, so that
+ *     SEEN THROUGH ANY SYNCHRONOUS ENTRY POINT, THE GENERATOR STANDS BEHIND EXACTLY THE WORDS CALLERS HAVE TAKEN:
+ * cpc_mt_draw_host, cpc_negidx_sample_host(_async) and cpc_mt_get_state first wait for the worker as cpc_negidx_wait does (that
+ * blocks the host on a device draw nobody took) and, unless every word drawn ahead was taken, go back to the state in front of
+ * the draw and generate the taken words again; cpc_mt_set_state and cpc_mt_seed wait and forget the draw.  A draw ahead that is
+ * not taken, or taken in part, is thereby undone without anyone asking for it; one that is taken whole costs nothing.
+ * cpc_negidx_draw_ahead: the worker (ONE thread per generator with ONE stream, made on its first device job apart from
+ *   `caller_stream`'s hardware queue: cpc_stream_create_apart) settles the draw ahead before this one in the same way, draws
+ *   2 * batch * n_neg * window words into raw_host (pinned), copies them to raw_dev and expands them into ext_dev
+ *   [batch * window * n_neg] on its stream -- the two torch.randint calls AND the index arithmetic of criterion.py:247-266 for
+ *   step i + 1, done while step i runs -- and records an event behind them.  raw_dev == ext_dev == NULL: words into raw_host
+ *   only, no HIP call.
+ * cpc_negidx_take: the caller uses the next `words` of the words drawn ahead (at most those left of them, else CPC_ERR_INVALID):
+ *   waits for the worker's HOST part and makes `stream` (may be NULL after a host-only draw) wait for the event, so that
+ *   everything enqueued on it afterwards may read raw_dev / ext_dev; the host is not blocked on the device. */
+int cpc_negidx_draw_ahead(cpc_mt19937 *g, uint32_t *raw_host, uint32_t *raw_dev, int32_t *ext_dev, int device,
+                          int batch, int seq_len, int window, int n_neg, cpc_stream_t caller_stream);
+int cpc_negidx_take(cpc_mt19937 *g, size_t words, cpc_stream_t stream);
 int cpc_negidx_stream(cpc_mt19937 *g, cpc_stream_t *out);      /* the worker's stream (NULL before its first device job) */
 int cpc_negidx_expand(const uint32_t *raw, int32_t *ext_idx, int batch, int seq_len, int window, int n_neg,
                       cpc_stream_t stream);

@@ -119,18 +119,41 @@ int main(int argc, char **argv)
         for (size_t i = 0; i < n; ++i)
             if (e1[i] < 0 || e1[i] >= b * T || bi[i] < 0 || bi[i] >= b || si[i] < 1 || si[i] >= T) { fprintf(stderr, "index out of range\n"); return 1; }
         if (cpc_mt_draw_host(g1, raw1.data(), 2 * n) != CPC_OK) return 1;
-        if (cpc_mt_draw_host_async(g2, raw2.data(), 2 * n) != CPC_OK) return 1;
+        if (cpc_negidx_draw_ahead(g2, raw2.data(), nullptr, nullptr, 0, b, T, W, nneg, nullptr) != CPC_OK) return 1;   // host form: 2 n words
+        if (cpc_negidx_take(g2, 2 * n, nullptr) != CPC_OK) return 1;
         // a second request while the first is in flight must wait for it, not race it
         if (cpc_mt_draw_host(g2, raw2.data(), 0) != CPC_OK) return 1;
         if (memcmp(raw1.data(), raw2.data(), 2 * n * sizeof(uint32_t)) != 0) { fprintf(stderr, "async draw differs\n"); return 1; }
     }
+    // the draw ahead: whatever part of it is taken, the next synchronous draw goes on behind exactly the words taken.  `want` is
+    // the straight stream of g1 from here on; g2 stands where g1 does (the loop above took every draw ahead whole)
+    std::vector<uint32_t> want(12 * n), got(2 * n), sync(n);
+    if (cpc_mt_draw_host(g1, want.data(), want.size()) != CPC_OK) return 1;
+    size_t at = 0;                                          // words of `want` that callers of g2 have received
+    auto ahead = [&] { return cpc_negidx_draw_ahead(g2, got.data(), nullptr, nullptr, 0, b, T, W, nneg, nullptr) == CPC_OK; };
+    auto took = [&](size_t words) {                         // the first `words` of the draw ahead are the stream's next ones
+        if (cpc_negidx_take(g2, words, nullptr) != CPC_OK || memcmp(got.data(), want.data() + at, words * sizeof(uint32_t)) != 0) return false;
+        at += words;
+        return true;
+    };
+    auto synchronous = [&](size_t words) {
+        if (cpc_mt_draw_host(g2, sync.data(), words) != CPC_OK || memcmp(sync.data(), want.data() + at, words * sizeof(uint32_t)) != 0) return false;
+        at += words;
+        return true;
+    };
+    const size_t part = 2 * 2 * nneg * W + 1;               // a smaller call's words and one more: an odd count
+    if (!ahead() || !took(part) || !synchronous(n)) { fprintf(stderr, "a draw after a partial take does not continue behind the words taken\n"); return 1; }
+    if (!ahead() || !synchronous(n)) { fprintf(stderr, "a draw after an untaken draw ahead does not continue where that one started\n"); return 1; }
+    if (!ahead() || !took(part) || !ahead() || !took(2 * n) || !synchronous(n)) { fprintf(stderr, "the worker did not settle a partial take in front of the next draw ahead\n"); return 1; }
+    if (!ahead() || cpc_negidx_take(g2, 2 * n + 1, nullptr) != CPC_ERR_INVALID || strstr(cpc::g_err, "cpc_negidx_take") == nullptr || !took(2 * n) ||
+        cpc_negidx_take(g2, 1, nullptr) != CPC_ERR_INVALID) { fprintf(stderr, "a take of more than was drawn was not refused\n"); return 1; }
     uint32_t st[624];
     int left = 0, next = 0;
     if (cpc_mt_get_state(g1, st, &left, &next) != CPC_OK || cpc_mt_set_state(g2, st, left, next) != CPC_OK) return 1;
     if (cpc_mt_set_state(g2, st, 0, 0) == CPC_OK || cpc_mt_set_state(g2, st, 700, 3) == CPC_OK) { fprintf(stderr, "bad state accepted\n"); return 1; }
     if (cpc_negidx_sample_host(g1, 0, T, W, nneg, 0, e1.data(), nullptr, nullptr) == CPC_OK) return 1;     // bad arguments are refused
     if (cpc_negidx_sample_host(g1, b, T, T + 1, nneg, 0, e1.data(), nullptr, nullptr) == CPC_OK) return 1;
-    cpc_mt_draw_host_async(g2, raw2.data(), 2 * n);          // destroyed with a draw in flight: must join, not leak or race
+    cpc_negidx_draw_ahead(g2, raw2.data(), nullptr, nullptr, 0, b, T, W, nneg, nullptr);          // destroyed with a draw in flight: must join, not leak or race
     cpc_mt_destroy(g1);
     cpc_mt_destroy(g2);
     printf("host sanitizer driver ok: %ld fixtures decoded, %ld mutants (%ld rejected, the rest decoded to something), sampler paths exercised\n",

@@ -241,6 +241,64 @@ def test_lr_schedules_follow_the_reference(tag, step, ramp, done):
     assert np.allclose(lrs, ref, rtol=1e-12, atol=0)
 
 
+# ----------------------------------------------------------------------------- sampler: the draw ahead's bookkeeping (cpc2_hip.h)
+def test_sampler_draw_ahead_keeps_one_stream():
+    """cpc2_hip.h: seen through any synchronous entry point, the generator stands behind exactly the words callers have taken.  The
+    host form of the draw ahead (no device buffers: no HIP call) through ctypes, against the oracle's generator word for word: a
+    seeded plan of draws ahead of m words, takes of j <= m of them (none, some, all, in one or several takes), synchronous draws of
+    r words and get_state / set_state round trips, sizes from 1 to 3000 so that takes and settles straddle the 624-word twist.
+    Every word a caller receives is the next word of the one stream, and the state read back is the oracle's behind those words.
+    (A draw ahead is 2 * batch * n_neg * window words, so m is even; j and r are not.)"""
+    from oracle.mt19937 import MT19937
+    lib, seed = _lib.load(), 20240607
+    g = ctypes.c_void_p(lib.cpc_mt_create(seed))
+    oracle, rs = MT19937(seed), np.random.RandomState(5)
+    ahead, left_of_it, seen = None, 0, []          # the buffer of the draw ahead, how many of its words nobody took yet
+
+    def words_ptr(a):
+        return a.ctypes.data_as(ctypes.c_void_p)
+
+    try:
+        for step in range(40):
+            kinds = ["ahead", "draw", "state"] + (["take", "take"] if left_of_it else [])
+            kind = kinds[rs.randint(len(kinds))]
+            seen.append((kind, left_of_it > 0))
+            if kind == "ahead":                                 # (words of the one before it that nobody took were never drawn)
+                m = 2 * int(rs.randint(1, 1501))
+                buf = np.zeros(m, dtype=np.uint32)               # (the one before it may still be written: it lives until the call returns)
+                _lib.check(lib.cpc_negidx_draw_ahead(g, words_ptr(buf), None, None, 0, m // 2, 2, 1, 1, None), "negidx_draw_ahead")
+                ahead, left_of_it = buf, m
+            elif kind == "take":
+                j = int(rs.choice([0, left_of_it, rs.randint(0, left_of_it + 1)]))
+                _lib.check(lib.cpc_negidx_take(g, j, None), "negidx_take")
+                at = len(ahead) - left_of_it
+                assert np.array_equal(ahead[at:at + j], oracle.draw(j)), (step, "take", j)
+                left_of_it -= j
+            elif kind == "draw":
+                r = int(rs.randint(1, 3001))
+                got = np.zeros(r, dtype=np.uint32)
+                _lib.check(lib.cpc_mt_draw_host(g, words_ptr(got), r), "mt_draw_host")
+                assert np.array_equal(got, oracle.draw(r)), (step, "draw", r)
+                left_of_it = 0
+            else:
+                mt, left, nxt = np.zeros(624, dtype=np.uint32), ctypes.c_int(0), ctypes.c_int(0)
+                _lib.check(lib.cpc_mt_get_state(g, words_ptr(mt), ctypes.byref(left), ctypes.byref(nxt)), "mt_get_state")
+                assert (left.value, nxt.value) == (oracle.left, oracle.next) and np.array_equal(mt, oracle.mt), (step, "state")
+                _lib.check(lib.cpc_mt_set_state(g, words_ptr(mt), left.value, nxt.value), "mt_set_state")
+                left_of_it = 0
+        # the plan met what it is for: a synchronous draw, a state read and another draw ahead, each behind words left untaken
+        for kind in ("draw", "state", "ahead"):
+            assert (kind, True) in seen, (kind, seen)
+        buf = np.zeros(10, dtype=np.uint32)
+        _lib.check(lib.cpc_negidx_draw_ahead(g, words_ptr(buf), None, None, 0, 5, 2, 1, 1, None), "negidx_draw_ahead")
+        assert lib.cpc_negidx_take(g, 11, None) == -1 and b"cpc_negidx_take" in lib.cpc_last_error()      # CPC_ERR_INVALID, by name
+        _lib.check(lib.cpc_negidx_take(g, 4, None), "negidx_take")
+        assert lib.cpc_negidx_take(g, 7, None) == -1
+        assert np.array_equal(buf[:4], oracle.draw(4))
+    finally:
+        lib.cpc_mt_destroy(g)
+
+
 # ----------------------------------------------------------------------------- sampler: random shapes (criterion.py:247-266)
 def test_sampler_matches_torch_randint_on_random_shapes():
     """Property test over ragged shapes: the native MT19937 sampler reproduces, bit for bit, the index arithmetic of

@@ -3011,3 +3011,32 @@ def test_prefetch_under_torchs_global_generator_is_bit_exact():
     for i, ((a, sa), (c, sc)) in enumerate(zip(*results)):
         assert torch.equal(a, c), f"call {i}: indices differ with prefetch"
         assert torch.equal(sa, sc), f"call {i}: torch's generator state differs with prefetch"
+
+
+
+def test_prefetch_serves_calls_by_the_fast_paths():
+    """The bit-exact tests above pass just as well when every call takes the slow path; `served` tells.  By the rules of
+    NegativeSampler.sample: the draws ahead are made for the largest call seen, so on a private stream the first call and a LARGER
+    one draw for themselves, the call drawn for is served ahead and a smaller one from a prefix of the words on the device;
+    under torch's generator a smaller call draws for itself (no prefix there) and the draws ahead stay with the large size."""
+    t_len, k, nn = 64, 12, 32
+    plans = [(False, [8, 8, 5, 8, 3, 3, 8, 12, 12], ["drawn", "ahead", "prefix", "ahead", "prefix", "prefix", "ahead", "drawn", "ahead"]),
+             (True, [8, 8, 5, 8], ["drawn", "ahead", "drawn", "ahead"])]
+    for follow_torch, sizes, want_served in plans:
+        ref, dev = cpc2_amd.criterion.NegativeSampler(), cpc2_amd.criterion.NegativeSampler()
+        if follow_torch:
+            torch.manual_seed(33)
+        else:
+            ref.seed(33)
+            dev.seed(33)
+        want = [ref.sample_host(b, t_len, t_len - k, nn, time_major=True).clone() for b in sizes]
+        if follow_torch:
+            torch.manual_seed(33)
+        assert dev.prefetch and dev.follow_torch == follow_torch and not dev.served
+        served = []
+        for i, b in enumerate(sizes):
+            before = dev.served.copy()
+            got = dev.sample(b, t_len, t_len - k, nn, torch.device(DEV))
+            assert torch.equal(got.cpu(), want[i]), (follow_torch, i, b)
+            served += list((dev.served - before).elements())
+        assert served == want_served, (follow_torch, served)
