@@ -129,6 +129,9 @@ SIGNATURES = {
     "cpc_text_format_i64": (c_int, [c_ptr, c_long, c_ptr, c_ptr, c_ptr]),
     "cpc_text_row_bytes": (c_int, [c_ptr, c_long, c_int, c_ptr, c_ptr, c_ptr]),
     "cpc_text_pack": (c_int, [c_ptr, c_ptr, c_long, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_long, c_ptr]),
+    "cpc_ctc_beam_search_scratch_bytes": (c_size_t, [c_int] * 4),
+    "cpc_ctc_beam_search": (c_int, [c_ptr, c_ptr] + [c_int] * 6 + [c_ptr] * 6 + [c_size_t, c_ptr]),
+    "cpc_align_score": (c_int, [c_ptr, c_long, c_ptr, c_ptr, c_long, c_ptr] + [c_int] * 4 + [c_ptr, c_ptr]),
 }
 
 _lib = None

@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcpc2_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-SOURCES = ["gemm_f32.hip", "gemm_planes.hip", "rowops.hip", "encoder.hip", "gru.hip", "lstm.hip", "infonce.hip", "side_stream.hip", "transformer.hip", "abx.hip", "abx_units.hip", "kmeans.hip", "probe.hip", "augment.hip", "resample.hip", "text.hip", "negidx.cpp", "flac.cpp"]
+SOURCES = ["gemm_f32.hip", "gemm_planes.hip", "rowops.hip", "encoder.hip", "gru.hip", "lstm.hip", "infonce.hip", "side_stream.hip", "transformer.hip", "abx.hip", "abx_units.hip", "kmeans.hip", "probe.hip", "augment.hip", "resample.hip", "text.hip", "seqalign.hip", "negidx.cpp", "flac.cpp"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-pthread"]
 # Device code is built WITHOUT the packed-f32 VALU instructions (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32).  Round 3 found
 # (profiles/r03_dp_rootcause.md; tools/load_determinism_probe.py reproduces it) that kernels which hipcc
@@ -17,6 +17,10 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-pthrea
 # instructions, 0 of 1 260 without, at no measurable cost (5.42 against 5.43-5.64 ms per step; the guide lists packed f32
 # beside MFMAs as an anti-lever anyway).  The host pass does not know the feature and says so: that line is filtered.
 DEVICE_FLAGS = ["--offload-arch=gfx950", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+# seqalign.hip restates a float32 numpy program operation for operation: a product and the sum behind it must stay two roundings.
+# hipcc's default (-ffp-contract=fast) fuses them whatever the source says (__fmul_rn / __fadd_rn are plain operators, a pragma
+# is not honoured), so contraction is off for that file.
+FILE_FLAGS = {"seqalign.hip": ["-ffp-contract=off"]}
 
 
 def _newer(target, deps):
@@ -38,7 +42,7 @@ def build(force=False, verbose=True):
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
         if not force and _newer(obj, [src] + headers):
             return obj
-        cmd = [HIPCC] + FLAGS + (DEVICE_FLAGS if src.endswith(".hip") else []) + ["-c", src, "-o", obj]
+        cmd = [HIPCC] + FLAGS + (DEVICE_FLAGS if src.endswith(".hip") else []) + FILE_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
         if verbose:
             print(" ".join(cmd), flush=True)
         res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)

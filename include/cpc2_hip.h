@@ -48,7 +48,8 @@ int cpc_version(void);          /* 100 x major + minor; 105 = the entry points o
                                   * 110 = cpc_abx_dtw_units (+ scratch query); 111 = cpc_augment_*; 112 = cpc_resample_*;
                                   * 113 = cpc_text_*;
                                   * 114 = one forward and one backward entry point per op: x_rest / n_first, c_frames, `deferred`;
-                                  * 115 = the library owns the sampler's draw ahead: cpc_negidx_draw_ahead / cpc_negidx_take */
+                                  * 115 = the library owns the sampler's draw ahead: cpc_negidx_draw_ahead / cpc_negidx_take;
+                                  * 116 = cpc_ctc_beam_search (+ scratch query) / cpc_align_score */
 const char *cpc_last_error(void);
 
 /* In-situ kernel timing for bench.py: when enabled, the launchers bracket each launch of the named
@@ -617,6 +618,40 @@ int cpc_text_format_i64(const long *x, long count, unsigned long long *slots, un
 int cpc_text_row_bytes(const unsigned char *len, long rows, int cols, const long *prefix_off, long *row_bytes, cpc_stream_t stream);
 int cpc_text_pack(const unsigned long long *slots, const unsigned char *len, long rows, int cols, const unsigned char *prefix,
                   const long *prefix_off, const long *row_off, unsigned char *out, long out_total, cpc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Phone error rate of a CTC probe (cpc/criterion/seq_alignment.py of the reference; cpc2_amd/seq_alignment.py).  version 116.
+ * Every pointer is a DEVICE pointer, row-major and contiguous; labels and lengths are int32.
+ *
+ * cpc_ctc_beam_search: beam_search (seq_alignment.py:11-61) of n sequences.  probs [n][t_max][p] are probabilities (not logs),
+ *   lengths[i] the frames of sequence i to decode (clamped to [0, t_max]; rows beyond it are never read), blank any class in
+ *   [0, p).  Limits: 1 <= n_keep <= 128, 2 <= p <= 128 (a frame's n_keep * p candidates are held in LDS), t_max <= 8192;
+ *   anything else is CPC_ERR_INVALID.  With R = n_keep (best_only == 0) or R = 1 (best_only != 0, the best prefix only):
+ *     scores [n][R]        pb + pnb of the kept prefixes, best first; 0 behind the last one
+ *     out_lengths [n][R]   their label counts; 0 behind the last one
+ *     labels [n][R][t_max] their labels, -1 behind each prefix's last label
+ *     counts [n]           how many of the R rows hold a prefix (fewer than n_keep exist only in the first frames)
+ *     ties [n]             1 when some frame met two equal scores among its first n_keep + 1 candidates, else 0
+ *   The arithmetic is the reference's, operation for operation, in f32 with subnormals kept and no fused multiply-add:
+ *   pb' = (pnb + pb) p[blank]; pnb' = pnb p[last] for the prefix itself, plus pb p[c] when c repeats the last label of the
+ *   prefix it extends and (pb + pnb) p[c] otherwise; score = pb + pnb.  Without ties the output equals the reference's bit for
+ *   bit.  EQUAL scores are ordered by (rank of the extended prefix in the previous frame's beam, symbol), an unextended prefix
+ *   counting as its own rank with symbol = blank; the reference orders them by the prefixes' decimal strings, which is not
+ *   reproduced.  The order is a function of the inputs alone: two launches give the same bytes.
+ *   scratch: cpc_ctc_beam_search_scratch_bytes(n, t_max, p, n_keep) (per sequence a trie of at most 1 + t_max * n_keep prefixes
+ *   and its (parent, symbol) table; 0 with a message for sizes outside the limits); too little gives CPC_ERR_WORKSPACE.
+ * cpc_align_score: NeedlemanWunschAlignScore (seq_alignment.py:89-112) of n pairs without its normalisation:
+ *   score[i] = -H[len1[i]][len2[i]] with H[a][0] = a d, H[0][b] = b d and
+ *   H[a+1][b+1] = max(H[a][b] + (seq1[i][a] == seq2[i][b] ? r : m), H[a+1][b] + d, H[a][b+1] + d): integers, exact.
+ *   seq1 [n][ld1], seq2 [n][ld2] (1 <= ld <= 4096; lengths clamped to [0, ld]; padding is not read), |d|, |m|, |r| <= 32768.
+ *   get_seq_PER of the reference is d = m = -1, r = 0 and score / len1.
+ * ------------------------------------------------------------------------------------------ */
+size_t cpc_ctc_beam_search_scratch_bytes(int n, int t_max, int p, int n_keep);
+int cpc_ctc_beam_search(const float *probs, const int *lengths, int n, int t_max, int p, int n_keep, int blank, int best_only,
+                        float *scores, int *out_lengths, int *labels, int *counts, int *ties, void *scratch, size_t scratch_bytes,
+                        cpc_stream_t stream);
+int cpc_align_score(const int *seq1, long ld1, const int *len1, const int *seq2, long ld2, const int *len2, int n, int d, int m,
+                    int r, int *score, cpc_stream_t stream);
 
 #ifdef __cplusplus
 }
