@@ -132,6 +132,14 @@ SIGNATURES = {
     "cpc_ctc_beam_search_scratch_bytes": (c_size_t, [c_int] * 4),
     "cpc_ctc_beam_search": (c_int, [c_ptr, c_ptr] + [c_int] * 6 + [c_ptr] * 6 + [c_size_t, c_ptr]),
     "cpc_align_score": (c_int, [c_ptr, c_long, c_ptr, c_ptr, c_long, c_ptr] + [c_int] * 4 + [c_ptr, c_ptr]),
+    "cpc_ctc_loss_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "cpc_ctc_loss": (c_int, [c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_size_t, c_ptr]),
+    "cpc_seqnorm_len_forward": (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_float, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "cpc_seqnorm_len_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr]),
+    "cpc_conv_head_forward_scratch_bytes": (c_size_t, [c_int] * 5),
+    "cpc_conv_head_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr] + [c_int] * 5 + [c_ptr, c_size_t, c_ptr]),
+    "cpc_conv_head_backward_data": (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr]),
+    "cpc_gather_utterances": (c_int, [c_ptr, c_long, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_long, c_ptr]),
 }
 
 _lib = None

@@ -49,7 +49,9 @@ int cpc_version(void);          /* 100 x major + minor; 105 = the entry points o
                                   * 113 = cpc_text_*;
                                   * 114 = one forward and one backward entry point per op: x_rest / n_first, c_frames, `deferred`;
                                   * 115 = the library owns the sampler's draw ahead: cpc_negidx_draw_ahead / cpc_negidx_take;
-                                  * 116 = cpc_ctc_beam_search (+ scratch query) / cpc_align_score */
+                                  * 116 = cpc_ctc_beam_search (+ scratch query) / cpc_align_score;
+                                  * 117 = cpc_ctc_loss (+ scratch query) / cpc_seqnorm_len_* / cpc_conv_head_forward (+ scratch query) / cpc_conv_head_backward_data /
+                                  * cpc_gather_utterances */
 const char *cpc_last_error(void);
 
 /* In-situ kernel timing for bench.py: when enabled, the launchers bracket each launch of the named
@@ -652,6 +654,64 @@ int cpc_ctc_beam_search(const float *probs, const int *lengths, int n, int t_max
                         cpc_stream_t stream);
 int cpc_align_score(const int *seq1, long ld1, const int *len1, const int *seq2, long ld2, const int *len2, int n, int d, int m,
                     int r, int *score, cpc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The whole-utterance CTC phone recogniser (CTCphone_criterion of the reference's cpc/eval/common_voices_eval.py;
+ * cpc2_amd/eval/common_voices_eval.py).  version 117.  Every pointer is a DEVICE pointer, row-major and contiguous; lengths,
+ * offsets and targets are int64 (torch.long).  No float atomic in these kernels: two launches give the same bits.
+ *
+ * cpc_ctc_loss: nn.CTCLoss(blank = k - 1, reduction, zero_infinity = True) of log_softmax(logits) for logits [b][t_max][k] with
+ *   an input length per sequence: in_lengths [b], targets [b][max_l] (padding ignored: the padded width does not matter) and
+ *   tgt_lengths [b].  reduction: 0 = sum, 1 = mean.  nll[i] = -log p_i; loss[0] = sum_i nll[i], or for the mean
+ *   (sum_i nll[i] / max(L_i, 1)) / b.  dlogits (may be NULL, may alias logits) = (softmax - occupancy) on the frames
+ *   < in_lengths[i], divided by b max(L_i, 1) for the mean.  Frames at or beyond in_lengths[i] are never read and get gradient
+ *   exactly 0.  A sequence without an alignment (an input length of 0 included) has nll 0 and gradient 0.  An input length
+ *   outside [0, t_max], a target length outside [0, max_l] or a label outside [0, k - 1) gives that sequence NaN nll and NaN
+ *   in all of its dlogits, as cpc_probe_ctc does.  alpha and beta are f64 in log space, fused with the log-softmax (one workgroup
+ *   per sequence); the gradient is a second launch over (sequence, 1024 elements) workgroups; b <= 65535.  With every
+ *   input length = t_max and the mean the results equal cpc_probe_ctc's bit for bit.
+ *   Limits: 1 <= t_max <= 4096 (164 s of audio behind a stride-4 head), 2 <= k <= 65536, 0 <= max_l <= min(t_max, 1024): the
+ *   2 max_l + 1 extended states of a sequence are held in LDS at 20 bytes each, 40 KB at 1024 labels.
+ *   scratch: cpc_ctc_loss_scratch_bytes(b, t_max, max_l) (f64 [b][t_max] + [b][t_max][2 max_l + 1] + [b], int [b]; 0 with a message in
+ *   cpc_last_error for sizes outside the limits).
+ * cpc_seqnorm_len_forward: the seqNorm branch of getPrediction.  x [b][s][h], lengths [b]: m = the mean and v = the unbiased
+ *   variance of the frames < lengths[i] per (i, channel), then y = (x - m) / sqrt(v + eps) on ALL s frames; mean [b][h] and rstd
+ *   [b][h] = 1 / sqrt(v + eps) are saved.  The statistics are summed in f64 in a fixed order.  lengths[i] = 1 gives NaN (0 / 0,
+ *   as torch.var); a length outside [1, s] is invalid and gives that utterance NaN.
+ * cpc_seqnorm_len_backward: the exact gradient from dy, the forward's y and rstd:
+ *   dx[f] = rstd (dy[f] - [f < len] (A / len + B y[f] / (len - 1))), A = sum_f dy[f], B = sum_f dy[f] y[f] over ALL s frames
+ *   (every frame's dy feeds dm and dv; only the frames < len receive those terms).
+ * cpc_conv_head_backward_data: dx of Conv1d(h, c, ks, stride = ks / 2) on channel-last data.  dout [b][P][c] with
+ *   P = (s - ks) / stride + 1, wp [c][ks][h] (the weight repacked, taps before channels), dx [b][s][h]:
+ *   dx[i][stride j + u] = dout[i][j] . wp[:, u] + dout[i][j - 1] . wp[:, stride + u] for u < stride (a term whose output frame
+ *   does not exist is 0); every element of dx is written once.  Supported: every even ks >= 2 (the reference's default is 8),
+ *   ks <= s <= 262140.  The weight gradient takes no entry of its own: it is cpc_gemm_tn over the overlapping rows of the features
+ *   (row j of an utterance = the ks h floats from frame stride j on: ldb = stride h), whose K split is summed from slabs in order.
+ * cpc_conv_head_forward: out [b][P][c] = the same layer's outputs.  No kernel of its own: it is the product of cpc_gemm_nt, once
+ *   per utterance (its rows end where the utterance ends), reading x [b][s][h] in place with lda = stride h against wp [c][ks][h]
+ *   (bias [c] may be NULL); the unfolded [b][P][ks h] matrix never exists.  What it adds to cpc_gemm_nt is the lent scratch: with
+ *   ks h >= 2048 and few output tiles that product splits K, and the public entry then adds the parts with fp32 atomics; here they
+ *   go to slabs that are summed in a fixed order, so two launches give the same bits.
+ *   scratch: cpc_conv_head_forward_scratch_bytes(b, s, h, c, ks) (0 with a message for sizes outside the limits).
+ * cpc_gather_utterances: out [n][max_len] = the zero-padded batch of whole utterances:
+ *   out[i][p] = pack[offsets[i] + roffset[i] + p] for p < lengths[i] - roffset[i], 0 behind it (roffset NULL: 0 everywhere).
+ *   `pack` holds `total` floats; an item that leaves it, or whose roffset is outside [0, lengths[i]], becomes a row of zeros.
+ * ------------------------------------------------------------------------------------------ */
+size_t cpc_ctc_loss_scratch_bytes(int b, int t_max, int max_l);
+int cpc_ctc_loss(const float *logits, int b, int t_max, int k, const int64_t *in_lengths, const int64_t *targets, int max_l,
+                 const int64_t *tgt_lengths, int reduction, float *nll, float *loss, float *dlogits, void *scratch,
+                 size_t scratch_bytes, cpc_stream_t stream);
+int cpc_seqnorm_len_forward(const float *x, const int64_t *lengths, int b, int s, int h, float eps, float *y, float *mean,
+                            float *rstd, cpc_stream_t stream);
+int cpc_seqnorm_len_backward(const float *dy, const float *y, const float *rstd, const int64_t *lengths, int b, int s, int h,
+                             float *dx, cpc_stream_t stream);
+size_t cpc_conv_head_forward_scratch_bytes(int b, int s, int h, int c, int ks);
+int cpc_conv_head_forward(const float *x, const float *wp, const float *bias, float *out, int b, int s, int h, int c, int ks,
+                          void *scratch, size_t scratch_bytes, cpc_stream_t stream);
+int cpc_conv_head_backward_data(const float *dout, const float *wp, int b, int s, int h, int c, int ks, float *dx,
+                                cpc_stream_t stream);
+int cpc_gather_utterances(const float *pack, long total, const int64_t *offsets, const int64_t *lengths, const int64_t *roffset,
+                          float *out, int n, long max_len, cpc_stream_t stream);
 
 #ifdef __cplusplus
 }
