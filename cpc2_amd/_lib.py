@@ -110,6 +110,8 @@ SIGNATURES = {
     "cpc_kmeans_assign": (c_int, [c_ptr, c_long, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr]),
     "cpc_kmeans_distances": (c_int, [c_ptr, c_long, c_int, c_ptr, c_int, c_ptr, c_ptr]),
     "cpc_kmeans_accumulate": (c_int, [c_ptr, c_long, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_size_t, c_ptr]),
+    "cpc_moments_scratch_bytes": (c_size_t, [c_long, c_int, c_int]),
+    "cpc_moments_accumulate": (c_int, [c_ptr, c_long, c_int, c_ptr, c_long, c_int, c_long, c_ptr, c_ptr, c_ptr, c_size_t, c_ptr]),
     "cpc_probe_xent": (c_int, [c_ptr, c_ptr, c_long, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     "cpc_probe_xent_backward_scratch_bytes": (c_size_t, [c_int]),
     "cpc_probe_head_backward": (c_int, [c_ptr, c_long, c_int, c_ptr, c_ptr, c_ptr, c_size_t, c_ptr]),

@@ -257,3 +257,11 @@ def buildFeature_batch(featureMaker, seqPath, strict=False, maxSizeSeq=8000, seq
     seq = _load(seqPath)
     spans = _plan(seq.size(1), maxSizeSeq, strict, featureMaker.getDownsamplingFactor(), drop_short_rest=True)
     return _extract(featureMaker, seq, spans, batch_size, seqNorm)
+
+
+def buildFeature_batch_device(featureMaker, seqPath, strict=False, maxSizeSeq=8000, seqNorm=False, batch_size=8):
+    """buildFeature_batch with the result left on the model's device (the moments of cpc2_amd.cca.train_cca): the same spans,
+    the same values."""
+    seq = _load(seqPath)
+    spans = _plan(seq.size(1), maxSizeSeq, strict, featureMaker.getDownsamplingFactor(), drop_short_rest=True)
+    return _extract(featureMaker, seq, spans, batch_size, seqNorm, to_host=False)

@@ -51,7 +51,8 @@ int cpc_version(void);          /* 100 x major + minor; 105 = the entry points o
                                   * 115 = the library owns the sampler's draw ahead: cpc_negidx_draw_ahead / cpc_negidx_take;
                                   * 116 = cpc_ctc_beam_search (+ scratch query) / cpc_align_score;
                                   * 117 = cpc_ctc_loss (+ scratch query) / cpc_seqnorm_len_* / cpc_conv_head_forward (+ scratch query) / cpc_conv_head_backward_data /
-                                  * cpc_gather_utterances */
+                                  * cpc_gather_utterances;
+                                  * 118 = cpc_moments_scratch_bytes / cpc_moments_accumulate */
 const char *cpc_last_error(void);
 
 /* In-situ kernel timing for bench.py: when enabled, the launchers bracket each launch of the named
@@ -515,6 +516,26 @@ int cpc_kmeans_assign(const float *x, long n, int d, const float *ck, int k, int
 int cpc_kmeans_distances(const float *x, long n, int d, const float *ck, int k, float *dist, cpc_stream_t stream);
 int cpc_kmeans_accumulate(const float *x, long n, int d, const int *index, int k, float *sums, int64_t *counts,
                           void *scratch, size_t scratch_bytes, cpc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Streaming second moments of one or two feature streams in f64 (the CCA of cpc2_amd/cca; a PCA needs the one-stream form).
+ * x [n][dx] and y [n][dy] are fp32 DEVICE rows with row strides ldx >= dx and ldy >= dy (elements); x and y may alias.
+ * y == NULL with dy == 0 is the one-stream form.  With D = dx + dy and row z = [x row, y row], the running totals are
+ *   sums[D] += sum z,   gram[D][D] += sum z z^T     (f64 DEVICE buffers; gram row-major and FULL: both triangles are written and
+ * are equal bit for bit).  The caller zeroes sums and gram once and keeps the row count itself.
+ * Limits: 1 <= dx <= 512, 0 <= dy <= 512, 1 <= n < 2^31; a call outside them (or with ld below the width, or dy > 0 without y)
+ * returns CPC_ERR_INVALID with a message before any launch, and the size query returns 0.
+ *
+ * Every product of two f32 values is exact in f64; the products are accumulated in f64 on v_mfma_f64_16x16x4_f64, so the only
+ * rounding is that of an f64 sum.  One workgroup per (64 x 64 tile of the upper block triangle, one of S row ranges) leaves a
+ * partial tile in scratch; a second kernel adds the S partials in range order and mirrors the triangle.  S depends on
+ * (n, dx + dy) alone and there is no float atomic: the same call gives the same bits.  Columns beyond D and rows beyond n are
+ * zero-filled in the kernel; no padded copy and no f64 copy of the inputs is made.
+ * scratch: cpc_moments_scratch_bytes(n, dx, dy) bytes.
+ * ------------------------------------------------------------------------------------------ */
+size_t cpc_moments_scratch_bytes(long n, int dx, int dy);
+int cpc_moments_accumulate(const float *x, long ldx, int dx, const float *y, long ldy, int dy, long n,
+                           double *sums, double *gram, void *scratch, size_t scratch_bytes, cpc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Loss heads of the linear-separability probe (cpc/eval/linear_separability.py and the supervised criteria of
