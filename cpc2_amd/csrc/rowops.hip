@@ -331,16 +331,20 @@ __global__ void channelnorm_cf_fwd_kernel(const float *x, const float *w, const 
     if (col >= (long)N * L) return;
     const int n = (int)(col / L), l = (int)(col - (long)n * L);
     const float *xp = x + (long)n * C * L + l;
+    // the mean as x0 + m, m = the mean of x - x0 (x0 = the column's first element): the sum of C values that share an offset
+    // loses log2(C) bits of the mean to that offset, the sum of their differences does not (x = 10 + randn, C = 256: y off
+    // by 2.1e-6 of its range against 3.8e-7; tests/test_channelnorm_gpu.py::test_channelnorm_on_offset_data)
+    const float x0 = xp[0];
     float s = 0.f;
-    for (int c = 0; c < C; ++c) s += xp[(long)c * L];
-    const float mean = s / C;
+    for (int c = 0; c < C; ++c) s += xp[(long)c * L] - x0;
+    const float m = s / C;
     float ss = 0.f;
-    for (int c = 0; c < C; ++c) { const float d = xp[(long)c * L] - mean; ss += d * d; }
+    for (int c = 0; c < C; ++c) { const float d = (xp[(long)c * L] - x0) - m; ss += d * d; }
     const float rstd = rsqrtf(ss / (C - 1) + eps);
     rstd_save[col] = rstd;
     float *yp = y + (long)n * C * L + l;
     for (int c = 0; c < C; ++c) {
-        float v = (xp[(long)c * L] - mean) * rstd;
+        float v = ((xp[(long)c * L] - x0) - m) * rstd;
         if (w != nullptr) v = v * w[c] + b[c];
         yp[(long)c * L] = v;
     }
@@ -355,14 +359,15 @@ __global__ void channelnorm_cf_bwd_kernel(const float *x, const float *w, const 
     const int n = ok ? (int)(col / L) : 0, l = ok ? (int)(col - (long)n * L) : 0;
     const float *xp = x + (long)n * C * L + l;
     const float *gp = dy + (long)n * C * L + l;
-    float mean = 0.f, rstd = 0.f, s1 = 0.f, s2 = 0.f;
+    float x0 = 0.f, m = 0.f, rstd = 0.f, s1 = 0.f, s2 = 0.f;
     if (ok) {
+        x0 = xp[0];                         // the forward kernel's mean, x0 + m, term by term
         float s = 0.f;
-        for (int c = 0; c < C; ++c) s += xp[(long)c * L];
-        mean = s / C;
+        for (int c = 0; c < C; ++c) s += xp[(long)c * L] - x0;
+        m = s / C;
         rstd = rstd_save[col];
         for (int c = 0; c < C; ++c) {
-            const float xh = (xp[(long)c * L] - mean) * rstd;
+            const float xh = ((xp[(long)c * L] - x0) - m) * rstd;
             const float g = gp[(long)c * L] * (w != nullptr ? w[c] : 1.f);
             s1 += g;
             s2 += g * xh;
@@ -371,7 +376,7 @@ __global__ void channelnorm_cf_bwd_kernel(const float *x, const float *w, const 
     for (int c = 0; c < C; ++c) {
         float gy = 0.f, xh = 0.f;
         if (ok) {
-            xh = (xp[(long)c * L] - mean) * rstd;
+            xh = ((xp[(long)c * L] - x0) - m) * rstd;
             gy = gp[(long)c * L];
             const float g = gy * (w != nullptr ? w[c] : 1.f);
             dx[(long)n * C * L + (long)c * L + l] = rstd * (g - s1 / C - xh * s2 / (C - 1));

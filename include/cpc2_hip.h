@@ -117,7 +117,10 @@ int cpc_prof_read(const char *name, double *total_ms, long *count);
  * (v_mfma_f32_32x32x2_f32); mode 2 (opt-in, never the default) makes the encoder's plane-fed convolution products at
  * hidden 256 / 512 multiply only a0 b0 + a0 b1 + a1 b0 of the split (16 bits of product mantissa, f32 accumulation: half the
  * matrix work; TF32 -- what cuDNN gives the reference's convolutions on its own GPUs by default -- keeps 10 bits), everything
- * else as mode 0.  cpc_gemm_set_mode returns the previous mode; other values only query.  The mode is PROCESS-WIDE (atomic, default
+ * else as mode 0.  Domain of modes 0 and 2: |x| < (2 - 2^-8) 2^127 = 3.3962e38 for every operand element -- from there to FLT_MAX
+ * the first bf16 term rounds to infinity and every output the element feeds is inf or NaN (never a finite wrong value; mode 1
+ * multiplies such values as f32); and bf16's smallest subnormal being 2^-133, an element below 2^-110 in magnitude is held to
+ * within 2^-134 absolute, not relative -- which shows only where it multiplies one of 2^100 or more.  cpc_gemm_set_mode returns the previous mode; other values only query.  The mode is PROCESS-WIDE (atomic, default
  * 0) and the only setting the library keeps between calls: it selects the arithmetic of a whole run (the tests' yardstick, the
  * benchmark's labelled entry) and has to reach the backward pass, which autograd runs on a thread of its own -- a per-thread mode
  * does not (tried in round 4).  Select it before the first call of a run, not concurrently with one.
