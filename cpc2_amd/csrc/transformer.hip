@@ -482,7 +482,7 @@ __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(AttnArgs a)
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
                     const int il = at_row(e, h2), i = 32 * w + il, j = 32 * jt + r32;
-                    rv[e] = Pw[il * AT_LP + min(SS - 1 - i + j, AT_LP - 1)];
+                    rv[e] = Pw[il * AT_LP + min(max(SS - 1 - i + j, 0), AT_LP - 1)];    // (below 0 for rows past the sequence)
                 }
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
@@ -710,9 +710,10 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_kernel(AttnArgs a)
                 float tv[4];
 #pragma unroll
                 for (int x = 0; x < 4; ++x) {
-                    // (read at a clamped position, selected afterwards: no branch per element.  j <= iq is m < SS)
+                    // (read at a position clamped to the row, selected afterwards: no branch per element.  j <= iq is m < SS;
+                    //  a row past the sequence reaches j = iq + 7, behind the end of PS for iq = 127)
                     const int m = mb + x, j = m - sh;
-                    const float v = PS[iq * AT_LP + max(j, 0)];
+                    const float v = PS[iq * AT_LP + min(max(j, 0), AT_LP - 1)];
                     tv[x] = (m >= sh && m < SS && iq < SS) ? v : 0.f;
                 }
                 at_mfma4(dq, make_float4(tv[0], tv[1], tv[2], tv[3]), *reinterpret_cast<const float4 *>(&Rk[r32 * AT_LP + mb]));
@@ -736,8 +737,8 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_kernel(AttnArgs a)
             float tv[4];
 #pragma unroll
             for (int x = 0; x < 4; ++x) {
-                const int i = i0 + x, j = mk - (SS - 1 - i);            // (j <= i is mk < SS)
-                const float v = PS[i * AT_LP + max(j, 0)];
+                const int i = i0 + x, j = mk - (SS - 1 - i);            // (j <= i is mk < SS; up to 254 for sizeSeq 1: clamped to the row)
+                const float v = PS[i * AT_LP + min(max(j, 0), AT_LP - 1)];
                 tv[x] = (j >= 0 && i < SS && mk < SS) ? v : 0.f;
             }
             at_mfma4(dr, make_float4(tv[0], tv[1], tv[2], tv[3]), *reinterpret_cast<const float4 *>(&QT[r32 * AT_LP + i0]));

@@ -289,7 +289,14 @@ int cpc_rnn_backward(const float *x, const float *const *params, const float *do
  *           the multi-head predictor (MultiClassifierTransformerHead, transformers.py:137-158):
  *           lin2.weight is [k*d, 2048], lin2.bias [k*d], and
  *           out[n, s, c, :] = LN2(Wl (y + FFN(y)[c*d : (c+1)*d]) + bl), out is [n, s, k, d_out].
- *   backward: dout -> dx (may be NULL), grads (same order/shapes as params, overwritten).
+ *   backward: dout -> dx (may be NULL), grads (same order/shapes as params, overwritten; NULL where the parameter is NULL).
+ *   domain  d_model and d_out each one of 32, 64, 128, 256, 512 (independently; 8 heads of d_model / 8); 1 <= size_seq <= 128;
+ *           1 <= layers <= 4, and layers > 1 needs d_out == d_model; 1 <= n_classifiers <= 64.  Anything else: the size
+ *           queries return 0 and the entry points CPC_ERR_INVALID with the reason in cpc_last_error, nothing is launched.
+ *   saved, scratch  exactly cpc_transformer_saved_bytes / _scratch_bytes are used.  Their contents are unspecified on entry:
+ *           forward writes every part of `saved` that backward reads, and neither call reads scratch it has not written
+ *           (scratch may be reused or overwritten between the two calls).
+ *   (tests/test_transformer_abi_gpu.py holds the entry points to all of this in poisoned buffers against fp64.)
  * ------------------------------------------------------------------------------------------ */
 int cpc_transformer_param_count(void);
 size_t cpc_transformer_saved_bytes(int n, int s, int d_model, int d_out, int size_seq, int layers, int n_classifiers);
