@@ -70,48 +70,3 @@ class _TailScope:
         self.module._defer_tail = self.prev
         return False
 
-
-
-
-# --------------------------------------------------------------------------- gradients with a fixed home
-# Buffers for gradients whose layout is fixed by the caller (criterion.py: the zero halves of train.py:102-103's slices; cpcStep's
-# split of the encoder output into context windows and target windows): allocated and zeroed once per (shape, device, slot), the
-# producers write their part in place and the consumer hands the whole buffer on.  A buffer is reused only after the backward pass
-# that read it has been enqueued on the same stream; the slot carries every number the "stays zero" / "who writes what" invariant
-# depends on (window counts), so two users with the same full shape but different splits never share one.
-_grad_cache = {}
-
-
-def _cached_grad_buffer(shape, device, slot):
-    key = (tuple(shape), str(device), slot)
-    buf = _grad_cache.get(key)
-    if buf is None:
-        if len(_grad_cache) > 8:
-            _grad_cache.clear()
-        buf = _grad_cache[key] = torch.zeros(shape, dtype=torch.float32, device=device)
-    return buf
-
-
-def grad_home(t):
-    """(full_shape, slot, start) a tensor was marked with by split_windows (criterion.py), if it can be honoured: the gradient with
-    respect to `t` should be written into windows start.. of that cached buffer -- the consumer then takes it without a copy."""
-    home = getattr(t, "_cpc_grad_home", None)
-    if home is None or not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-        return None
-    # ONE consumer per home: a second function that takes the same tagged tensor would write the same memory, and autograd would
-    # then add the buffer to itself (twice the last gradient, no error).  The first forward that honours the home claims it.
-    if getattr(t, "_cpc_grad_home_claimed", False):
-        return None
-    full_shape, _slot, start = home
-    if tuple(t.shape[1:]) != tuple(full_shape[1:]) or start + t.shape[0] > full_shape[0]:
-        return None
-    t._cpc_grad_home_claimed = True
-    return home
-
-
-def grad_home_view(home, like):
-    """The piece of its home buffer a gradient shaped like `like` is written into (None: no home, allocate)."""
-    if home is None:
-        return torch.empty_like(like)
-    full_shape, slot, start = home
-    return _cached_grad_buffer(full_shape, like.device, slot)[start:start + like.shape[0]]

@@ -20,6 +20,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import check, f32c, grad_buffers, ptr, require_gpu, scratch, stream_ptr
+from ._route import DeferScope, cached_grad_buffer, grad_home, grad_home_view, join_deferred, keep_deferred, mark
 from .sampler import NegativeSampler  # noqa: F401  (its home is sampler.py; importers find it here as before)
 
 
@@ -39,188 +40,43 @@ def _packed_view(tensors):
     return torch.as_strided(first, (k,) + tuple(first.shape), (first.numel(),) + tuple(first.stride()))
 
 
-# ---- the deferred backward (cpc2_hip.h, cpc_infonce_backward with deferred = 1) -----------------------------------------------
-# The criterion's dz and predictor weight gradients are produced on a stream of the library's while the context network's
-# backward runs; whoever consumes them has to sit behind join_deferred().  Nothing but the caller can promise that, so the
-# deferral is an EXPLICIT opt-in of the caller's, never something a tensor attribute switches on by travelling through
-# wrappers: `with criterion.deferred_backward(encoded_full): criterion(c, z, label)` (cpcStep does it) states that
-#   * `encoded_full` came out of grad_join() (CPCModel.forward applies it BEFORE the context network, so autograd runs its
-#     backward after the context network's and before anything that reads the summed gradient of the encoder output),
-#   * the criterion call inside the scope is the ONLY consumer of that tensor (a second loss term on it, or a tensor hook,
-#     would make autograd read dz before the join), and
-#   * nothing reads the predictors' weight gradients before the backward pass has ended.
-# The scope is refused (the backward then runs at once, on the caller's stream) when the criterion object is not the bare
-# module (DistributedDataParallel / DataParallel around it: DDP's reducer copies a weight gradient into its bucket the moment
-# autograd accumulates it, i.e. before the side stream has written it) or when a predictor weight carries a backward or
-# post-accumulate hook.  A callback at the end of the backward pass joins whatever is still pending (an encoder without
-# gradient: nobody reads dz, the optimiser reads the weight gradients).
-_deferred = {}          # device index -> tensors the side stream still reads / writes (kept alive until the join)
-
-
-def join_deferred(device):
-    """Make the current stream of `device` wait for a pending deferred criterion backward (no-op when none is)."""
-    device = torch.device(device)
-    if device.type != "cuda":
-        return
-    if _deferred.pop(_lib.device_index(device), None) is not None:
-        check(_lib.load().cpc_infonce_join(stream_ptr(device)), "infonce_join")
-
-
-class _GradJoin(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x):
-        return x.view_as(x)
-
-    @staticmethod
-    def backward(ctx, g):
-        join_deferred(g.device)
-        return g
-
-
-def grad_join(encoded):
-    """Identity on the encoder output; its backward is where a deferred criterion backward is joined.  Returns the tensor the
-    criterion should be given (marked `_cpc_join`; `_cpc_join_source` = the tensor whose gradient is the complete one)."""
-    if not (encoded.is_cuda and encoded.requires_grad and torch.is_grad_enabled()):
-        return encoded
-    out = _GradJoin.apply(encoded)
-    out._cpc_join = True
-    out._cpc_join_source = encoded
-    return out
-
-
-def carry_join(view, parent, start):
-    """`view` = parent[start:start + n] (windows) of a grad_join() output.  The criterion then differentiates with respect to
-    `parent` itself (its dz lands in rows start.. of a gradient of parent's size), so that no slicing node of autograd's --
-    which would read dz BEFORE the context network's backward, i.e. before the join -- sits between the two."""
-    if getattr(parent, "_cpc_join", False) and parent.is_contiguous() and view.is_contiguous() and \
-            view.data_ptr() == parent.data_ptr() + start * parent.stride(0) * parent.element_size():
-        view._cpc_join = True
-        view._cpc_join_parent = (parent, int(start))
-    return view
-
-
-# ---- gradients that are zero by construction, without materialising the zeros every step ----------------------------------------
-# train.py:102-103 slices the model's outputs (context of the first b windows, targets of the last b): autograd turns each slice's
-# gradient back into the full tensor with a zero fill plus a copy (16.8 MB + 8.4 MB per slice at the benchmark shape, two small
-# launches each).  The halves that are zero are zero EVERY step, so they live in buffers that are allocated and zeroed once per
-# (device, shape, slot): the criterion's backward writes dc / dz straight into the other half and hands the whole buffer on.
-# Nothing ever writes the zero half (autograd only reads gradients it does not own: this cache holds a reference), and a buffer is
-# reused only after the backward pass that read it has been enqueued on the same stream.
-from ._tail import _cached_grad_buffer, grad_home, grad_home_view  # noqa: E402
-
-
-class _FirstWindows(torch.autograd.Function):
-    """x[:n] (windows) whose backward does not fill and copy: the gradient of the slice is written by its producer straight into
-    the first n windows of a cached buffer whose other windows stay zero (see above); any other gradient is copied into it."""
-
-    @staticmethod
-    def forward(ctx, x, n):
-        ctx.full_shape, ctx.n = tuple(x.shape), n
-        out = x[:n]
-        return out.view_as(out)
-
-    @staticmethod
-    def backward(ctx, g):
-        buf = _cached_grad_buffer(ctx.full_shape, g.device, ("context", ctx.n))
-        if not (g.data_ptr() == buf.data_ptr() and g.is_contiguous() and g.dtype == torch.float32):
-            buf[:ctx.n].copy_(g)
-        return buf, None
-
-
-def first_windows(x, n):
-    """x[:n] for the context features in cpcStep (train.py:102); marks the result so that the criterion's backward writes its
-    gradient where _FirstWindows.backward expects it."""
-    if not (x.is_cuda and x.requires_grad and torch.is_grad_enabled() and x.is_contiguous() and x.dtype == torch.float32):
-        return x[:n]
-    out = _FirstWindows.apply(x, n)
-    out._cpc_first_of = (tuple(x.shape), n)
-    return out
-
-
-class _SplitWindows(torch.autograd.Function):
-    """(x[:n], x[n:]) along the window axis whose backward neither fills nor adds: both gradients are written by their producers
-    straight into the two parts of ONE cached buffer (grad_home), which is handed on whole.  The deferred criterion backward is
-    joined here -- autograd runs this node when BOTH gradients are due, i.e. after the context network's backward."""
-
-    @staticmethod
-    def forward(ctx, x, n, tag):
-        ctx.full_shape, ctx.n, ctx.tag = tuple(x.shape), n, tag
-        ctx.set_materialize_grads(False)
-        first, rest = x[:n], x[n:]
-        return first.view_as(first), rest.view_as(rest)
-
-    @staticmethod
-    def backward(ctx, g_first, g_rest):
-        n = ctx.n
-        device = (g_first if g_first is not None else g_rest).device
-        join_deferred(device)
-        buf = _cached_grad_buffer(ctx.full_shape, device, (ctx.tag, n))
-        row = buf.stride(0) * buf.element_size()
-        for g, part, at in ((g_first, buf[:n], 0), (g_rest, buf[n:], n)):
-            if g is None:
-                part.zero_()
-            elif not (g.data_ptr() == buf.data_ptr() + at * row and g.is_contiguous() and g.dtype == torch.float32):
-                part.copy_(g)
-        return buf, None, None
-
-
-def split_windows(x, n, tag="split"):
-    """cpcStep's split of the encoder output [2b, T, H] into the context network's windows x[:n] and the criterion's target windows
-    x[n:] (train.py:99-103 keeps exactly these: the context of the first half, the encoded data of the second).  Each part is marked
-    with its home in the gradient buffer (`_cpc_grad_home`, honoured by the recurrent / transformer / criterion backward) and the
-    second with `_cpc_join`: whoever consumes the gradient of `x` sits behind the join of a deferred criterion backward."""
-    if not (x.is_cuda and x.requires_grad and torch.is_grad_enabled() and x.is_contiguous() and x.dtype == torch.float32):
-        return x[:n], x[n:]
-    first, rest = _SplitWindows.apply(x, n, tag)
-    first._cpc_grad_home = (tuple(x.shape), (tag, n), 0)
-    rest._cpc_grad_home = (tuple(x.shape), (tag, n), n)
-    rest._cpc_join = True
-    return first, rest
-
-
-class _FirstFrames(torch.autograd.Function):
-    """x[:, :w] (the frames the criterion uses) as a contiguous tensor; the gradient goes back into x's home in the gradient buffer
-    (grad_home), whose frames w.. nobody writes: they stay zero from the buffer's allocation on (its slot is this form's own)."""
-
-    @staticmethod
-    def forward(ctx, x, w):
-        ctx.home, ctx.shape, ctx.w = grad_home(x), tuple(x.shape), w
-        return x[:, :w].contiguous()
-
-    @staticmethod
-    def backward(ctx, g):
-        if ctx.home is not None:
-            full_shape, slot, start = ctx.home
-            buf = _cached_grad_buffer(full_shape, g.device, slot)[start:start + ctx.shape[0]]
-        else:
-            buf = torch.zeros(ctx.shape, dtype=torch.float32, device=g.device)
-        buf[:, :ctx.w].copy_(g)
-        return buf, None
-
-
-def first_frames(x, w, total):
-    """x[:, :w] of a `total`-frame sequence for a causal context network whose later frames nobody uses (criterion.py:296 keeps
-    cFeature[:, :windowSize]); the result is marked `_cpc_frames_of = total` so that the criterion knows it was handed the slice."""
-    if x.is_cuda and x.requires_grad and torch.is_grad_enabled() and x.dtype == torch.float32 and x.is_contiguous():
-        out = _FirstFrames.apply(x, w)
+def _infonce_forward(z, ext_idx, weights, n_neg, c=None, wpred=None, preds=None):
+    """The one launch of the fused InfoNCE forward: z [b, t, dim_enc], ext_idx int32 [b, W, n_neg], weights [b * W] or None, and
+    either c [b, t or W, dim_ar] with the packed predictor weights wpred [K, dim_enc, dim_ar] (the kernel forms the predictions)
+    or the K prediction tensors preds [b, W, dim_enc]; float tensors fp32 and contiguous.  Returns (losses [K], acc [K], saved)."""
+    lib = _lib.load()
+    if preds is None:
+        b, tc, dim_ar = c.shape
+        k, dim_enc, _ = wpred.shape
+        t = z.shape[1]
+        # c holds the t frames of the sequence, or only the W = t - k the criterion uses (criterion.py:296: cFeature[:, :windowSize])
+        if z.shape != (b, t, dim_enc) or wpred.shape[2] != dim_ar or tc not in (t, t - k):
+            raise ValueError(f"shape mismatch c={tuple(c.shape)} z={tuple(z.shape)} W={tuple(wpred.shape)}")
     else:
-        out = x[:, :w].contiguous()
-    out._cpc_frames_of = total
-    return out
-
-
-class _DeferScope:
-    def __init__(self, criterion, encoded_full):
-        self.criterion, self.tensor = criterion, encoded_full
-
-    def __enter__(self):
-        ok = getattr(self.tensor, "_cpc_join", False) and not hasattr(self.tensor, "_cpc_join_parent")
-        self.criterion._defer_scope = self.tensor if ok else None
-        return self
-
-    def __exit__(self, *exc):
-        self.criterion._defer_scope = None
-        return False
+        b, t, dim_enc = z.shape
+        k, dim_ar = len(preds), dim_enc
+        if any(p.shape != (b, t - k, dim_enc) for p in preds):
+            raise ValueError(f"predictions must be [b, W, dim_enc] = {(b, t - k, dim_enc)}")
+    if ext_idx.dtype != torch.int32 or ext_idx.numel() != b * n_neg * (t - k):
+        raise ValueError("ext_idx must be int32 [b, W, n_neg]")
+    if weights is not None and weights.numel() != b * (t - k):
+        raise ValueError(f"weights must hold one value per (window, frame): {b * (t - k)}, got {weights.numel()}")
+    nsaved = lib.cpc_infonce_saved_bytes(b, t, k, dim_ar, dim_enc, n_neg)
+    nscratch = lib.cpc_infonce_scratch_bytes(b, t, k, dim_ar, dim_enc, n_neg)
+    if nsaved == 0:
+        check(-1, "infonce shape query")
+    losses = torch.empty(k, dtype=torch.float32, device=z.device)
+    acc = torch.empty(k, dtype=torch.float32, device=z.device)
+    saved = torch.empty(nsaved, dtype=torch.uint8, device=z.device)
+    sc = scratch(nscratch, z.device)
+    if preds is None:
+        check(lib.cpc_infonce_forward(ptr(c), ptr(z), ptr(wpred), ptr(ext_idx), ptr(weights), ptr(losses), ptr(acc),
+                                      ptr(saved), ptr(sc), b, t, tc, k, dim_ar, dim_enc, n_neg, stream_ptr(z.device)), "infonce_forward")
+    else:
+        check(lib.cpc_infonce_forward_pred(_lib.ptr_array(preds), ptr(z), ptr(ext_idx), ptr(weights), ptr(losses), ptr(acc),
+                                           ptr(saved), ptr(sc), b, t, k, dim_enc, n_neg, stream_ptr(z.device)),
+              "infonce_forward_pred")
+    return losses, acc, saved
 
 
 class _InfoNCEFn(torch.autograd.Function):
@@ -230,8 +86,7 @@ class _InfoNCEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, c, z, ext_idx, weights, n_neg, defer, *wk):
         require_gpu(c, z, ext_idx, weights, *wk)
-        lib = _lib.load()
-        ctx.c_first_of = getattr(c, "_cpc_first_of", None) if (c.is_contiguous() and c.dtype == torch.float32) else None
+        ctx.c_home = grad_home(c)              # (first_windows: dc goes where the slice's backward looks for it, the rest stays zero)
         c = f32c(c)
         ctx.z_full_shape = None
         ctx.z_home = grad_home(z)              # (split_windows: dz is written where the split's backward looks for it)
@@ -242,30 +97,11 @@ class _InfoNCEFn(torch.autograd.Function):
         wpred = _packed_view([w.detach() for w in wk])
         if wpred is None:
             wpred = torch.stack([f32c(w.detach()) for w in wk], dim=0)
-        b, tc, dim_ar = c.shape
-        k, dim_enc, _ = wpred.shape
-        t = z.shape[1]
-        # c holds the t frames of the sequence, or only the W = t - k the criterion uses (criterion.py:296: cFeature[:, :windowSize])
-        if z.shape != (b, t, dim_enc) or wpred.shape[2] != dim_ar or tc not in (t, t - k):
-            raise ValueError(f"shape mismatch c={tuple(c.shape)} z={tuple(z.shape)} W={tuple(wpred.shape)}")
-        if ext_idx.dtype != torch.int32 or ext_idx.numel() != b * n_neg * (t - k):
-            raise ValueError("ext_idx must be int32 [b, W, n_neg]")
-        if weights is not None and weights.numel() != b * (t - k):
-            raise ValueError(f"weights must hold one value per (window, frame): {b * (t - k)}, got {weights.numel()}")
         w = f32c(weights) if weights is not None else None
-        nsaved = lib.cpc_infonce_saved_bytes(b, t, k, dim_ar, dim_enc, n_neg)
-        nscratch = lib.cpc_infonce_scratch_bytes(b, t, k, dim_ar, dim_enc, n_neg)
-        if nsaved == 0:
-            check(-1, "infonce shape query")
-        losses = torch.empty(k, dtype=torch.float32, device=c.device)
-        acc = torch.empty(k, dtype=torch.float32, device=c.device)
-        saved = torch.empty(nsaved, dtype=torch.uint8, device=c.device)
-        sc = scratch(nscratch, c.device)
-        check(lib.cpc_infonce_forward(ptr(c), ptr(z), ptr(wpred), ptr(ext_idx), ptr(w), ptr(losses), ptr(acc),
-                                      ptr(saved), ptr(sc), b, t, tc, k, dim_ar, dim_enc, n_neg, stream_ptr(c.device)), "infonce_forward")
+        losses, acc, saved = _infonce_forward(z, ext_idx, w, n_neg, c=c, wpred=wpred)
         ctx.save_for_backward(c, z, wpred, ext_idx, w, saved)
         ctx.param_refs = wk
-        ctx.dims = (b, t, k, dim_ar, dim_enc, n_neg)
+        ctx.dims = (c.shape[0], z.shape[1], wpred.shape[0], c.shape[2], z.shape[2], n_neg)
         ctx.mark_non_differentiable(acc)
         ctx.set_materialize_grads(False)       # (no zeros tensor -- a launch -- for the gradient of `acc`, which nobody has)
         return losses, acc
@@ -278,14 +114,11 @@ class _InfoNCEFn(torch.autograd.Function):
         if dlosses is None:                    # (materialize_grads is off: a loss nobody differentiated)
             dlosses = torch.zeros(k, dtype=torch.float32, device=c.device)
         dlosses = f32c(dlosses)
-        if ctx.c_first_of is not None:       # (first_windows: dc goes where the slice's backward looks for it, the rest stays zero)
-            dc = _cached_grad_buffer(ctx.c_first_of[0], c.device, ("context", ctx.c_first_of[1]))[:c.shape[0]]
-        else:
-            dc = torch.empty_like(c)
+        dc = grad_home_view(ctx.c_home, c)
         defer = ctx.z_full_shape is not None
         if defer and ctx.z_full_shape != tuple(z.shape):
-            # (windows outside start .. start + n get no gradient from the criterion: zero once, see _cached_grad_buffer)
-            dz_out = _cached_grad_buffer(ctx.z_full_shape, z.device, ("targets", ctx.z_start, z.shape[0]))
+            # (windows outside start .. start + n get no gradient from the criterion: zero once, see cached_grad_buffer)
+            dz_out = cached_grad_buffer(ctx.z_full_shape, z.device, ("targets", ctx.z_start, z.shape[0]))
             dz = dz_out[ctx.z_start:ctx.z_start + z.shape[0]]
         else:
             dz_out = dz = grad_home_view(ctx.z_home, z)
@@ -305,9 +138,7 @@ class _InfoNCEFn(torch.autograd.Function):
                                        ptr(dz), ptr(dw), b, t, c.shape[1], k, dim_ar, dim_enc, n_neg, int(defer), stream_ptr(c.device)),
               "infonce_backward")
         if defer:
-            _deferred[_lib.device_index(c.device)] = (c, z, wpred, ext_idx, w, dlosses, saved, sc, dz_out, dw)
-            device = c.device
-            torch.autograd.Variable._execution_engine.queue_callback(lambda: join_deferred(device))
+            keep_deferred(c.device, (c, z, wpred, ext_idx, w, dlosses, saved, sc, dz_out, dw))
         if not direct:
             gw = list(dw.unbind(0))
         return (dc, dz_out, None, None, None, None) + tuple(gw)
@@ -320,31 +151,12 @@ class _InfoNCEPredFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, z, ext_idx, weights, n_neg, *preds):
         require_gpu(z, ext_idx, weights, *preds)
-        lib = _lib.load()
         z = f32c(z)
         preds = tuple(f32c(p) for p in preds)
-        b, t, dim_enc = z.shape
-        k = len(preds)
-        if any(p.shape != (b, t - k, dim_enc) for p in preds):
-            raise ValueError(f"predictions must be [b, W, dim_enc] = {(b, t - k, dim_enc)}")
-        if ext_idx.dtype != torch.int32 or ext_idx.numel() != b * n_neg * (t - k):
-            raise ValueError("ext_idx must be int32 [b, W, n_neg]")
-        if weights is not None and weights.numel() != b * (t - k):
-            raise ValueError(f"weights must hold one value per (window, frame): {b * (t - k)}, got {weights.numel()}")
         w = f32c(weights) if weights is not None else None
-        nsaved = lib.cpc_infonce_saved_bytes(b, t, k, dim_enc, dim_enc, n_neg)
-        nscratch = lib.cpc_infonce_scratch_bytes(b, t, k, dim_enc, dim_enc, n_neg)
-        if nsaved == 0:
-            check(-1, "infonce shape query")
-        losses = torch.empty(k, dtype=torch.float32, device=z.device)
-        acc = torch.empty(k, dtype=torch.float32, device=z.device)
-        saved = torch.empty(nsaved, dtype=torch.uint8, device=z.device)
-        sc = scratch(nscratch, z.device)
-        check(lib.cpc_infonce_forward_pred(_lib.ptr_array(preds), ptr(z), ptr(ext_idx), ptr(w), ptr(losses), ptr(acc),
-                                           ptr(saved), ptr(sc), b, t, k, dim_enc, n_neg, stream_ptr(z.device)),
-              "infonce_forward_pred")
+        losses, acc, saved = _infonce_forward(z, ext_idx, w, n_neg, preds=preds)
         ctx.save_for_backward(z, ext_idx, w, saved, *preds)
-        ctx.dims = (b, t, k, dim_enc, n_neg)
+        ctx.dims = (z.shape[0], z.shape[1], len(preds), z.shape[2], n_neg)
         ctx.mark_non_differentiable(acc)
         ctx.set_materialize_grads(False)
         return losses, acc
@@ -366,39 +178,65 @@ class _InfoNCEPredFn(torch.autograd.Function):
         return (dz, None, None, None) + tuple(dpreds)
 
 
+# --------------------------------------------------------------------------- y = x W^T (+ b)
+def _rows(x, last_frame):
+    """(tensor, byte offset, row stride, rows, width) of the rows a head reads: every frame of x [..., H], or with last_frame
+    the frame S - 1 of every sequence of x [B, S, H], read in place (lda = S * H)."""
+    if last_frame:
+        b, s, h = x.shape
+        return x, (s - 1) * h * 4, s * h, b, h
+    return x, 0, x.shape[-1], x.numel() // x.shape[-1], x.shape[-1]
+
+
+def _linear_grads(dy, x, w, dw, db, dx, scale=None, off=0, lda=None):
+    """The gradients of y = x W^T + b from dy [m, n] (times the one-element `scale`, in place, when given): db = its column sums
+    (cpc_probe_head_backward), dW = dy^T x (cpc_gemm_tn) and, when `dx` is given, dX = dy W (cpc_gemm_nt on the transposed
+    weight).  The rows of x and dx start `off` bytes into the tensor and lie `lda` elements apart (_rows)."""
+    lib = _lib.load()
+    m, n = dy.shape
+    kdim = w.shape[1]
+    lda = kdim if lda is None else lda
+    dev = dy.device
+    st = stream_ptr(dev)
+    if db is not None:
+        nb = lib.cpc_probe_xent_backward_scratch_bytes(n)
+        check(lib.cpc_probe_head_backward(ptr(dy), m, n, ptr(scale), ptr(db), ptr(scratch(nb, dev)), nb, st), "probe_head_backward")
+    nt = lib.cpc_gemm_tn_scratch_bytes(n, kdim, m)
+    check(lib.cpc_gemm_tn(ptr(dy), n, ctypes.c_void_p(x.data_ptr() + off), lda, ptr(dw), kdim, n, kdim, m, ptr(scratch(nt, dev)), nt, st),
+          "gemm_tn")
+    if dx is not None:
+        wt = w.t().contiguous()                                     # [K, N]: the NT form's B operand of dx = dy W
+        check(lib.cpc_gemm_nt(ptr(dy), n, ptr(wt), n, ctypes.c_void_p(dx.data_ptr() + off), lda, None, m, kdim, n, st), "gemm_nt")
+
+
 class _LinearFn(torch.autograd.Function):
-    """y = x W^T on the library's GEMMs (x [..., K], W [N, K]): the predictions of the linear predictors as tensors, for the
-    paths that need them outside the fused kernel (predictor dropout)."""
+    """y = x W^T (+ b) on the library's GEMMs (x [..., K], W [N, K], b [N] or None): the predictions of the linear predictors as
+    tensors, for the paths that need them outside the fused kernel (predictor dropout), and the layers of PhoneCriterion."""
 
     @staticmethod
-    def forward(ctx, x, weight):
-        require_gpu(x, weight)
+    def forward(ctx, x, weight, bias):
+        require_gpu(x, weight, bias)
         lib = _lib.load()
         x2 = f32c(x).reshape(-1, x.shape[-1])
         w = f32c(weight.detach())
+        b = f32c(bias.detach()) if bias is not None else None
         m, kdim = x2.shape
         n = w.shape[0]
         y = torch.empty(m, n, dtype=torch.float32, device=x.device)
-        check(lib.cpc_gemm_nt(ptr(x2), kdim, ptr(w), kdim, ptr(y), n, None, m, n, kdim, stream_ptr(x.device)), "gemm_nt")
+        check(lib.cpc_gemm_nt(ptr(x2), kdim, ptr(w), kdim, ptr(y), n, ptr(b), m, n, kdim, stream_ptr(x.device)), "gemm_nt")
         ctx.save_for_backward(x2, w)
         ctx.xshape = x.shape
+        ctx.params = (weight, bias)
         return y.view(*x.shape[:-1], n)
 
     @staticmethod
     def backward(ctx, dy):
-        lib = _lib.load()
         x2, w = ctx.saved_tensors
-        m, kdim = x2.shape
-        n = w.shape[0]
-        dy2 = f32c(dy).reshape(m, n)
-        wt = w.t().contiguous()                                     # [K, N]: the NT form's B operand of dx = dy W
-        dx = torch.empty(m, kdim, dtype=torch.float32, device=dy.device)
-        check(lib.cpc_gemm_nt(ptr(dy2), n, ptr(wt), n, ptr(dx), kdim, None, m, kdim, n, stream_ptr(dy.device)), "gemm_nt")
-        dw = torch.empty(n, kdim, dtype=torch.float32, device=dy.device)
-        nb = lib.cpc_gemm_tn_scratch_bytes(n, kdim, m)
-        sc = scratch(nb, dy.device)
-        check(lib.cpc_gemm_tn(ptr(dy2), n, ptr(x2), kdim, ptr(dw), kdim, n, kdim, m, ptr(sc), nb, stream_ptr(dy.device)), "gemm_tn")
-        return dx.view(ctx.xshape), dw
+        dy2 = f32c(dy).reshape(x2.shape[0], w.shape[0])
+        dw, db = grad_buffers(ctx.params)
+        dx = torch.empty_like(x2)
+        _linear_grads(dy2, x2, w, dw, db, dx)
+        return dx.view(ctx.xshape), dw, db
 
 
 # --------------------------------------------------------------------------- modules
@@ -536,7 +374,7 @@ class CPCUnsupersivedCriterion(BaseCriterion):
     def deferred_backward(self, encoded_full):
         """Context manager: the criterion call(s) inside may run the deferred backward with respect to `encoded_full`, a
         grad_join() output that nothing else consumes (see the comment above join_deferred)."""
-        return _DeferScope(self, encoded_full)
+        return DeferScope(self, encoded_full)
 
     def _prepare(self, cFeature, encodedData):
         if self.mode == "reverse":                      # criterion.py:292-294
@@ -561,7 +399,7 @@ class CPCUnsupersivedCriterion(BaseCriterion):
             preds = [predictor(cW) for predictor in net.predictors]
             preds = [p[0] if isinstance(p, tuple) else p for p in preds]   # criterion.py:164-165
         elif drop is not None:
-            preds = [_LinearFn.apply(cW, predictor.weight) for predictor in net.predictors]
+            preds = [_LinearFn.apply(cW, predictor.weight, None) for predictor in net.predictors]
         else:
             return None
         if drop is not None:
@@ -594,24 +432,13 @@ class CPCUnsupersivedCriterion(BaseCriterion):
             z = f32c(encodedData)
             b, t, dim_enc = z.shape
             k = self.nPredicts
-            losses = torch.empty(k, dtype=torch.float32, device=z.device)
-            acc = torch.empty(k, dtype=torch.float32, device=z.device)
-            dim_ar = dim_enc if preds is not None else cFeature.size(2)
-            nsaved = lib.cpc_infonce_saved_bytes(b, t, k, dim_ar, dim_enc, n_neg)
-            if nsaved == 0:
-                check(-1, "infonce shape query")
-            saved = torch.empty(nsaved, dtype=torch.uint8, device=z.device)
-            sc = scratch(lib.cpc_infonce_scratch_bytes(b, t, k, dim_ar, dim_enc, n_neg), z.device)
             if preds is None:
-                c = f32c(cFeature)
+                dim_ar = cFeature.size(2)
                 wpred = torch.stack([f32c(p.weight.detach()) for p in self.wPrediction.predictors], dim=0)
-                check(lib.cpc_infonce_forward(ptr(c), ptr(z), ptr(wpred), ptr(extIdx), None, ptr(losses), ptr(acc), ptr(saved),
-                                              ptr(sc), b, t, t, k, dim_ar, dim_enc, n_neg, stream_ptr(z.device)), "infonce_forward")
+                _losses, _acc, saved = _infonce_forward(z, extIdx, None, n_neg, c=f32c(cFeature), wpred=wpred)
             else:
-                preds = [f32c(p) for p in preds]
-                check(lib.cpc_infonce_forward_pred(_lib.ptr_array(preds), ptr(z), ptr(extIdx), None, ptr(losses), ptr(acc),
-                                                   ptr(saved), ptr(sc), b, t, k, dim_enc, n_neg, stream_ptr(z.device)),
-                      "infonce_forward_pred")
+                dim_ar = dim_enc
+                _losses, _acc, saved = _infonce_forward(z, extIdx, None, n_neg, preds=[f32c(p) for p in preds])
             off = lib.cpc_infonce_logits_offset(b, t, k, dim_ar, dim_enc, n_neg)
             n = b * windowSize * k * (n_neg + 1)
             slot_order = saved[off:off + 4 * n].view(torch.float32).view(b, windowSize, k, n_neg + 1)
@@ -650,7 +477,8 @@ class CPCUnsupersivedCriterion(BaseCriterion):
     def forward(self, cFeature, encodedData, label, signal_quality=None):
         batchSize, seqSize, _ = cFeature.size()
         windowSize = seqSize - self.nPredicts
-        if getattr(cFeature, "_cpc_frames_of", None) == encodedData.size(1) and seqSize == encodedData.size(1) - self.nPredicts \
+        cMark, zMark = mark(cFeature), mark(encodedData)
+        if cMark is not None and cMark.frames == encodedData.size(1) and seqSize == encodedData.size(1) - self.nPredicts \
                 and self.mode != "reverse":
             # the caller (cpcStep) handed over cFeature[:, :windowSize] of a causal context network -- what :296 slices out itself
             seqSize, windowSize = encodedData.size(1), seqSize
@@ -660,8 +488,8 @@ class CPCUnsupersivedCriterion(BaseCriterion):
         defer = None
         scope = self._defer_scope
         if scope is not None and self.mode != "reverse" and not os.environ.get("CPC_NCE_NO_DEFER") \
-                and encodedData.dtype == torch.float32 and encodedData.is_contiguous() and getattr(encodedData, "_cpc_join", False):
-            zFull, start = getattr(encodedData, "_cpc_join_parent", (encodedData, 0))
+                and encodedData.dtype == torch.float32 and encodedData.is_contiguous() and zMark is not None and zMark.join:
+            zFull, start = zMark.parent or (encodedData, 0)
             if zFull is scope and self._may_defer():
                 defer = (start, batchSize)
         cFeature, encodedData = self._prepare(cFeature, encodedData)
@@ -687,15 +515,6 @@ class CPCUnsupersivedCriterion(BaseCriterion):
 
 
 # --------------------------------------------------------------------------- supervised probe heads (criterion.py:366-538)
-def _rows(x, last_frame):
-    """(tensor, byte offset, row stride, rows, width) of the rows a head reads: every frame of x [..., H], or with last_frame
-    the frame S - 1 of every sequence of x [B, S, H], read in place (lda = S * H)."""
-    if last_frame:
-        b, s, h = x.shape
-        return x, (s - 1) * h * 4, s * h, b, h
-    return x, 0, x.shape[-1], x.numel() // x.shape[-1], x.shape[-1]
-
-
 class _ProbeHeadFn(torch.autograd.Function):
     """loss of logits = x W^T + b on the library's kernels: cpc_gemm_nt (with the bias) for the logits, then one pass of
     cpc_probe_xent (kind "xent": labels [rows]; returns loss [1] and the accuracy, double [1]) or cpc_probe_ctc (kind "ctc":
@@ -739,72 +558,23 @@ class _ProbeHeadFn(torch.autograd.Function):
             check(lib.cpc_probe_ctc(ptr(logits), b, t, c, ptr(labels), labels.shape[1], ptr(lengths), ptr(nll), ptr(loss),
                                     ptr(logits) if want_grad else None, ptr(scratch(nb, dev)), nb, stream_ptr(dev)), "probe_ctc")
         ctx.save_for_backward(x, w, logits if want_grad else None)
-        ctx.geom = (off, lda, n, h, c, last_frame)
+        ctx.geom = (off, lda, last_frame)
         ctx.params = (weight, bias)
         ctx.mark_non_differentiable(acc)
         return loss, acc
 
     @staticmethod
     def backward(ctx, dloss, _dacc):
-        lib = _lib.load()
         x, w, dlogits = ctx.saved_tensors
         if dlogits is None:
             raise RuntimeError("the probe head ran without a gradient (want_grad=False) and cannot be differentiated")
-        off, lda, n, h, c, last_frame = ctx.geom
-        dev = x.device
-        st = stream_ptr(dev)
+        off, lda, last_frame = ctx.geom
         dw, db = grad_buffers(ctx.params)
-        nb = lib.cpc_probe_xent_backward_scratch_bytes(c)
-        check(lib.cpc_probe_head_backward(ptr(dlogits), n, c, ptr(f32c(dloss.reshape(1))), ptr(db), ptr(scratch(nb, dev)), nb, st),
-              "probe_head_backward")
-        xp = ctypes.c_void_p(x.data_ptr() + off)
-        nt = lib.cpc_gemm_tn_scratch_bytes(c, h, n)
-        check(lib.cpc_gemm_tn(ptr(dlogits), c, xp, lda, ptr(dw), h, c, h, n, ptr(scratch(nt, dev)), nt, st), "gemm_tn")
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.zeros_like(x) if last_frame else torch.empty_like(x)
-            wt = w.t().contiguous()                                     # [H, C]: the NT form's B operand of dx = dlogits W
-            check(lib.cpc_gemm_nt(ptr(dlogits), c, ptr(wt), c, ctypes.c_void_p(dx.data_ptr() + off), lda, None, n, h, c, st),
-                  "gemm_nt")
+        _linear_grads(dlogits, x, w, dw, db, dx, scale=f32c(dloss.reshape(1)), off=off, lda=lda)
         return dx, dw, db, None, None, None, None, None
-
-
-class _AffineFn(torch.autograd.Function):
-    """y = x W^T + b on the library's GEMMs (the hidden layers of PhoneCriterion with nLayers > 1)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias):
-        require_gpu(x, weight, bias)
-        lib = _lib.load()
-        x2 = f32c(x).reshape(-1, x.shape[-1])
-        w = f32c(weight.detach())
-        m, k = x2.shape
-        n = w.shape[0]
-        y = torch.empty(m, n, dtype=torch.float32, device=x.device)
-        check(lib.cpc_gemm_nt(ptr(x2), k, ptr(w), k, ptr(y), n, ptr(f32c(bias.detach())), m, n, k, stream_ptr(x.device)), "gemm_nt")
-        ctx.save_for_backward(x2, w)
-        ctx.xshape = x.shape
-        ctx.params = (weight, bias)
-        return y.view(*x.shape[:-1], n)
-
-    @staticmethod
-    def backward(ctx, dy):
-        lib = _lib.load()
-        x2, w = ctx.saved_tensors
-        m, k = x2.shape
-        n = w.shape[0]
-        dev = dy.device
-        st = stream_ptr(dev)
-        dy2 = f32c(dy).reshape(m, n)
-        dw, db = grad_buffers(ctx.params)
-        nb = lib.cpc_probe_xent_backward_scratch_bytes(n)
-        check(lib.cpc_probe_head_backward(ptr(dy2), m, n, None, ptr(db), ptr(scratch(nb, dev)), nb, st), "probe_head_backward")
-        nt = lib.cpc_gemm_tn_scratch_bytes(n, k, m)
-        check(lib.cpc_gemm_tn(ptr(dy2), n, ptr(x2), k, ptr(dw), k, n, k, m, ptr(scratch(nt, dev)), nt, st), "gemm_tn")
-        dx = torch.empty(m, k, dtype=torch.float32, device=dev)
-        wt = w.t().contiguous()
-        check(lib.cpc_gemm_nt(ptr(dy2), n, ptr(wt), n, ptr(dx), k, None, m, k, n, st), "gemm_nt")
-        return dx.view(ctx.xshape), dw, db
 
 
 def _wants_grad(*tensors):
@@ -852,7 +622,7 @@ class PhoneCriterion(BaseCriterion):
         """the input of the last Linear: the features themselves, or the hidden layers' output"""
         layers = _linear_layers(self.PhoneCriterionClassifier)
         for lin in layers[:-1]:
-            features = torch.relu(_AffineFn.apply(features, lin.weight, lin.bias))
+            features = torch.relu(_LinearFn.apply(features, lin.weight, lin.bias))
         return features, layers[-1]
 
     def forward(self, cFeature, otherEncoded, label):
@@ -864,7 +634,7 @@ class PhoneCriterion(BaseCriterion):
 
     def getPrediction(self, cFeature):
         hidden, lin = self._hidden(cFeature)
-        return _AffineFn.apply(hidden, lin.weight, lin.bias)
+        return _LinearFn.apply(hidden, lin.weight, lin.bias)
 
 
 class CTCPhoneCriterion(BaseCriterion):
@@ -881,7 +651,7 @@ class CTCPhoneCriterion(BaseCriterion):
 
     def getPrediction(self, cFeature):
         lin = self.PhoneCriterionClassifier
-        return _AffineFn.apply(cFeature, lin.weight, lin.bias)
+        return _LinearFn.apply(cFeature, lin.weight, lin.bias)
 
     def forward(self, cFeature, otherEncoded, label):
         from .seq_alignment import collapse_padded

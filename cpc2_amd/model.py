@@ -16,7 +16,8 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import check, f32c, grad_buffers, ptr, ptr_array, require_gpu, scratch, stream_ptr
-from ._tail import _TailScope, _all_in_place, _keep_for_tail, _no_hooks, _tail, _tail_tag, grad_home, grad_home_view, join_tail  # noqa: F401
+from ._route import grad_home, grad_home_view, grad_join
+from ._tail import _TailScope, _all_in_place, _keep_for_tail, _no_hooks, _tail, _tail_tag, join_tail  # noqa: F401
 
 
 # --------------------------------------------------------------------------- ChannelNorm
@@ -443,8 +444,7 @@ class CPCModel(nn.Module):
         if self.mask_prob > 0.0:
             encodedData = self.getMask(encodedData)
         # (before the context network: autograd then runs this node's backward AFTER the context network's, and a criterion
-        #  backward that was deferred beside it is joined there -- criterion.py, grad_join)
-        from .criterion import grad_join
+        #  backward that was deferred beside it is joined there -- _route.py, grad_join)
         encodedOut = grad_join(encodedData)
         cFeature = self.gAR(encodedData)
         return cFeature, encodedOut, label

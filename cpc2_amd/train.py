@@ -19,7 +19,8 @@ import torch.distributed as dist
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
-from .criterion import CPCUnsupersivedCriterion, NoneCriterion, carry_join, first_frames, first_windows, split_windows
+from ._route import carry_join, first_frames, first_windows, mark, mark_frames, split_windows
+from .criterion import CPCUnsupersivedCriterion, NoneCriterion
 from .model import CPCAR, CPCEncoder, CPCModel, join_tail
 
 
@@ -423,7 +424,9 @@ class DataParallelContext:
     def attach(self, encoder_output):
         """Register the hook that starts the early reductions when the gradient of `encoder_output` is ready (everything
         downstream of the encoder has then written its parameter gradients)."""
-        encoder_output = getattr(encoder_output, "_cpc_join_source", encoder_output)   # (criterion.py, grad_join)
+        m = mark(encoder_output)
+        if m is not None and m.source is not None:              # (_route.py, grad_join)
+            encoder_output = m.source
         if not (self.active and self.early and encoder_output.requires_grad):
             return
         if self._fired:
@@ -606,8 +609,7 @@ def cpcStep(past, future, label, cpcModel, cpcCriterion, signal_quality=None, de
             if w:
                 # ... and only over the W frames criterion.py:296 keeps of it (a causal recurrent network: _context_frames_only)
                 context_in, encoded_data = split_windows(encoded_full, b, tag=("split_w", w))
-                c_feature = cpcModel.gAR(first_frames(context_in, w, frames))         # [b, W, H]
-                c_feature._cpc_frames_of = frames
+                c_feature = mark_frames(cpcModel.gAR(first_frames(context_in, w)), frames)      # [b, W, H]
             else:
                 context_in, encoded_data = split_windows(encoded_full, b)
                 c_feature = cpcModel.gAR(context_in)                                  # [b, T, H]: train.py:102's c_feature[:b]

@@ -19,7 +19,8 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import check, f32c, grad_buffers, ptr, ptr_array, require_gpu, scratch, stream_ptr
-from ._tail import _TailScope, _all_in_place, _keep_for_tail, _no_hooks, _tail_tag, grad_home, grad_home_view
+from ._route import grad_home, grad_home_view
+from ._tail import _TailScope, _all_in_place, _keep_for_tail, _no_hooks, _tail_tag
 
 
 class ScaledDotProductAttention(nn.Module):

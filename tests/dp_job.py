@@ -155,7 +155,7 @@ elif mode in ("ddp", "ddpref"):
         tape.begin()
         tot, ls, _acc = cpcStep(x, x, label, ddp_model, ddp_crit)
         tot.backward()
-        from cpc2_amd import criterion as _cm
+        from cpc2_amd import _route as _cm
         assert not _cm._deferred, "a criterion inside DistributedDataParallel must not defer its backward"
         opt._gather_stray_grads()
         tape("post", 0, opt.flat_grad.numel(), opt.flat_grad)         # DDP's averages, back in the parameters' gradients

@@ -1836,7 +1836,7 @@ def test_deferred_criterion_backward_gives_the_same_step_bit_for_bit(monkeypatch
     immediate form: every gradient and the parameters after two steps are equal bit for bit -- with cpcStep's default (context
     network on the b context windows: the criterion differentiates with respect to the target half of split_windows), with the
     reference's own 2b-window dataflow (strict: with respect to the full encoder output, rows b.. only) and with dedup."""
-    from cpc2_amd import criterion as crit_mod
+    from cpc2_amd import _route as route_mod, criterion as crit_mod
     hidden, b = 256, 6
     dedup, strict = form == "dedup", form == "strict"
     results = []
@@ -1867,7 +1867,7 @@ def test_deferred_criterion_backward_gives_the_same_step_bit_for_bit(monkeypatch
         for _ in range(2):
             tot, _losses, _acc = cpcStep(x, x, label, model, crit, dedup=dedup, strict=strict)
             tot.backward()
-            assert not crit_mod._deferred, "a deferred backward is still pending after the backward pass"
+            assert not route_mod._deferred, "a deferred backward is still pending after the backward pass"
             grads.append(opt.flat_grad.detach().clone())
             opt.step()
             opt.zero_grad()
@@ -2025,7 +2025,7 @@ import sys, torch
 sys.path.insert(0, {root!r})
 import cpc2_amd
 from cpc2_amd import _lib
-from cpc2_amd import criterion as crit_mod
+from cpc2_amd import _route as route_mod
 from cpc2_amd.train import buildOptimizer, cpcStep
 from oracle import synth
 hidden, b, mode = 512, 32, {mode!r}
@@ -2039,7 +2039,7 @@ label = torch.zeros(b, dtype=torch.long, device="cuda:0")
 for _ in range(2):
     tot, _l, _a = cpcStep(x, x, label, model, crit)
     tot.backward()
-    assert not crit_mod._deferred
+    assert not route_mod._deferred
     opt.step()
     opt.zero_grad()
 _lib.check(_lib.load().cpc_async_error_check(_lib.stream_ptr(torch.device("cuda:0"))), "async error check")
@@ -2094,7 +2094,7 @@ def test_criterion_backward_is_deferred_only_inside_the_callers_scope(monkeypatc
     does, with a SECOND loss term on the encoder output -- autograd sums the two gradients of that tensor as soon as both
     exist, i.e. before a join: nothing may be deferred, and the gradient is the sum of the two terms' own gradients.
     (2) inside cpcStep, a predictor weight with a tensor hook (what DDP's reducer amounts to): not deferred either."""
-    from cpc2_amd import criterion as crit_mod
+    from cpc2_amd import _route as route_mod
     hidden, b = 256, 4
     mp = synth.encoder_params(hidden, 21)
     mp.update(synth.gru_params(hidden, hidden, 1, 22))
@@ -2112,7 +2112,7 @@ def test_criterion_backward_is_deferred_only_inside_the_callers_scope(monkeypatc
         crit.seed(5)
         opt.zero_grad()
         c, z, _ = model(x, label)
-        assert getattr(z, "_cpc_join", False)                    # the attribute is there -- and must not be what decides
+        assert getattr(route_mod.mark(z), "join", False)         # the mark is there -- and must not be what decides
         tot = 0.0
         if with_nce:
             losses, _acc = crit(c, z, label)
@@ -2120,7 +2120,7 @@ def test_criterion_backward_is_deferred_only_inside_the_callers_scope(monkeypatc
         if with_extra:
             tot = tot + (z * probe).sum() * 1e-3
         tot.backward()
-        assert not crit_mod._deferred
+        assert not route_mod._deferred
         opt._gather_stray_grads()
         return opt.flat_grad.detach().clone()
     seen, both = _spied_criterion_calls(monkeypatch, lambda: direct(True, True))
@@ -2925,7 +2925,7 @@ def test_a_gradient_home_serves_one_consumer():
     """split_windows tags its parts with a fixed place in the encoder output's gradient buffer; the first function that consumes a
     part writes there in place.  A SECOND consumer of the same part (a subclass that runs two recurrent nets on x) must get a buffer
     of its own -- both writing the home would make autograd add the buffer to itself."""
-    from cpc2_amd.criterion import split_windows
+    from cpc2_amd._route import split_windows
     hidden, n, t_len = 256, 6, 32
     torch.manual_seed(2)
     ar1 = cpc2_amd.CPCAR(hidden, hidden, False, 1).to(DEV)
@@ -2942,6 +2942,35 @@ def test_a_gradient_home_serves_one_consumer():
     plain, tagged = run(False), run(True)
     assert float(plain[n // 2:].abs().max()) == 0.0 and float(tagged[n // 2:].abs().max()) == 0.0
     assert_close(tagged[:n // 2], plain[:n // 2], 2e-6, "gradient of a part with two consumers")
+
+
+def test_a_first_windows_home_serves_one_consumer():
+    """The same for first_windows, whose home the criterion's backward honours for dc: the loss is the sum of TWO criterion calls on
+    one first_windows output (different negatives).  Only the first may write dc into the cached buffer; the gradient equals that of
+    the plain slice c_full[:2], the windows 2.. stay exactly zero, and a second pass reuses the buffer with the same result."""
+    from cpc2_amd import _route
+    torch.manual_seed(4)
+    crit = cpc2_amd.CPCUnsupersivedCriterion(4, 32, 32, 8, rnnMode="linear", sizeInputSeq=16).to(DEV)
+    c_data = torch.randn(4, 16, 32, device=DEV)
+    z = torch.randn(2, 16, 32, device=DEV)
+    label = torch.zeros(2, dtype=torch.long, device=DEV)
+
+    def run(tagged):
+        crit.seed(11)
+        crit.zero_grad()
+        c_full = c_data.clone().requires_grad_(True)
+        c = _route.first_windows(c_full, 2) if tagged else c_full[:2]
+        (crit(c, z, label)[0].sum() + crit(c, z, label)[0].sum()).backward()
+        return c_full.grad.clone()
+    plain, tagged = run(False), run(True)
+    buf = _route.cached_grad_buffer((4, 16, 32), c_data.device, ("context", 2))
+    again = run(True)
+    assert _route.cached_grad_buffer((4, 16, 32), c_data.device, ("context", 2)) is buf, "the cached buffer was not reused"
+    assert float(plain[:2].abs().max()) > 0
+    for name, got in (("tagged", tagged), ("tagged, second pass", again)):
+        assert float(plain[2:].abs().max()) == 0.0 and float(got[2:].abs().max()) == 0.0, name
+        assert_close(got[:2], plain[:2], 2e-6, f"gradient of a first_windows output with two consumers ({name})")
+    assert_close(again, tagged, 2e-6, "gradient of the second pass through the cached buffer")
 
 
 def test_forward_hooks_keep_the_reference_call():
