@@ -112,6 +112,15 @@ SIGNATURES = {
     "cpc_kmeans_accumulate": (c_int, [c_ptr, c_long, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_size_t, c_ptr]),
     "cpc_moments_scratch_bytes": (c_size_t, [c_long, c_int, c_int]),
     "cpc_moments_accumulate": (c_int, [c_ptr, c_long, c_int, c_ptr, c_long, c_int, c_long, c_ptr, c_ptr, c_ptr, c_size_t, c_ptr]),
+    "cpc_mfcc_tables_doubles": (c_long, [c_int, c_int, c_int]),
+    "cpc_mfcc_tables_host": (c_int, [c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, c_ptr, c_long]),
+    "cpc_mfcc_frame_tile": (c_int, []),
+    "cpc_melspec_scratch_bytes": (c_size_t, [c_long, c_int, c_int]),
+    "cpc_melspec_db": (c_int, [c_ptr, c_long, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_long, c_long, c_int, c_int, c_int, c_int, c_ptr,
+                               c_int, ctypes.c_double, c_ptr, c_size_t, c_ptr]),
+    "cpc_mfcc_finish": (c_int, [c_ptr, c_size_t, c_ptr, c_ptr, c_ptr, c_int, c_long, c_int, c_int, c_int, c_int, c_ptr, c_int, c_ptr,
+                                c_long, c_long, c_ptr]),
+    "cpc_deltas": (c_int, [c_ptr, c_long, c_ptr, c_long, c_int, c_ptr, c_ptr, c_int, c_long, c_long, c_ptr]),
     "cpc_probe_xent": (c_int, [c_ptr, c_ptr, c_long, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     "cpc_probe_xent_backward_scratch_bytes": (c_size_t, [c_int]),
     "cpc_probe_head_backward": (c_int, [c_ptr, c_long, c_int, c_ptr, c_ptr, c_ptr, c_size_t, c_ptr]),

@@ -52,7 +52,9 @@ int cpc_version(void);          /* 100 x major + minor; 105 = the entry points o
                                   * 116 = cpc_ctc_beam_search (+ scratch query) / cpc_align_score;
                                   * 117 = cpc_ctc_loss (+ scratch query) / cpc_seqnorm_len_* / cpc_conv_head_forward (+ scratch query) / cpc_conv_head_backward_data /
                                   * cpc_gather_utterances;
-                                  * 118 = cpc_moments_scratch_bytes / cpc_moments_accumulate */
+                                  * 118 = cpc_moments_scratch_bytes / cpc_moments_accumulate;
+                                  * 119 = cpc_mfcc_tables_doubles / cpc_mfcc_tables_host / cpc_mfcc_frame_tile / cpc_melspec_scratch_bytes /
+                                  * cpc_melspec_db / cpc_mfcc_finish / cpc_deltas */
 const char *cpc_last_error(void);
 
 /* In-situ kernel timing for bench.py: when enabled, the launchers bracket each launch of the named
@@ -546,6 +548,58 @@ int cpc_kmeans_accumulate(const float *x, long n, int d, const int *index, int k
 size_t cpc_moments_scratch_bytes(long n, int dx, int dy);
 int cpc_moments_accumulate(const float *x, long ldx, int dx, const float *y, long ldy, int dy, long n,
                            double *sums, double *gram, void *scratch, size_t scratch_bytes, cpc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Log-mel and MFCC baseline features (cpc2_amd/spectral.py; csrc/mfcc.hip).  version 119.
+ * The definition restates torchaudio's documented Spectrogram / MelScale / AmplitudeToDB / create_dct / compute_deltas; it has
+ * never been compared with a torchaudio binary.  For a signal x[0 .. L) and n_freqs = n_fft / 2 + 1:
+ *   frame t is centred on c_t = t * hop + offset and reads xr[c_t - n_fft / 2 + n], n < n_fft, xr = x reflected without
+ *     repeating the edge sample (i < 0 -> -i, i >= L -> 2 (L - 1) - i; needs L > n_fft / 2);
+ *   w[n] = 0.5 - 0.5 cos(2 pi n / n_fft);   P[t][k] = | sum_n w[n] xr_t[n] e^(-2 pi i ((n k) mod n_fft) / n_fft) |^2, k < n_freqs;
+ *   fb[k][m] = max(0, min(-(f[m] - a[k]) / (f[m+1] - f[m]), (f[m+2] - a[k]) / (f[m+2] - f[m+1]))), a = linspace(0, sample_rate / 2
+ *     (integer division), n_freqs), f = the inverse of mel(.) = 2595 log10(1 + . / 700) on linspace(mel(f_min), mel(f_max), n_mels + 2);
+ *   D = 10 log10(max(P fb, 1e-10)), then D = max(D, max(D) - top_db) with the outer maximum over one signal (floor_mode 1), over
+ *     every signal of the call (2), or no clamp (0);
+ *   mel output: D [frames][n_mels];   mfcc output: C[t][k] = sum_m D[t][m] dct[k][m], k < n_out,
+ *     dct[k][m] = cos(pi / n_mels (m + 0.5) k) sqrt(2 / n_mels), row 0 times 1 / sqrt(2);
+ *   deltas: d[t] = ((c[t+1] - c[t-1]) + 2 (c[t+2] - c[t-2])) / 10, t +- j clamped to the signal's frames.
+ * Samples are converted exactly, every table is built on the host in double, every sum and the log10 are f64, and one rounding
+ * to f32 happens at the store.  No float atomic; a frame's order of summation depends on (n_fft, n_freqs, n_mels) alone: the
+ * same call gives the same bits and, with floor_mode 0 or 1, a signal in a pack gives the bits it gives alone.
+ *
+ * Limits: 32 <= n_fft <= 512, 1 <= hop <= n_fft, 0 <= offset <= hop, 1 <= n_mels <= 512, 1 <= n_out <= n_mels, count >= 1.
+ * Anything else, and a shortest signal (min_len, the caller's host value) of n_fft / 2 samples or fewer, returns CPC_ERR_INVALID
+ * with a message before any launch; the size queries return 0.
+ *
+ * mfcc_tables_doubles / mfcc_tables_host: the one table buffer the kernels read, in HOST memory, `capacity` doubles:
+ *   window [Wp] | cos [Hp][Fp] | sin [Hp][Fp] | fb [Fp][Mp] | dct transposed [n_mels][n_out], one behind the other, with
+ *   Wp = n_fft rounded up to 4, Hp = n_freqs rounded up to 4, Fp = n_freqs rounded up to 16, Mp = n_mels rounded up to 16, the
+ *   padding zero.  Only the twiddle rows n <= n_fft / 2 exist: cos is even and sin odd about n_fft / 2, and the kernel folds the
+ *   windowed sample n_fft - n onto n before the product.  The caller copies the buffer to the device.
+ * mfcc_frame_tile: frames per workgroup (16).  Signal i owns the tiles tile_start[i] .. tile_start[i + 1), ceil(n_frames[i] / tile)
+ *   of them; total_tiles = tile_start[count].
+ * melspec_db: `count` signals in one launch, signal i = x[in_off[i] .. in_off[i] + in_len[i]) of a flat DEVICE vector of x_total
+ *   floats; in_off, in_len, n_frames [count] and tile_start [count + 1] are int64 DEVICE tables.  Leaves the unrounded dB rows, the
+ *   tile maxima and the floors in scratch (cpc_melspec_scratch_bytes(total_tiles, count, n_mels) bytes) for mfcc_finish.  A table
+ *   entry that leaves x is read as silence; nothing outside x is read.
+ * mfcc_finish: out[(row_off[i] + t) * ldo + k] for t < n_frames[i], k < n_out (want_dct != 0: the MFCCs; 0: the dB rows,
+ *   n_out == n_mels); rows outside [0, out_rows) are not written, nor is anything else of out.  Same scratch, tables and floor_mode.
+ * deltas: out[(row_off[i] + t) * ldo + c] = d[t] of in[(row_off[i] + t) * ldi + c], c < cols; in and out may be column ranges of
+ *   one buffer that do not overlap.  max_frames: the largest n_frames (host value: it sizes the grid); count <= 65535.
+ * ------------------------------------------------------------------------------------------ */
+long cpc_mfcc_tables_doubles(int n_fft, int n_mels, int n_out);
+int cpc_mfcc_tables_host(int n_fft, int n_mels, int n_out, int sample_rate, double f_min, double f_max, double *tables_host,
+                         long capacity);
+int cpc_mfcc_frame_tile(void);
+size_t cpc_melspec_scratch_bytes(long total_tiles, int count, int n_mels);
+int cpc_melspec_db(const float *x, long x_total, const long *in_off, const long *in_len, const long *n_frames,
+                   const long *tile_start, int count, long total_tiles, long min_len, int n_fft, int hop, int offset, int n_mels,
+                   const double *tables, int floor_mode, double top_db, void *scratch, size_t scratch_bytes, cpc_stream_t stream);
+int cpc_mfcc_finish(const void *scratch, size_t scratch_bytes, const long *n_frames, const long *row_off, const long *tile_start,
+                    int count, long total_tiles, int n_fft, int n_mels, int n_out, int want_dct, const double *tables,
+                    int floor_mode, float *out, long ldo, long out_rows, cpc_stream_t stream);
+int cpc_deltas(const float *in, long ldi, float *out, long ldo, int cols, const long *n_frames, const long *row_off, int count,
+               long max_frames, long rows_total, cpc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Loss heads of the linear-separability probe (cpc/eval/linear_separability.py and the supervised criteria of
