@@ -89,6 +89,27 @@ def ctc_len(logits, in_lengths, targets, tgt_lengths, reduction):
     return loss, nll, grad
 
 
+def ctc_long_case(seed=256):
+    """(logits [9, 300, 41] f32, input lengths, targets [9, 150], target lengths): transcriptions of 128 to 150 labels, so that
+    the 2 L + 1 extended states pass 256 (a workgroup of ctc_len_kernel owns state s in thread s % 256).  Rows: 128 labels
+    (257 states); 129; 150 with labels 126..129 equal (no-skip transitions at states 253..261); 150 labels that all differ from
+    their neighbours in 299 frames; in exactly 150 frames (one alignment); in 149 (none); 150 equal labels in 300 frames (299
+    are needed); in 298 (no alignment); and an empty transcription."""
+    rng = np.random.default_rng(seed)
+    b, t, w, k = 9, 300, 150, 41
+    logits = (2 * rng.standard_normal((b, t, k))).astype(np.float32)
+    targets = rng.integers(0, k - 1, (b, w))
+    targets[2, 126:130] = targets[2, 126]
+    targets[3:6] = np.arange(w) % 40
+    targets[6:8] = 3
+    in_len = np.array([300, 300, 300, 299, 150, 149, 300, 298, 300], np.int64)
+    tgt_len = np.array([128, 129, 150, 150, 150, 150, 150, 150, 0], np.int64)
+    return logits, in_len, targets.astype(np.int64), tgt_len
+
+
+CTC_LONG_INFEASIBLE = (5, 7)
+
+
 def criterion(c, sizes, state, seqNorm, useLSTM, label=None, labelSize=None, reduction="mean", eps=1e-8):
     """CTCphone_criterion in float64 (eval mode: no dropout).  state: the module's state dict (any float dtype).  Returns a dict:
     pred [B, P, C]; with labels also loss, dc and grads {state-dict key: gradient} (the LSTM's are zero arrays without useLSTM)."""

@@ -252,6 +252,31 @@ def test_oracle_ctc_agrees_with_torch_in_float64(golden, i, reduction):
         assert (grad[row, n:] == 0).all() and np.abs(grad[row, :n]).max() > 0
 
 
+@pytest.mark.parametrize("reduction", ["mean", "sum"])
+def test_oracle_ctc_agrees_with_torch_in_float64_past_256_states(reduction):
+    """The same comparison on the rows of oracle.ctc_long_case (128 to 150 labels: 257 to 301 extended states), which the GPU
+    tests hold ctc_len_kernel to where a thread owns more than one state.  The gradient row by row against that row's largest
+    element: under the mean reduction the empty transcription's row is a hundred times the long rows'."""
+    logits, in_len, targets, tgt_len = oracle.ctc_long_case()
+    assert logits.shape == (9, 300, 41) and (2 * tgt_len[:8] + 1 > 256).all() and tgt_len[8] == 0
+    assert (targets[2, 126:130] == targets[2, 126]).all() and (np.diff(targets[3]) != 0).all() and (targets[6] == 3).all()
+    loss, nll, grad = oracle.ctc_len(logits, in_len, targets, tgt_len, reduction)
+    for row in range(9):                                # rows 5 and 7 are one frame short of an alignment
+        assert (nll[row] == 0) == (row in oracle.CTC_LONG_INFEASIBLE) and nll[row] >= 0
+    x = torch.tensor(logits.astype(np.float64), requires_grad=True)
+    ref = torch.nn.functional.ctc_loss(torch.log_softmax(x, 2).permute(1, 0, 2), torch.tensor(targets), torch.tensor(in_len),
+                                       torch.tensor(tgt_len), blank=40, reduction=reduction, zero_infinity=True)
+    ref.backward()
+    ref_grad = x.grad.numpy()
+    assert abs(loss - ref.item()) <= 1e-10 * max(1.0, abs(ref.item()))
+    for row, n in enumerate(in_len):
+        if row in oracle.CTC_LONG_INFEASIBLE:
+            assert (grad[row] == 0).all() and (ref_grad[row] == 0).all()
+            continue
+        assert np.abs(grad[row] - ref_grad[row]).max() <= 1e-10 * np.abs(ref_grad[row]).max()
+        assert (grad[row, n:] == 0).all() and np.abs(grad[row, :n]).max() > 0
+
+
 def test_oracle_ctc_edge_cases():
     rng = np.random.default_rng(5)
     logits = rng.standard_normal((3, 7, 4))
@@ -311,3 +336,28 @@ def test_entries_refuse_by_name_before_any_gpu_call():
     assert b"conv_head_forward: kernel size 7" in lib.cpc_last_error()
     assert lib.cpc_gather_utterances(null, 10, null, null, null, null, 0, 5, null) == -1
     assert b"gather_utterances:" in lib.cpc_last_error()
+
+
+def test_ctc_loss_and_conv_head_refuse_every_size_outside_their_limits_before_any_gpu_call():
+    """The limits the GPU tests run AT (4096 frames, 1024 labels, max_l = t_max, 2 classes; even kernel sizes from 2 and
+    s = ks), each passed by one.  Every pointer is NULL, as above."""
+    lib = _lib.load()
+    null = ctypes.c_void_p(0)
+    for (b, t, k, max_l), word in [((6, 4097, 6, 9), b"t_max=4097"), ((1, 4096, 6, 1025), b"max_l=1025"), ((6, 37, 6, 38), b"max_l=38"),
+                                   ((65536, 37, 6, 9), b"b=65536"), ((6, 37, 1, 9), b"k=1"), ((6, 37, 0, 9), b"k=0"),
+                                   ((6, 37, 65537, 9), b"k=65537")]:
+        assert lib.cpc_ctc_loss(null, b, t, k, null, null, max_l, null, 1, null, null, null, null, 0, null) == -1
+        message = lib.cpc_last_error()
+        assert message.startswith(b"ctc_loss: sizes outside the supported limits") and word in message, message
+    for s, ks, word in [(40, 3, b"kernel size 3"), (40, 0, b"kernel size 0"), (40, -2, b"kernel size -2"), (1, 2, b"s=1"),
+                        (15, 16, b"s=15")]:
+        assert lib.cpc_conv_head_forward_scratch_bytes(3, s, 32, 6, ks) == 0
+        message = lib.cpc_last_error()
+        assert message.startswith(b"conv_head_forward:") and word in message, message
+        assert lib.cpc_conv_head_forward(null, null, null, null, 3, s, 32, 6, ks, null, 0, null) == -1
+        message = lib.cpc_last_error()
+        assert message.startswith(b"conv_head_forward:") and word in message, message
+        assert lib.cpc_conv_head_backward_data(null, null, 3, s, 32, 6, ks, null, null) == -1
+        message = lib.cpc_last_error()
+        assert message.startswith(b"conv_head_backward_data:") and word in message, message
+    assert lib.cpc_conv_head_forward_scratch_bytes(3, 2, 32, 6, 2) > 0 and lib.cpc_conv_head_forward_scratch_bytes(3, 16, 32, 6, 16) > 0
