@@ -145,6 +145,9 @@ SIGNATURES = {
     "cpc_align_score": (c_int, [c_ptr, c_long, c_ptr, c_ptr, c_long, c_ptr] + [c_int] * 4 + [c_ptr, c_ptr]),
     "cpc_ctc_loss_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
     "cpc_ctc_loss": (c_int, [c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_size_t, c_ptr]),
+    "cpc_ctc_align_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "cpc_ctc_align": (c_int, [c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_int] + [c_ptr] * 7 + [c_size_t, c_ptr]),
+    "cpc_ctc_align_segments": (c_int, [c_ptr, c_int, c_int, c_int, c_ptr, c_int] + [c_ptr] * 8),
     "cpc_seqnorm_len_forward": (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_float, c_ptr, c_ptr, c_ptr, c_ptr]),
     "cpc_seqnorm_len_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr]),
     "cpc_conv_head_forward_scratch_bytes": (c_size_t, [c_int] * 5),

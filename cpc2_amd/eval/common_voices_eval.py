@@ -4,6 +4,8 @@ features of a CPC checkpoint, trained on transcriptions that are not aligned (`t
     python -m cpc2_amd.eval.common_voices_eval train PATH_DB PATH_PHONE CHECKPOINT [-o OUT] [--freeze] [--pathTrain F] [--pathVal F]
                                                [--LSTM] [--seqNorm] [--dropout] [--loss_reduction mean|sum] [--roffset N] ...
     python -m cpc2_amd.eval.common_voices_eval per OUT [--name NAME] [--pathDB D] [--pathVal F] [--pathPhone F] [--batchSize B]
+    python -m cpc2_amd.eval.common_voices_eval align OUT -o ALIGN_DIR [--pathDB D] [--pathVal F] [--pathPhone F] [--batchSize B]
+                                               [--file_extension .wav] [--debug] [--blank_label N] [--name NAME]
 
 Names and signatures are the reference's (SingleSequenceDataset, CTCphone_criterion, cut_data, prepare_data, train_step, val_step,
 get_per, perStep, run, get_PER_args, both sub-commands with every flag).  The head runs on the library (include/cpc2_hip.h,
@@ -33,6 +35,13 @@ Deviations from the reference:
     items' random offsets are drawn with random.randint(0, random_offset_amplitude) in item order, as __getitem__ draws them.
   * perStep runs batched on the device (softmax, cpc_ctc_beam_search with 20 prefixes, cpc_align_score), one copy to the host per
     batch, no process pool and no progress bar; it also reports how many utterances met a tie in the search (seq_alignment.py).
+  * `align` is not the reference's (it has no aligner): the trained head's best CTC alignment of every utterance with its
+    transcription (cpc2_amd/seq_alignment.py: ctc_forced_align, whose docstring is the definition; cpc_ctc_align, version 120),
+    written as one label per 10 ms frame (alignment_frames.txt, the format dataset.parseSeqLabels reads, so that
+    linear_separability --pathPhone runs on a corpus that had no alignment), one line per token (alignment_segments.txt:
+    name phone start_s end_s mean_log_posterior) and alignment_log.json.  One copy to the host per batch.  Agreement with
+    torchaudio.functional.forced_align is UNMEASURED.  Writing ABX .item files from alignments is left as the follow-up: they
+    need speaker and context columns, and a 40 ms grid is coarse for them.
 All refusals happen before any audio file is looked for.
 """
 import argparse
@@ -48,6 +57,7 @@ import time
 from copy import deepcopy
 from pathlib import Path
 
+import numpy as np
 import torch
 
 from .. import _lib, audio
@@ -55,7 +65,8 @@ from .._lib import check, f32c, ptr, require_gpu, scratch, stream_ptr
 from ..dataset import filterSeqs, findAllSeqs, parseSeqLabels
 from ..feature_loader import loadModel
 from ..model import LSTMPredictor
-from ..seq_alignment import beam_search, beam_search_batch, get_seq_PER, get_seq_PER_batch
+from ..seq_alignment import (beam_search, beam_search_batch, ctc_forced_align, frame_labels, get_seq_PER, get_seq_PER_batch,
+                             head_frame_of, head_tokens)
 
 MAX_TARGET = 1024          # cpc_ctc_loss: labels per utterance (the extended states live in LDS)
 
@@ -123,6 +134,7 @@ class SingleSequenceDataset:
             self.phoneOffsets.append(self.phoneOffsets[-1] + n)
         self.maxSize = max(sizes, default=0)
         self.maxSizePhone = max(n_labels, default=0)
+        self.names = [name for name, _ in loaded]
         self.data = (torch.cat([wav.reshape(-1) for _, wav in loaded]).float() if loaded else torch.zeros(0)).to(self.device)
         self.phoneLabels = torch.tensor([label for t in transcripts for label in t], dtype=torch.long)
         print(f'Loaded {len(self.phoneOffsets)} sequences in {time.time() - t0:.2f} seconds')
@@ -400,6 +412,28 @@ class CTCphone_criterion(torch.nn.Module):
         label = torch.as_tensor(label).to(device=dev, dtype=torch.int64)
         return ctc_loss(predictions, featureSize, label, labelSize, self.reduction).view(1, -1)
 
+    def align(self, cFeature, featureSize, label, labelSize):
+        """The best CTC alignment of every utterance with its transcription (seq_alignment.ctc_forced_align -> AlignResult, on
+        the device): getPrediction in eval mode without gradients, the input lengths that forward and perStep use,
+        clamp(featureSize // downsampling_factor, max = P)."""
+        training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                predictions = self.getPrediction(cFeature, featureSize)
+        finally:
+            self.train(training)
+        return self.align_predictions(predictions, featureSize, label, labelSize)
+
+    def align_predictions(self, predictions, featureSize, label, labelSize):
+        """align behind getPrediction: the classifier's outputs [B, P, nPhones + 1] and the sizes that getPrediction took."""
+        dev = predictions.device
+        featureSize = torch.as_tensor(featureSize).to(device=dev, dtype=torch.int64).view(-1)
+        featureSize = torch.clamp(featureSize // self.downsampling_factor, max=predictions.size(1))
+        labelSize = torch.as_tensor(labelSize).to(device=dev, dtype=torch.int64).view(-1)
+        label = torch.as_tensor(label).to(device=dev, dtype=torch.int64)
+        return ctc_forced_align(predictions.detach(), featureSize, label, labelSize)
+
 
 def cut_data(seq, sizeSeq):
     """seq [N, L, ...] cut along dimension 1 to the longest of sizeSeq."""
@@ -517,6 +551,114 @@ def perStep(val_loader,
     return avgPER
 
 
+# --------------------------------------------------------------------------- forced alignment
+SAMPLES_PER_FRAME = 160        # one feature frame (and one written label) per 160 samples
+SAMPLE_RATE = 16000
+
+
+def utterance_alignment(path, labels, confidence, n_samples, blank_label=None, kernel=8, stride=4):
+    """One aligned utterance on the host (numpy rows of an AlignResult) -> (frame labels: int64 [n_samples // 160] or None,
+    segments: [(label, start_s, end_s, mean log posterior)] one per token).  Both come from seq_alignment's frame map: a blank
+    head frame belongs to the preceding token and leading blanks to the first, so the segments tile [0, duration); blank_label
+    changes the frame labels only."""
+    n_frames = int(n_samples) // SAMPLES_PER_FRAME
+    rows = argparse.Namespace(path=path[None], labels=labels[None])
+    frames = frame_labels(rows, [n_frames], kernel, stride, blank_label)[0]
+    tokens = head_tokens(path)
+    segments = []
+    if tokens is not None and n_frames > 0:
+        by_token = frame_labels(rows, [n_frames], kernel, stride)[0]
+        per_frame = tokens[head_frame_of(n_frames, len(tokens), kernel, stride)]
+        starts = [0] + [f for f in range(1, n_frames) if per_frame[f] != per_frame[f - 1]]
+        for n, f0 in enumerate(starts):
+            end = starts[n + 1] * SAMPLES_PER_FRAME / SAMPLE_RATE if n + 1 < len(starts) else int(n_samples) / SAMPLE_RATE
+            segments.append((int(by_token[f0]), f0 * SAMPLES_PER_FRAME / SAMPLE_RATE, end, float(confidence[per_frame[f0]])))
+    return frames, segments
+
+
+def write_alignment(frames_file, segments_file, name, frames, segments):
+    """One utterance's lines: `name l0 l1 ...` (dataset.parseSeqLabels reads it) and `name phone start_s end_s mean_log_posterior`
+    per token."""
+    if frames is not None and len(frames):
+        frames_file.write(name + " " + " ".join(str(int(v)) for v in frames) + "\n")
+    for label, start, end, conf in segments:
+        segments_file.write(f"{name} {label} {start:.6f} {end:.6f} {conf:.6f}\n")
+
+
+def check_align_dir(path):
+    """Refuses an output directory that holds anything.  Reads no audio."""
+    if os.path.exists(path) and (not os.path.isdir(path) or os.listdir(path)):
+        raise ValueError(f"-o {path}: the alignment directory exists and is not empty; give an empty or a new one")
+
+
+def parse_transcripts(pathPhone):
+    """{name: [labels]} of a transcription file `name l0 l1 ...`; unlike dataset.parseSeqLabels a line that holds a name only is
+    an empty transcription."""
+    out = {}
+    with open(pathPhone) as file:
+        for line in file:
+            data = line.split()
+            if data:
+                out[data[0]] = [int(x) for x in data[1:]]
+    return out
+
+
+def alignStep(loader, names, model, criterion, downsampling_factor, align_dir, blank_label=None, timings=None):
+    """Aligns every utterance of `loader` (batches in the order of `names`) and writes ALIGN_DIR/alignment_frames.txt and
+    alignment_segments.txt; returns the counts of alignment_log.json.  One copy to the host per batch.  timings (a dict): seconds
+    per stage (audio, model, head, alignment, writing) are added to it, with a device synchronisation behind each stage."""
+    model.eval()
+    criterion.eval()
+    log = dict(utterances=0, aligned=0, no_alignment=[], invalid=[], empty_transcription=[], met_a_tie=0)
+
+    def lap(stage, since):
+        if timings is None:
+            return since
+        torch.cuda.synchronize()
+        now = time.perf_counter()
+        timings[stage] = timings.get(stage, 0.0) + now - since
+        return now
+
+    at = 0
+    os.makedirs(align_dir, exist_ok=True)
+    with open(os.path.join(align_dir, "alignment_frames.txt"), "w") as frames_file, \
+            open(os.path.join(align_dir, "alignment_segments.txt"), "w") as segments_file:
+        clock = time.perf_counter()
+        for data in loader:
+            with torch.no_grad():
+                seq, sizeSeq, phone, sizePhone = prepare_data(data)
+                clock = lap("audio", clock)
+                c_feature = model(seq, None)[0]
+                clock = lap("model", clock)
+                frames = sizeSeq // downsampling_factor
+                predictions = criterion.getPrediction(c_feature, frames)         # (eval mode, no gradients: what align does)
+                clock = lap("head", clock)
+                res = criterion.align_predictions(predictions, frames, phone, sizePhone)
+                t_max, max_l = res.path.shape[1], res.first.shape[1]
+                packed = torch.cat([res.path.double(), res.labels.double(), res.first.double(), res.last.double(),
+                                    res.confidence.double(), res.status.double().view(-1, 1), res.ties.double().view(-1, 1),
+                                    sizeSeq.double().view(-1, 1), sizePhone.double().view(-1, 1)], dim=1).cpu().numpy()
+                clock = lap("alignment", clock)
+            cuts = [t_max, 2 * t_max, 2 * t_max + max_l, 2 * t_max + 2 * max_l, 2 * t_max + 3 * max_l]
+            for row in packed:
+                name = names[at]
+                at += 1
+                path, labels = row[:cuts[0]].astype(np.int64), row[cuts[0]:cuts[1]].astype(np.int64)
+                conf = row[cuts[3]:cuts[4]]
+                status, tie, n_samples, n_labels = (int(v) for v in row[cuts[4]:cuts[4] + 4])
+                log["utterances"] += 1
+                if status != 0:
+                    log["no_alignment" if status == 1 else "invalid"].append(name)
+                    continue
+                log["aligned"] += 1
+                log["met_a_tie"] += tie
+                if n_labels == 0:
+                    log["empty_transcription"].append(name)
+                write_alignment(frames_file, segments_file, name, *utterance_alignment(path, labels, conf, n_samples, blank_label))
+            clock = lap("writing", clock)
+    return log
+
+
 def _with_prefix(state_dict):
     return {f"module.{k}": v for k, v in state_dict.items()}
 
@@ -611,9 +753,22 @@ def parse_args(argv):
     per.add_argument('--file_extension', type=str, default=".wav")
     per.add_argument('--name', type=str, default="0", help="suffix of the log and argument files")
 
+    align = commands.add_parser('align', help="forced alignment of transcriptions with the head of a run directory written by train")
+    align.add_argument('output', type=str, help="run directory")
+    align.add_argument('-o', '--align_dir', type=str, required=True, help="directory the alignment files are written to (empty or new)")
+    align.add_argument('--batchSize', type=int, default=8, help="utterances per batch")
+    align.add_argument('--debug', action='store_true', help="at most 100 utterances")
+    align.add_argument('--pathDB', type=str, default=None, help="another audio directory than the run's")
+    align.add_argument('--pathVal', type=str, default=None, help="another list of utterances than the run's")
+    align.add_argument('--pathPhone', type=str, default=None, help="other transcriptions than the run's")
+    align.add_argument('--file_extension', type=str, default=".wav")
+    align.add_argument('--blank_label', type=int, default=None,
+                       help="label written for blank frames (default: a blank frame takes the preceding token's label)")
+    align.add_argument('--name', type=str, default="0", help="suffix of the log file")
+
     args = parser.parse_args(argv)
     if args.command is None:
-        parser.error("a command is needed: train or per")
+        parser.error("a command is needed: train, per or align")
     return args
 
 
@@ -656,7 +811,9 @@ def main(argv):
     args = parse_args(argv)
     random.seed()
 
-    if args.command == 'per':
+    if args.command == 'align':
+        check_align_dir(args.align_dir)
+    if args.command in ('per', 'align'):
         args = get_PER_args(args)
     check_supported(args)
     if not torch.cuda.is_available():
@@ -665,7 +822,7 @@ def main(argv):
     if not os.path.isdir(args.output):
         os.mkdir(args.output)
 
-    name = f"_{args.name}" if args.command == "per" else ""
+    name = f"_{args.name}" if args.command in ("per", "align") else ""
     pathLogs = os.path.join(args.output, f'logs_{args.command}{name}.txt')
     with open(pathLogs, 'w') as log, contextlib.redirect_stdout(_Tee(sys.stdout, log)):
         return _main(args)
@@ -693,7 +850,40 @@ def _split(args, inSeqs):
     return seqTrain, seqVal
 
 
+def _main_align(args):
+    """`align`: the run is loaded the way `per` loads it; the head's size comes from the checkpoint, so that other
+    transcriptions than the run's (a label the head does not know makes that utterance invalid) can be aligned."""
+    phoneLabels = parse_transcripts(args.pathPhone)
+    inSeqs, _ = findAllSeqs(args.pathDB, extension=args.file_extension, loadCache=False)
+    _, seqVal = _split(args, inSeqs)
+    pathCheckpoint = os.path.join(args.output, 'checkpoint.pt')
+    print(f"Loading data at {pathCheckpoint}")
+    state_dict = torch.load(pathCheckpoint, map_location="cpu")
+    nPhones = _without_prefix(state_dict['classifier'])['PhoneCriterionClassifier.weight'].shape[0] - 1
+    feature_maker, hiddenGar, _ = loadModel([args.pathCheckpoint], loadStateDict=not args.no_pretraining)
+    feature_maker.cuda()
+    phone_criterion = CTCphone_criterion(hiddenGar, nPhones, args.LSTM, seqNorm=args.seqNorm, dropout=args.dropout,
+                                         reduction=args.loss_reduction)
+    phone_criterion.cuda()
+    load_checkpoint(state_dict, feature_maker, phone_criterion)
+    feature_maker.optimize = False
+    print(f"Loading the dataset at {args.pathDB}")
+    dataset = SingleSequenceDataset(args.pathDB, seqVal, phoneLabels, inDim=args.in_dim, random_offset_amplitude=0)
+    t0 = time.time()
+    log = alignStep(dataset.batches(args.batchSize, shuffle=False), dataset.names, feature_maker, phone_criterion, 160, args.align_dir,
+                    args.blank_label)
+    log["seconds"] = time.time() - t0
+    log["arguments"] = vars(args)
+    with open(os.path.join(args.align_dir, "alignment_log.json"), 'w') as file:
+        json.dump(log, file, indent=2)
+    print(f"{log['aligned']} of {log['utterances']} utterances aligned ({len(log['no_alignment'])} without a possible alignment, "
+          f"{len(log['invalid'])} invalid, {len(log['empty_transcription'])} with an empty transcription, {log['met_a_tie']} met a tie)")
+    return log
+
+
 def _main(args):
+    if args.command == 'align':
+        return _main_align(args)
     phoneLabels, nPhones = parseSeqLabels(args.pathPhone)
     inSeqs, _ = findAllSeqs(args.pathDB, extension=args.file_extension, loadCache=False)
     seqTrain, seqVal = _split(args, inSeqs)

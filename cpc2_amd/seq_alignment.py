@@ -9,7 +9,25 @@ the previous frame's beam, symbol) -- a prefix that is not extended counts as it
 reference compares the prefixes' decimal strings.  The order is a function of the inputs alone (two runs give the same bytes),
 and the search reports per sequence whether any frame met a tie among its first nKeep + 1 candidates.  A sequence whose scores
 underflow to exactly 0 becomes all ties, as in the reference.
+
+CTC forced alignment (ctc_forced_align, frame_labels; csrc/ctc_align.hip, include/cpc2_hip.h version 120) is NOT the reference's:
+it has no aligner, so the definition is the specification.  One sequence has logits x [T][k] (float32), targets y[0..L) and
+blank = k - 1; extended states s in [0, 2 L + 1), sym(s) = blank for even s and y[s // 2] for odd s.  Every alignment emits one
+symbol per frame, so sum_t lse_t is common to all paths and the maximisation runs on the raw logits:
+    start  v[0][0] = x[0][blank]; v[0][1] = x[0][y0] when L >= 1; every other state -inf
+    step   v[t][s] = max(v[t-1][s], v[t-1][s-1] when s >= 1, v[t-1][s-2] when s is odd, s >= 3 and y[s//2] != y[s//2 - 1])
+                     + x[t][sym(s)], all float64, the max first, then ONE addition (a host statement with the same operation
+           order gives the same bits)
+    ties   among equal finite candidates s wins over s - 1, which wins over s - 2; at the end state 2 L wins over 2 L - 1 unless
+           the latter is strictly larger.  ties = 1 when a maximum on the returned path, the end included, had an equal finite
+           competitor
+    status 0 aligned; 1 no alignment exists (T < L + #{i: y[i] == y[i-1]}, or T = 0); 2 an argument of that sequence is invalid
+           (input length outside [0, t_max], target length outside [0, max_l], a label outside [0, k - 1)).  With 1 or 2 the
+           path is -1 on every frame, the scores are NaN and first / last / confidence are -1 / -1 / NaN.
+Agreement with torchaudio.functional.forced_align is UNMEASURED (torchaudio is not a dependency and was not at hand).
 """
+from collections import namedtuple
+
 import numpy as np
 import torch
 
@@ -99,6 +117,119 @@ def beam_search(score_preds, nKeep, blankLabel):
     scores, sizes, labels, counts, _ = beam_search_batch(probs.float().unsqueeze(0), None, nKeep, blankLabel)
     scores, sizes, labels = scores[0].cpu().numpy(), sizes[0].cpu().numpy(), labels[0].cpu().numpy()
     return [(scores[i], [int(x) for x in labels[i, :sizes[i]]]) for i in range(int(counts[0]))]
+
+
+# --------------------------------------------------------------------------- CTC forced alignment
+MAX_ALIGN_TARGET = 1024        # cpc_ctc_align: labels per utterance (the extended states live in LDS)
+
+AlignResult = namedtuple("AlignResult", ["path", "labels", "score", "log_prob", "status", "ties", "first", "last", "confidence"])
+AlignResult.__doc__ = """ctc_forced_align's result, all on the device, b sequences of up to t_max frames and max_l labels:
+path int32 [b, t_max] (the state per frame, -1 from the input length on), labels int64 [b, t_max] (the path mapped through sym:
+a target label, the blank k - 1, or -1 where the path is -1), score float64 [b] (the path's logit sum), log_prob float64 [b]
+(score - sum_t lse_t: the path's log posterior), status int32 [b], ties int32 [b], first / last int32 [b, max_l] (the first and
+last frame of every token, -1 beyond the target length) and confidence float32 [b, max_l] (the mean log posterior of the token's
+label over its frames)."""
+
+
+def ctc_forced_align(logits, in_lengths, targets, tgt_lengths):
+    """The best CTC alignment (module docstring) of logits [b, t_max, k] float32 (blank = k - 1) with int64 device tables
+    in_lengths [b], targets [b, W], tgt_lengths [b] -> AlignResult.  Rows of logits at or beyond an input length and target padding
+    are never read.  Targets wider than the kernel holds (min(t_max, 1024) labels) are cut to that width: a sequence whose target
+    length lies beyond it then has status 2.  Two launches, no float atomic, and no copy to the host: the caller synchronises when
+    it reads the result."""
+    if logits.dim() != 3 or targets.dim() != 2:
+        raise ValueError(f"ctc_forced_align: logits must be [b, t_max, k] and targets [b, W] (got {tuple(logits.shape)} and "
+                         f"{tuple(targets.shape)})")
+    require_gpu(logits, in_lengths, targets, tgt_lengths)
+    lib = _lib.load()
+    logits = _lib.f32c(logits)
+    b, t, k = logits.shape
+    dev = logits.device
+    if in_lengths.shape != (b,) or tgt_lengths.shape != (b,) or targets.shape[0] != b:
+        raise ValueError(f"ctc_forced_align: {b} sequences, but in_lengths {tuple(in_lengths.shape)}, targets {tuple(targets.shape)}, "
+                         f"tgt_lengths {tuple(tgt_lengths.shape)}")
+    max_l = min(targets.shape[1], t, MAX_ALIGN_TARGET)
+    nbytes = lib.cpc_ctc_align_scratch_bytes(b, t, max_l)
+    if nbytes == 0:
+        raise ValueError("ctc_forced_align: " + lib.cpc_last_error().decode(errors="replace"))
+    in_lengths = in_lengths.to(torch.int64).contiguous()
+    tgt_lengths = tgt_lengths.to(torch.int64).contiguous()
+    targets = targets[:, :max_l].to(torch.int64).contiguous()
+    path = torch.empty(b, t, dtype=torch.int32, device=dev)
+    score = torch.empty(b, 2, dtype=torch.float64, device=dev)
+    status = torch.empty(b, dtype=torch.int32, device=dev)
+    ties = torch.empty(b, dtype=torch.int32, device=dev)
+    lse = torch.empty(b, t, dtype=torch.float64, device=dev)
+    first = torch.empty(b, max_l, dtype=torch.int32, device=dev)
+    last = torch.empty(b, max_l, dtype=torch.int32, device=dev)
+    conf = torch.empty(b, max_l, dtype=torch.float32, device=dev)
+    buf = _lib.scratch(nbytes, dev)
+    tg = ptr(targets) if max_l else None
+    check(lib.cpc_ctc_align(ptr(logits), b, t, k, ptr(in_lengths), tg, max_l, ptr(tgt_lengths), ptr(path), ptr(score), ptr(status),
+                            ptr(ties), ptr(lse), ptr(buf), buf.numel(), stream_ptr(dev)), "ctc_align")
+    if max_l:
+        check(lib.cpc_ctc_align_segments(ptr(logits), b, t, k, tg, max_l, ptr(tgt_lengths), ptr(path), ptr(status), ptr(lse), ptr(first),
+                                         ptr(last), ptr(conf), stream_ptr(dev)), "ctc_align_segments")
+    blank = torch.full_like(path, k - 1, dtype=torch.int64)
+    if max_l:
+        token = targets.gather(1, (path.clamp(min=0) >> 1).clamp(max=max_l - 1).to(torch.int64))
+        labels = torch.where((path & 1) == 1, token, blank)
+    else:
+        labels = blank
+    labels = torch.where(path < 0, torch.full_like(labels, -1), labels)
+    return AlignResult(path, labels, score[:, 0], score[:, 1], status, ties, first, last, conf)
+
+
+def _host(x):
+    return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
+def head_frame_of(n_frames, n_head, kernel=8, stride=4):
+    """For each of n_frames feature frames the head frame whose receptive-field centre is nearest:
+    j = clamp((f - (kernel - stride) // 2) // stride, 0, n_head - 1); (f - 2) // 4 for the default head."""
+    f = np.arange(int(n_frames), dtype=np.int64)
+    return np.clip((f - (kernel - stride) // 2) // stride, 0, max(int(n_head) - 1, 0))
+
+
+def head_tokens(path_row):
+    """The token index of every head frame of one path (numpy, -1 padded): a frame in state 2 i + 1 has token i, a blank frame the
+    preceding token, leading blanks the first token.  None when the path holds no token (L = 0 or no alignment)."""
+    path_row = np.asarray(path_row)
+    states = path_row[path_row >= 0]
+    if len(states) == 0 or states[-1] == 0:
+        return None
+    return np.maximum((states.astype(np.int64) - 1) // 2, 0)
+
+
+def frame_labels(result, n_frames, kernel=8, stride=4, blank_label=None):
+    """One label per 10 ms feature frame for every sequence of an AlignResult (or anything with `path` and `labels`, tensors or
+    arrays [b, t_max]): n_frames [b] feature frames each -> a list of int64 arrays, None for a sequence without frame labels.
+    Feature frame f takes head frame j = clamp((f - (kernel - stride) // 2) // stride, 0, T - 1), T = the frames of the path.
+    Blank head frames take the preceding token's label and leading blanks the first token's; with blank_label given they take
+    that id instead.  A sequence with status 1 or 2 has none, nor has one with L = 0 unless blank_label is given.  The tensors
+    come to the host here (hand over host arrays to copy once for several uses)."""
+    path, labels = _host(result.path), _host(result.labels)
+    out = []
+    for row in range(path.shape[0]):
+        states = path[row][path[row] >= 0]
+        n_head = len(states)
+        if n_head == 0:
+            out.append(None)
+            continue
+        lab = labels[row, :n_head].astype(np.int64)
+        if blank_label is not None:
+            head = np.where(states & 1, lab, int(blank_label))
+        else:
+            tokens = head_tokens(states)
+            if tokens is None:
+                out.append(None)
+                continue
+            token_label = np.zeros(int(tokens.max()) + 1, np.int64)
+            odd = (states & 1) == 1
+            token_label[(states[odd] - 1) // 2] = lab[odd]
+            head = token_label[tokens]
+        out.append(head[head_frame_of(int(n_frames[row]), n_head, kernel, stride)])
+    return out
 
 
 # --------------------------------------------------------------------------- alignment score and phone error rate

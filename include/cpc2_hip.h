@@ -54,7 +54,8 @@ int cpc_version(void);          /* 100 x major + minor; 105 = the entry points o
                                   * cpc_gather_utterances;
                                   * 118 = cpc_moments_scratch_bytes / cpc_moments_accumulate;
                                   * 119 = cpc_mfcc_tables_doubles / cpc_mfcc_tables_host / cpc_mfcc_frame_tile / cpc_melspec_scratch_bytes /
-                                  * cpc_melspec_db / cpc_mfcc_finish / cpc_deltas */
+                                  * cpc_melspec_db / cpc_mfcc_finish / cpc_deltas;
+                                  * 120 = cpc_ctc_align (+ scratch query) / cpc_ctc_align_segments */
 const char *cpc_last_error(void);
 
 /* In-situ kernel timing for bench.py: when enabled, the launchers bracket each launch of the named
@@ -797,6 +798,49 @@ int cpc_conv_head_backward_data(const float *dout, const float *wp, int b, int s
                                 cpc_stream_t stream);
 int cpc_gather_utterances(const float *pack, long total, const int64_t *offsets, const int64_t *lengths, const int64_t *roffset,
                           float *out, int n, long max_len, cpc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * CTC forced alignment of whole utterances (csrc/ctc_align.hip; cpc2_amd/seq_alignment.py: ctc_forced_align; DESIGN.md section
+ * 19).  version 120.  Every pointer is a DEVICE pointer, row-major and contiguous; lengths and targets are int64 (torch.long).
+ * The reference has no aligner: the definition below is the specification.  Agreement with torchaudio.functional.forced_align
+ * is UNMEASURED.
+ *
+ * One sequence has logits x [T][k] (f32, T = its input length), targets y[0..L) and blank = k - 1 (the convention of cpc_ctc_loss
+ * and cpc_probe_ctc).  Extended states are s in [0, 2 L + 1): sym(s) = blank for even s and y[s / 2] for odd s.  Every alignment
+ * emits exactly one symbol per frame, so sum_t lse_t is the same for all paths: the maximisation runs on the raw logits and the
+ * normaliser enters only the reported score.  No exp or log occurs inside the recurrence.
+ *   Start.  v[0][0] = (double) x[0][blank]; v[0][1] = (double) x[0][y0] when L >= 1; every other state is -inf.
+ *   Step.   v[t][s] = max(v[t-1][s], v[t-1][s-1] when s >= 1, v[t-1][s-2] when s is odd, s >= 3 and y[s/2] != y[s/2 - 1])
+ *           + (double) x[t][sym(s)].  All values are f64; the max first, then ONE addition (the file is built with
+ *           -ffp-contract=off): a host program with the same operation order gives the same bits.
+ *   Ties inside a step (equal finite candidates): staying in s wins over s - 1, which wins over s - 2.
+ *   End.    State 2 L wins over 2 L - 1 unless v[T-1][2L-1] is strictly larger.  With L = 0 there is only state 0.
+ *   ties [b]     1 when a maximum ON THE RETURNED PATH had an equal finite competitor, the choice at the end included; else 0
+ *                (0 with status 1 or 2).
+ *   status [b]   0 = aligned; 1 = no alignment exists: T < L + #{i : y[i] == y[i-1]}, and T = 0 whatever L (there is no frame to
+ *                start from); 2 = an argument of that sequence is invalid: input length outside [0, t_max], target length
+ *                outside [0, max_l], or a label outside [0, k - 1).  With status 1 or 2 path is -1 on all t_max frames, both
+ *                scores and all of lse are NaN, and first / last / conf are -1 / -1 / NaN.
+ *   path [b][t_max]   the state index for t < T, -1 for T <= t < t_max
+ *   score [b][2]      score[0] = the path's logit sum v[T-1][end]; score[1] = score[0] - sum_t lse_t, lse_t the f64
+ *                     log-sum-exp of frame t, max-shifted as in cpc_ctc_loss (the sum over t in a fixed order)
+ *   lse [b][t_max]    optional (may be NULL): lse_t for t < T, NaN behind; cpc_ctc_align_segments needs it
+ * cpc_ctc_align_segments: for each token i < L of an aligned sequence first[i] and last[i] = the first and last frame whose state
+ *   is 2 i + 1, and conf[i] = the mean over those frames of x[t][y[i]] - lse_t, summed in f64 in frame order and stored as f32.
+ *   first, last, conf are [b][max_l]; tokens at or beyond L get -1 / -1 / NaN.  max_l = 0 writes nothing.
+ * Limits (those of cpc_ctc_loss): 1 <= t_max <= 4096, 2 <= k <= 65536, 0 <= max_l <= min(t_max, 1024), 1 <= b <= 65535; anything
+ *   else is CPC_ERR_INVALID with a message in cpc_last_error, and the scratch query returns 0 with a message.
+ *   scratch: cpc_ctc_align_scratch_bytes(b, t_max, max_l) (f64 [b][t_max] + one byte of back-pointer per (frame, state):
+ *   [b][t_max][2 max_l + 1], 8.4 MB per sequence at the limit); too little gives CPC_ERR_WORKSPACE.
+ * No float atomic: two launches give the same bytes.  Rows of logits at or beyond in_lengths[i] and target padding are never read.
+ * ------------------------------------------------------------------------------------------ */
+size_t cpc_ctc_align_scratch_bytes(int b, int t_max, int max_l);
+int cpc_ctc_align(const float *logits, int b, int t_max, int k, const int64_t *in_lengths, const int64_t *targets, int max_l,
+                  const int64_t *tgt_lengths, int *path, double *score, int *status, int *ties, double *lse /* may be NULL */,
+                  void *scratch, size_t scratch_bytes, cpc_stream_t stream);
+int cpc_ctc_align_segments(const float *logits, int b, int t_max, int k, const int64_t *targets, int max_l, const int64_t *tgt_lengths,
+                           const int *path, const int *status, const double *lse, int *first, int *last, float *conf,
+                           cpc_stream_t stream);
 
 #ifdef __cplusplus
 }
