@@ -112,6 +112,9 @@ SIGNATURES = {
     "cpc_kmeans_accumulate": (c_int, [c_ptr, c_long, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_size_t, c_ptr]),
     "cpc_moments_scratch_bytes": (c_size_t, [c_long, c_int, c_int]),
     "cpc_moments_accumulate": (c_int, [c_ptr, c_long, c_int, c_ptr, c_long, c_int, c_long, c_ptr, c_ptr, c_ptr, c_size_t, c_ptr]),
+    "cpc_seq_moments_scratch_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "cpc_seq_moments_accumulate": (c_int, [c_ptr, c_long, c_long, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_size_t, c_ptr]),
+    "cpc_center_scale_rows": (c_int, [c_ptr, c_long, c_ptr, c_ptr, c_ptr, c_long, c_long, c_int, c_ptr]),
     "cpc_mfcc_tables_doubles": (c_long, [c_int, c_int, c_int]),
     "cpc_mfcc_tables_host": (c_int, [c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, c_ptr, c_long]),
     "cpc_mfcc_frame_tile": (c_int, []),

@@ -55,7 +55,8 @@ int cpc_version(void);          /* 100 x major + minor; 105 = the entry points o
                                   * 118 = cpc_moments_scratch_bytes / cpc_moments_accumulate;
                                   * 119 = cpc_mfcc_tables_doubles / cpc_mfcc_tables_host / cpc_mfcc_frame_tile / cpc_melspec_scratch_bytes /
                                   * cpc_melspec_db / cpc_mfcc_finish / cpc_deltas;
-                                  * 120 = cpc_ctc_align (+ scratch query) / cpc_ctc_align_segments */
+                                  * 120 = cpc_ctc_align (+ scratch query) / cpc_ctc_align_segments;
+                                  * 121 = cpc_seq_moments_scratch_bytes / cpc_seq_moments_accumulate / cpc_center_scale_rows */
 const char *cpc_last_error(void);
 
 /* In-situ kernel timing for bench.py: when enabled, the launchers bracket each launch of the named
@@ -549,6 +550,38 @@ int cpc_kmeans_accumulate(const float *x, long n, int d, const int *index, int k
 size_t cpc_moments_scratch_bytes(long n, int dx, int dy);
 int cpc_moments_accumulate(const float *x, long ldx, int dx, const float *y, long ldy, int dy, long n,
                            double *sums, double *gram, void *scratch, size_t scratch_bytes, cpc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Second moments of windows of frames and of their frame-to-frame differences in f64 (the PCA / SFA projections of
+ * cpc2_amd/dim_reduction.py; csrc/seqmoments.hip).  version 121.
+ * x is [b][s][d] fp32 on the DEVICE with row stride ld >= d and sequence stride seq_stride >= s * ld (both in elements).  Of each
+ * sequence the frames t = skip .. s-1 are kept, and in ONE pass over x the running f64 DEVICE totals become
+ *   sums[d]     += sum x_t                                    over the kept frames,
+ *   gram[d][d]  += sum x_t x_t^T                              over the kept frames,
+ *   dgram[d][d] += sum (x_{t+1} - x_t) (x_{t+1} - x_t)^T      over t = skip .. s-2 of each sequence.
+ * gram and dgram are row-major and FULL: both triangles are written and are equal bit for bit.  The caller zeroes the three once and
+ * keeps the counts itself (b * (s - skip) rows, b * (s - skip - 1) differences).  With s - skip == 1 there is no difference and dgram
+ * is left as it was.
+ * The difference is taken in f64 from the two f32 values (exact) and never across a sequence boundary; products are accumulated
+ * in f64 on v_mfma_f64_16x16x4_f64 as cpc_moments_accumulate does, a fresh chain per slab of 32 rows added to the running tile in
+ * plain f64.  The split of the rows depends on (b, s, skip, d) alone and there is no float atomic: the same call gives the same bits.
+ * Skipped frames, the columns beyond d and the gap between sequences are never read, so nothing in them (a NaN included) reaches
+ * a result; no padded copy, no f64 copy and no difference tensor is made.
+ * Limits: 1 <= d <= 512, b >= 1, 0 <= skip < s, b * s < 2^31.  A call outside them, a stride below the width, a null buffer or a
+ * scratch below cpc_seq_moments_scratch_bytes(b, s, skip, d) returns CPC_ERR_INVALID with a message before any launch, and the
+ * size query returns 0 outside the limits.
+ *
+ * cpc_center_scale_rows: y[r][c] = (x[r][c] - mean[c]) / (scale[c] + 1e-8f) for r < n, c < d, in f32 with each of the three
+ * operations rounded once (a correctly rounded division): what the reference's SFALinear.forward does in two in-place passes.
+ * scale == NULL leaves the division out (its PCA.forward).  x, y are fp32 DEVICE rows with strides ldx, ldy >= d; y is apart from x,
+ * or y == x with ldy == ldx.  Limits: n >= 1, 1 <= d <= 512; anything else is CPC_ERR_INVALID with a message before any launch.
+ * ------------------------------------------------------------------------------------------ */
+size_t cpc_seq_moments_scratch_bytes(int b, int s, int skip, int d);
+int cpc_seq_moments_accumulate(const float *x, long ld, long seq_stride, int b, int s, int skip, int d,
+                               double *sums, double *gram, double *dgram,
+                               void *scratch, size_t scratch_bytes, cpc_stream_t stream);
+int cpc_center_scale_rows(const float *x, long ldx, const float *mean, const float *scale,
+                          float *y, long ldy, long n, int d, cpc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Log-mel and MFCC baseline features (cpc2_amd/spectral.py; csrc/mfcc.hip).  version 119.
