@@ -62,11 +62,13 @@ def _refuse_without_gpu():
 
 
 def beam_search_batch(probs, lengths, nKeep, blankLabel, best_only=False):
-    """probs [N, T, P] f32 probabilities on the device, lengths [N] (frames of row n to decode, 1 <= lengths[n] <= T; None: T
-    everywhere) -> (scores f32 [N, R], sizes int32 [N, R], labels int32 [N, R, T], counts int32 [N], ties int32 [N]) on the
-    device, R = 1 with best_only (the best prefix only) else nKeep: the kept prefixes best first, labels padded with -1, counts
-    the rows that hold a prefix (fewer than nKeep exist only in the first frames), ties whether a frame met equal scores among
-    its first nKeep + 1 candidates.  Rows of probs beyond lengths[n] are never read.  Nothing comes to the host."""
+    """probs [N, T, P] f32 probabilities on the device, lengths [N] (frames of row n to decode; None: T everywhere) -> (scores
+    f32 [N, R], sizes int32 [N, R], labels int32 [N, R, T], counts int32 [N], ties int32 [N]) on the device, R = 1 with
+    best_only (the best prefix only) else nKeep: the kept prefixes best first, labels padded with -1, counts the rows that hold
+    a prefix (fewer than nKeep exist only in the first frames), ties whether a frame met equal scores among its first nKeep + 1
+    candidates.  lengths[n] is clamped to [0, T]: a length above T decodes the T frames there are, and a length of 0 or below
+    decodes nothing -- that row returns the empty prefix alone, with score 1.0, counts 1 and ties 0.  Rows of probs beyond
+    lengths[n] are never read.  Nothing comes to the host."""
     if probs.dim() != 3:
         raise ValueError(f"beam_search_batch: probs must be [N, T, P] (got {tuple(probs.shape)})")
     n, t, p = probs.shape

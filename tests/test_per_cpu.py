@@ -69,6 +69,42 @@ def test_oracle_on_tied_cases_differs_only_inside_groups_of_equal_scores(golden,
         assert mine[0] == (int(np.float32(1.09).view(np.uint32)), [10])
 
 
+def test_oracle_stats_describe_the_search_and_do_not_change_it(golden):
+    """beam_search(..., stats={}) reports what the input made the search do -- where the cut between the nKeep-th and the next
+    candidate falls, groups of equal scores across it, folds, re-entries -- consistently with the returned tie flag, and returns
+    what the call without it returns."""
+    g = golden("g26_per.npz")
+    by_name = {c["name"]: c for c in json.loads(str(g["meta"]))["search"]}
+    for name in ("T6P5k4_tied", "T32P9k20_blankmid", "T96P42k20_rand"):
+        case, probs = by_name[name], g[f"bs_{name}_probs"]
+        plain, tie = per_oracle.beam_search(probs, case["nKeep"], case["blank"])
+        stats = {}
+        out, tie_s = per_oracle.beam_search(probs, case["nKeep"], case["blank"], stats=stats)
+        assert as_bits(out) == as_bits(plain) and tie_s == tie
+        assert set(stats) == {"levels", "groups", "folds", "reentries", "rejoined", "max_beam", "nodes"}
+        assert set(stats["levels"]) <= {0, 1, 2, 3, "tie"}
+        assert stats["levels"].count("tie") == len(stats["groups"])
+        assert tie or "tie" not in stats["levels"]              # a tie across the cut is a tie among the first nKeep + 1
+        assert stats["max_beam"] == case["nKeep"] and 0 <= stats["rejoined"] <= stats["reentries"]
+        # a frame has more candidates than nKeep from the first one that extends more than nKeep / P prefixes on
+        assert len(stats["levels"]) >= case["T"] - 2 and stats["nodes"] <= 1 + case["T"] * case["nKeep"]
+        for group in stats["groups"]:
+            assert 0 < group["need"] < group["size"] <= group["hi"] - group["lo"] + 1
+            assert group["lo"] <= group["taken_hi"] < group["hi"] < case["nKeep"] * case["P"]
+        if name == "T6P5k4_tied":
+            assert tie and stats["groups"] and stats["folds"] > 0
+        else:
+            assert not tie and not stats["groups"] and "tie" not in stats["levels"] and stats["folds"] > 0
+    # by hand: two frames of (0.5, 0.25, 0.25), blank 0, nKeep 2.  Frame 0: "" 0.5, then "1" and "2" at 0.25 -- three candidates,
+    # the second and the third equal (slots 1 and 2), one of them taken.  Frame 1 extends "" and "1": "" 0.25, "1" 0.125 + 0.0625
+    # + its extension from "" 0.125 (a fold) = 0.3125, "2" 0.125 (it had no node: no re-entry), "12" 0.0625, "11" 0 (pb of "1").
+    stats = {}
+    out, tie = per_oracle.beam_search(np.array([[0.5, 0.25, 0.25]] * 2, np.float32), 2, 0, stats=stats)
+    assert [(float(s), lab) for s, lab in out] == [(0.3125, [1]), (0.25, [])] and tie
+    assert stats == dict(levels=["tie", 2], groups=[dict(frame=0, size=2, lo=1, hi=2, need=1, taken_hi=1)], folds=1, reentries=0, rejoined=0,
+                         max_beam=2, nodes=2)
+
+
 def test_oracle_alignment_score_equals_the_reference(golden):
     g = golden("g26_per.npz")
     for i in range(len(g["al_len1"])):
