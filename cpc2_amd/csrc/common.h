@@ -163,6 +163,10 @@ int colsum_split(const float *part, long rows, long ld, int width, float *out0, 
 // column sums of a [rows][width] matrix with row stride ld (two-stage; scratch >= colsum_scratch_bytes)
 size_t colsum_rows_scratch_bytes(int width);
 int colsum_rows(const float *a, long ld, long rows, int width, float *out, void *scratch, hipStream_t st);
+// cpc_ctc_loss behind its checks (ctc_head.hip); in_lengths == nullptr: every input length is t_max.  scratch holds
+// cpc_ctc_loss_scratch_bytes(b, t_max, max_l)
+int ctc_loss_run(const float *logits, int b, int t_max, int k, const int64_t *in_lengths, const int64_t *targets, int max_l,
+                 const int64_t *tgt_lengths, int reduction, float *nll, float *loss, float *dlogits, void *scratch, hipStream_t st);
 
 int transpose2d(const float *a, float *at, int rows, int cols, hipStream_t st);                      // at[c][r]=a[r][c]
 

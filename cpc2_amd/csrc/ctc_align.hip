@@ -12,8 +12,8 @@
 //          2 L - 1 unless v[T-1][2L-1] is strictly larger.  ties = 1 when a maximum ON THE RETURNED PATH (the end included) had an
 //          equal finite competitor.
 //
-//   ctc_align_kernel     one workgroup per sequence.  The frames' log-sum-exp in f64 first (one wave per frame, max-shifted as in
-//                        ctc_len_kernel), then the recurrence: the 2 L + 1 values double-buffered in LDS next to the symbol table
+//   ctc_align_kernel     one workgroup per sequence.  The extended states and the frames' log-sum-exp in f64 first (one wave per
+//                        frame, max-shifted: ctc_lattice.h, shared with ctc_len_kernel), then the recurrence: the 2 L + 1 values double-buffered in LDS next to the symbol table
 //                        (41 KB at 1024 labels), threads strided over the states, one barrier per frame; the logit a state adds
 //                        in frame t + 1 is fetched while frame t is computed.  Only the states of the reachable band
 //                        2 L - 2 (T - 1 - t) - 1 <= s <= 2 t + 1 are computed: a state reads only states of the previous
@@ -25,6 +25,7 @@
 //                        in frame order by one thread.
 // No float atomic: two launches give the same bytes.  Frames at or beyond an input length and target padding are never read.
 #include "common.h"
+#include "ctc_lattice.h"
 
 #include <algorithm>
 
@@ -70,15 +71,7 @@ ctc_align_kernel(const float *__restrict__ logits, int t_max, int K, const int64
 
     if (tid == 0) { s_bad = len_ok ? 0 : 1; s_rep = 0; }
     __syncthreads();
-    for (int s = tid; s < S; s += CA_THREADS) {
-        int lab = blank;
-        if (s & 1) {
-            const int64_t v = targets[(size_t)seq * max_l + (s >> 1)];
-            if (v < 0 || v >= blank) s_bad = 1;              // (benign race: every writer stores 1)
-            lab = (v >= 0 && v < blank) ? (int)v : blank;
-        }
-        s_ext[s] = lab;
-    }
+    if (load_ext_states<CA_THREADS>(targets + (size_t)seq * max_l, S, blank, s_ext)) s_bad = 1;      // (benign race: all store 1)
     __syncthreads();
     for (int i = 1 + tid; i < L; i += CA_THREADS)
         if (s_ext[2 * i + 1] == s_ext[2 * i - 1]) atomicAdd(&s_rep, 1);      // (an integer count: the order does not matter)
@@ -95,29 +88,10 @@ ctc_align_kernel(const float *__restrict__ logits, int t_max, int K, const int64
         return;
     }
 
-    // log-sum-exp of every frame < T (one wave per frame, f64; ctc_len_kernel's statement)
+    // log-sum-exp of every frame < T (one wave per frame, f64)
     for (int f = tid >> 6; f < T; f += CA_THREADS / 64) {
-        const int lane = tid & 63;
-        double m = neg_inf, acc = 0.0;
-        for (int j = lane; j < K; j += 64) {
-            const double v = (double)x[(size_t)f * K + j];
-            if (v > m) {
-                acc = (m == neg_inf ? 0.0 : acc * exp(m - v)) + 1.0;
-                m = v;
-            } else {
-                acc += exp(v - m);
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const double om = __shfl_xor(m, o), oa = __shfl_xor(acc, o);
-            const double nm = fmax(m, om);
-            if (nm != neg_inf) {
-                acc = (m == neg_inf ? 0.0 : acc * exp(m - nm)) + (om == neg_inf ? 0.0 : oa * exp(om - nm));
-                m = nm;
-            }
-        }
-        if (lane == 0) lse[f] = m + log(acc);
+        const double v = frame_lse(x + (size_t)f * K, K, tid & 63);
+        if ((tid & 63) == 0) lse[f] = v;
     }
     for (int t = T + tid; t < t_max; t += CA_THREADS) { pth[t] = -1; lse[t] = __builtin_nan(""); }
 

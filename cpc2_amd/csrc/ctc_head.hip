@@ -1,16 +1,20 @@
 // The whole-utterance CTC phone recogniser of the reference's cpc/eval/common_voices_eval.py (CTCphone_criterion): what its head
 // needs beyond the GEMMs and the LSTM.  DESIGN.md section 16 has the layout.
 //
-//   ctc_len_kernel            probe_ctc_kernel (probe.hip) with an input length per sequence and both reductions: one workgroup
-//                             per sequence, log-sum-exp of the frames < len in f64 (global scratch, not LDS: t_max reaches 4096),
-//                             alpha and beta in f64 log space over the 2 L + 1 extended states (two LDS rows), alpha + beta of every
-//                             (t, s) in global scratch.  Frames >= len are never read.
+//   ctc_len_kernel            one workgroup per sequence: log-sum-exp of the frames < len in f64 (global scratch, not LDS: t_max
+//                             reaches 4096), alpha and beta in f64 log space over the 2 L + 1 extended states (two LDS rows), alpha
+//                             + beta of every (t, s) in global scratch.  f64 because the log-probabilities reach |log alpha| ~
+//                             T log K (~480 at T = 128, K = 42), where one f32 ulp is 3e-5 -- an error the occupancy exp(alpha +
+//                             beta - log p - log y) would carry whole.  Frames >= len are never read; without an array of input
+//                             lengths every length is t_max.
 //   ctc_grad_kernel           the gradient softmax - occupancy per (t, class), the occupancy summed over the states of that class in
-//                             ascending state order; 1024 elements of one sequence per workgroup, so the gradient fills the chip
-//                             where the sequential passes cannot.  Frames >= len get exactly 0.  The
-//                             arithmetic of a frame is probe_ctc_kernel's operation for operation: with every length = t_max and
-//                             the mean reduction the two give the same bits.
+//                             ascending state order (a label that occurs several times in the target shares its class's bin); 1024
+//                             elements of one sequence per workgroup, so the gradient fills the chip where the sequential passes
+//                             cannot.  Frames >= len get exactly 0.
 //   ctc_reduce_kernel         the loss as one workgroup's fixed-order sum.
+//   ctc_loss_run              the three launches; cpc_ctc_loss calls it, and cpc_probe_ctc (probe.hip) with no input lengths and
+//                             the mean reduction.  The lattice's shared pieces (extended states, frame log-sum-exp, log_add) are
+//                             in ctc_lattice.h.
 //   seqnorm_len_*_kernel      per (utterance, channel) statistics over the frames < len, applied to all frames; a workgroup owns 64
 //                             channels of one utterance, four waves share the frames, f64 sums merged in a fixed order.
 //   cpc_conv_head_forward     no kernel: cpc_gemm_nt's launcher once per utterance over the overlapping rows of the features, with
@@ -21,6 +25,7 @@
 //   gather_utt_kernel         the zero-padded batch of whole utterances out of the resident pack.
 // No float atomic anywhere: every result is bitwise reproducible.
 #include "common.h"
+#include "ctc_lattice.h"
 
 #include <algorithm>
 
@@ -37,14 +42,7 @@ enum { CTC_NO_ALIGNMENT = 0, CTC_FEASIBLE = 1, CTC_BAD = 2 };
 constexpr int SN_CH = 64;                    // channels per workgroup (one per lane)
 constexpr int SN_SL = CH_THREADS / SN_CH;    // waves sharing the frames
 
-__device__ __forceinline__ double log_add(double a, double b)
-{
-    const double m = fmax(a, b);
-    if (m == -__builtin_inf()) return m;
-    return m + log1p(exp(fmin(a, b) - m));
-}
-
-// logits [b][t_max][k] (blank = k - 1); in_lengths [b]; targets [b][max_l], tgt_lengths [b]; lse_all [b][t_max], work
+// logits [b][t_max][k] (blank = k - 1); in_lengths [b] or null (every length t_max); targets [b][max_l], tgt_lengths [b]; lse_all [b][t_max], work
 // [b][t_max][2 max_l + 1] (f64).  nll[seq] = -log p, 0 when no alignment exists (zero_infinity; an input length of 0 included)
 // and NaN for a length or label out of range; logp_out[seq] and status[seq] hand log p and the sequence's kind to ctc_grad_kernel.
 __global__ void __launch_bounds__(CH_THREADS)
@@ -63,7 +61,7 @@ ctc_len_kernel(const float *logits, int t_max, int K, const int64_t *__restrict_
     double *wk = work + (long)seq * t_max * sw;
     double *s_lse = lse_all + (long)seq * t_max;
     const int64_t l64 = tgt_lengths[seq];
-    const int64_t t64 = in_lengths[seq];
+    const int64_t t64 = in_lengths ? in_lengths[seq] : t_max;
     const bool len_ok = l64 >= 0 && l64 <= max_l && t64 >= 0 && t64 <= t_max;
     const int L = len_ok ? (int)l64 : 0;
     const int T = len_ok ? (int)t64 : 0;
@@ -71,38 +69,11 @@ ctc_len_kernel(const float *logits, int t_max, int K, const int64_t *__restrict_
 
     if (tid == 0) s_bad = len_ok ? 0 : 1;
     __syncthreads();
-    for (int s = tid; s < S; s += CH_THREADS) {
-        int lab = blank;
-        if (s & 1) {
-            const int64_t v = targets[(long)seq * max_l + (s >> 1)];
-            if (v < 0 || v >= blank) s_bad = 1;              // (benign race: every writer stores 1)
-            lab = (v >= 0 && v < blank) ? (int)v : blank;
-        }
-        s_ext[s] = lab;
-    }
+    if (load_ext_states<CH_THREADS>(targets + (long)seq * max_l, S, blank, s_ext)) s_bad = 1;      // (benign race: all store 1)
     // log-sum-exp of every frame < T (one wave per frame, f64)
     for (int f = tid >> 6; f < T; f += CH_THREADS / 64) {
-        const int lane = tid & 63;
-        double m = -__builtin_inf(), acc = 0.0;
-        for (int j = lane; j < K; j += 64) {
-            const double v = (double)x[(long)f * K + j];
-            if (v > m) {
-                acc = (m == -__builtin_inf() ? 0.0 : acc * exp(m - v)) + 1.0;
-                m = v;
-            } else {
-                acc += exp(v - m);
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const double om = __shfl_xor(m, o), oa = __shfl_xor(acc, o);
-            const double nm = fmax(m, om);
-            if (nm != -__builtin_inf()) {
-                acc = (m == -__builtin_inf() ? 0.0 : acc * exp(m - nm)) + (om == -__builtin_inf() ? 0.0 : oa * exp(om - nm));
-                m = nm;
-            }
-        }
-        if (lane == 0) s_lse[f] = m + log(acc);
+        const double v = frame_lse(x + (long)f * K, K, tid & 63);
+        if ((tid & 63) == 0) s_lse[f] = v;
     }
     __syncthreads();                                     // (orders the workgroup's global writes of s_lse before its reads too)
     const bool bad = s_bad != 0;
@@ -187,11 +158,10 @@ ctc_grad_kernel(const float *logits, int t_max, int K, const int64_t *__restrict
     const int st = status[seq];
     const bool feasible = st == CTC_FEASIBLE;
     const int L = feasible ? (int)tgt_lengths[seq] : 0;      // (in range: the forward kernel checked both lengths)
-    const int T = feasible ? (int)in_lengths[seq] : 0;
+    const int T = feasible ? (in_lengths ? (int)in_lengths[seq] : t_max) : 0;
     const int S = 2 * L + 1;
-    if (feasible && first < (long)T * K) {                   // (uniform per workgroup; the labels are needed only then)
-        for (int s = tid; s < S; s += CH_THREADS) s_ext[s] = (s & 1) ? (int)targets[(long)seq * max_l + (s >> 1)] : blank;
-    }
+    // (uniform per workgroup; the labels are needed only then, and the forward kernel found them all in range)
+    if (feasible && first < (long)T * K) load_ext_states<CH_THREADS>(targets + (long)seq * max_l, S, blank, s_ext);
     __syncthreads();
     const float *x = logits + (long)seq * total;
     const double *wk = work + (long)seq * t_max * sw;
@@ -370,6 +340,31 @@ static bool ctc_sizes_ok(int b, int t_max, int max_l)
 }
 
 }  // namespace
+
+// The three launches of the CTC loss, for cpc_ctc_loss and cpc_probe_ctc: the callers have checked the sizes and that scratch
+// holds cpc_ctc_loss_scratch_bytes(b, t_max, max_l).
+int ctc_loss_run(const float *logits, int b, int t_max, int k, const int64_t *in_lengths, const int64_t *targets, int max_l,
+                 const int64_t *tgt_lengths, int reduction, float *nll, float *loss, float *dlogits, void *scratch, hipStream_t st)
+{
+    Carver carve(scratch);
+    double *lse = carve.take<double>((size_t)b * t_max);
+    double *work = carve.take<double>((size_t)b * t_max * (2 * (size_t)max_l + 1));
+    double *logp = carve.take<double>((size_t)b);
+    int *status = carve.take<int>((size_t)b);
+    hipLaunchKernelGGL(ctc_len_kernel, dim3((unsigned)b), dim3(CH_THREADS), 0, st, logits, t_max, k, in_lengths, targets, max_l,
+                       tgt_lengths, lse, work, nll, logp, status);
+    CPC_CHECK_LAUNCH("ctc_len_kernel");
+    if (dlogits != nullptr) {
+        const unsigned chunks = (unsigned)cdiv((long)t_max * k, CTC_GRAD_PER_WG);
+        hipLaunchKernelGGL(ctc_grad_kernel, dim3(chunks, (unsigned)b), dim3(CH_THREADS), 0, st, logits, t_max, k, in_lengths, targets,
+                           max_l, tgt_lengths, lse, work, logp, status, dlogits, reduction);
+        CPC_CHECK_LAUNCH("ctc_grad_kernel");
+    }
+    hipLaunchKernelGGL(ctc_reduce_kernel, dim3(1), dim3(CH_THREADS), 0, st, nll, tgt_lengths, (long)b, reduction, loss);
+    CPC_CHECK_LAUNCH("ctc_reduce_kernel");
+    return CPC_OK;
+}
+
 }  // namespace cpc
 
 extern "C" size_t cpc_ctc_loss_scratch_bytes(int b, int t_max, int max_l)
@@ -395,24 +390,8 @@ extern "C" int cpc_ctc_loss(const float *logits, int b, int t_max, int k, const 
     CPC_REQUIRE(logits && in_lengths && tgt_lengths && nll && loss && (targets || max_l == 0), "ctc_loss: null buffer");
     const size_t need = cpc_ctc_loss_scratch_bytes(b, t_max, max_l);
     CPC_REQUIRE(scratch != nullptr && scratch_bytes >= need, "ctc_loss: scratch of %zu bytes, %zu needed", scratch_bytes, need);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    cpc::Carver carve(scratch);
-    double *lse = carve.take<double>((size_t)b * t_max);
-    double *work = carve.take<double>((size_t)b * t_max * (2 * (size_t)max_l + 1));
-    double *logp = carve.take<double>((size_t)b);
-    int *status = carve.take<int>((size_t)b);
-    hipLaunchKernelGGL(cpc::ctc_len_kernel, dim3((unsigned)b), dim3(cpc::CH_THREADS), 0, st, logits, t_max, k, in_lengths, targets,
-                       max_l, tgt_lengths, lse, work, nll, logp, status);
-    CPC_CHECK_LAUNCH("ctc_len_kernel");
-    if (dlogits != nullptr) {
-        const unsigned chunks = (unsigned)cpc::cdiv((long)t_max * k, cpc::CTC_GRAD_PER_WG);
-        hipLaunchKernelGGL(cpc::ctc_grad_kernel, dim3(chunks, (unsigned)b), dim3(cpc::CH_THREADS), 0, st, logits, t_max, k, in_lengths,
-                           targets, max_l, tgt_lengths, lse, work, logp, status, dlogits, reduction);
-        CPC_CHECK_LAUNCH("ctc_grad_kernel");
-    }
-    hipLaunchKernelGGL(cpc::ctc_reduce_kernel, dim3(1), dim3(cpc::CH_THREADS), 0, st, nll, tgt_lengths, (long)b, reduction, loss);
-    CPC_CHECK_LAUNCH("ctc_reduce_kernel");
-    return CPC_OK;
+    return cpc::ctc_loss_run(logits, b, t_max, k, in_lengths, targets, max_l, tgt_lengths, reduction, nll, loss, dlogits, scratch,
+                             static_cast<hipStream_t>(stream));
 }
 
 static int seqnorm_len_check(const char *name, int b, int s, int h)

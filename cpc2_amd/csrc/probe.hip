@@ -7,13 +7,9 @@
 //                          symmetric, so every lane ends with the same bits.  nll = max + log(sum) - x[label]; the prediction
 //                          is the LOWEST index among equal maxima (predictions.max(1)[1]).  With a gradient wanted the row is
 //                          overwritten by (softmax - onehot) / n.
-//   probe_ctc_kernel       one workgroup per sequence.  log-softmax of every frame, then alpha (forward) and beta (backward) in
-//                          log space over the 2L + 1 extended states, in f64: the log-probabilities reach |log alpha| ~ T log K
-//                          (~480 at T = 128, K = 42), where one f32 ulp is 3e-5 -- an error the occupancy exp(alpha + beta -
-//                          log p - log y) would carry whole.  alpha + beta of every (t, s) goes to global scratch [T][2L+1];
-//                          the gradient softmax - occupancy is then summed per (t, class) over the states of that class in
-//                          ascending state order (a label that occurs several times in the target shares its class's bin).
-//   probe_reduce_kernel    the mean loss as one workgroup's fixed-order sum, and the number of correct rows (integers).
+//   cpc_probe_ctc          no kernel of its own: the CTC loss of ctc_head.hip (cpc::ctc_loss_run) with every frame of every
+//                          sequence counted and the mean reduction.
+//   probe_reduce_kernel    the mean cross-entropy as one workgroup's fixed-order sum, and the number of correct rows (integers).
 //   probe_collapse_kernel  one wave64 per row: consecutive repeats removed (ballot + popcount), zero padded.
 //   probe_scale_kernel     dlogits *= the loss's incoming gradient (a device scalar: no host read).
 // No float atomic anywhere: every result is bitwise reproducible.
@@ -27,10 +23,9 @@ namespace {
 constexpr int PR_THREADS = 256;
 constexpr int PR_ROWS = PR_THREADS / 64;     // xent / collapse rows per workgroup (one wave each)
 constexpr int PR_MAX_C = 1 << 20;
-constexpr int CTC_THREADS = 256;
-constexpr int CTC_MAX_T = 1024;
-constexpr int CTC_MAX_S = 2 * CTC_MAX_T + 1;
-constexpr int CTC_MAX_K = 1 << 16;
+constexpr int PR_CTC_MAX_B = 65535;          // the probe's own CTC limits, inside cpc_ctc_loss's
+constexpr int PR_CTC_MAX_T = 1024;
+constexpr int PR_CTC_MAX_K = 1 << 16;
 
 __device__ __forceinline__ bool first_max(float v, int i, float bv, int bi)
 {
@@ -99,10 +94,10 @@ probe_xent_kernel(float *logits, const int64_t *__restrict__ labels, long n, int
     }
 }
 
-// loss[0] = (sum_i vals[i] / (lengths ? max(lengths[i], 1) : 1)) / n, fixed order; acc[0] = (sum_i correct[i]) / n in double
+// loss[0] = (sum_i vals[i]) / n, fixed order; acc[0] = (sum_i correct[i]) / n in double
 __global__ void __launch_bounds__(PR_THREADS)
-probe_reduce_kernel(const float *__restrict__ vals, const int64_t *__restrict__ lengths, const int *__restrict__ correct, long n,
-                    float *__restrict__ loss, double *__restrict__ acc)
+probe_reduce_kernel(const float *__restrict__ vals, const int *__restrict__ correct, long n, float *__restrict__ loss,
+                    double *__restrict__ acc)
 {
     __shared__ float s_sum[PR_THREADS];
     __shared__ long s_cnt[PR_THREADS];
@@ -110,10 +105,8 @@ probe_reduce_kernel(const float *__restrict__ vals, const int64_t *__restrict__ 
     float sum = 0.0f;
     long cnt = 0;
     for (long i = tid; i < n; i += PR_THREADS) {
-        float v = vals[i];
-        if (lengths) v /= (float)max((int64_t)1, lengths[i]);
-        sum += v;
-        if (correct) cnt += correct[i];
+        sum += vals[i];
+        cnt += correct[i];
     }
     s_sum[tid] = sum;
     s_cnt[tid] = cnt;
@@ -127,7 +120,7 @@ probe_reduce_kernel(const float *__restrict__ vals, const int64_t *__restrict__ 
     }
     if (tid == 0) {
         loss[0] = s_sum[0] / (float)n;
-        if (acc) acc[0] = (double)s_cnt[0] / (double)n;
+        acc[0] = (double)s_cnt[0] / (double)n;
     }
 }
 
@@ -160,151 +153,6 @@ probe_collapse_kernel(const int64_t *__restrict__ in, int b, int t, int64_t *__r
     if (lane == 0) lengths[row] = base;
 }
 
-// ---------------------------------------------------------------- CTC
-__device__ __forceinline__ double log_add(double a, double b)
-{
-    const double m = fmax(a, b);
-    if (m == -__builtin_inf()) return m;
-    return m + log1p(exp(fmin(a, b) - m));
-}
-
-// logits [b][t][k] (blank = k - 1); targets [b][max_l], lengths [b]; work [b][t][2 max_l + 1] (f64).  nll[seq] = -log p, 0 when
-// no alignment exists (zero_infinity) and NaN for a length or label out of range.  grad (may alias logits, may be null):
-// (softmax - occupancy) / (gridDim.x * max(L, 1)), 0 for an infeasible sequence.
-__global__ void __launch_bounds__(CTC_THREADS)
-probe_ctc_kernel(const float *logits, int T, int K, const int64_t *__restrict__ targets, int max_l,
-                 const int64_t *__restrict__ lengths, double *__restrict__ work, float *__restrict__ nll, float *grad)
-{
-    __shared__ double s_lse[CTC_MAX_T];
-    __shared__ double s_a[2][CTC_MAX_S];
-    __shared__ int s_ext[CTC_MAX_S];
-    __shared__ int s_bad;
-    const int tid = threadIdx.x;
-    const int seq = blockIdx.x;
-    const int blank = K - 1;
-    const int sw = 2 * max_l + 1;
-    const float *x = logits + (long)seq * T * K;
-    double *wk = work + (long)seq * T * sw;
-    const int64_t l64 = lengths[seq];
-    const bool len_ok = l64 >= 0 && l64 <= max_l;
-    const int L = len_ok ? (int)l64 : 0;
-    const int S = 2 * L + 1;
-
-    if (tid == 0) s_bad = len_ok ? 0 : 1;
-    __syncthreads();
-    for (int s = tid; s < S; s += CTC_THREADS) {
-        int lab = blank;
-        if (s & 1) {
-            const int64_t v = targets[(long)seq * max_l + (s >> 1)];
-            if (v < 0 || v >= blank) s_bad = 1;              // (benign race: every writer stores 1)
-            lab = (v >= 0 && v < blank) ? (int)v : blank;
-        }
-        s_ext[s] = lab;
-    }
-    // log-sum-exp of every frame (one wave per frame, f64)
-    for (int f = tid >> 6; f < T; f += CTC_THREADS / 64) {
-        const int lane = tid & 63;
-        double m = -__builtin_inf(), acc = 0.0;
-        for (int j = lane; j < K; j += 64) {
-            const double v = (double)x[(long)f * K + j];
-            if (v > m) {
-                acc = (m == -__builtin_inf() ? 0.0 : acc * exp(m - v)) + 1.0;
-                m = v;
-            } else {
-                acc += exp(v - m);
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const double om = __shfl_xor(m, o), oa = __shfl_xor(acc, o);
-            const double nm = fmax(m, om);
-            if (nm != -__builtin_inf()) {
-                acc = (m == -__builtin_inf() ? 0.0 : acc * exp(m - nm)) + (om == -__builtin_inf() ? 0.0 : oa * exp(om - nm));
-                m = nm;
-            }
-        }
-        if (lane == 0) s_lse[f] = m + log(acc);
-    }
-    __syncthreads();
-    const bool bad = s_bad != 0;
-    auto lp = [&](int f, int lab) { return (double)x[(long)f * K + lab] - s_lse[f]; };
-
-    // alpha, with wk[t][s] = alpha[t][s]
-    if (!bad) {
-        for (int s = tid; s < S; s += CTC_THREADS) {
-            const double a = s == 0 ? lp(0, blank) : (s == 1 ? lp(0, s_ext[1]) : -__builtin_inf());
-            s_a[0][s] = a;
-            wk[s] = a;
-        }
-    }
-    __syncthreads();
-    for (int f = 1; f < T && !bad; ++f) {
-        const double *prev = s_a[(f - 1) & 1];
-        double *cur = s_a[f & 1];
-        for (int s = tid; s < S; s += CTC_THREADS) {
-            double a = prev[s];
-            if (s >= 1) a = log_add(a, prev[s - 1]);
-            if (s >= 2 && s_ext[s] != blank && s_ext[s] != s_ext[s - 2]) a = log_add(a, prev[s - 2]);
-            if (a != -__builtin_inf()) a += lp(f, s_ext[s]);
-            cur[s] = a;
-            wk[(long)f * sw + s] = a;
-        }
-        __syncthreads();
-    }
-    const double *last = s_a[(T - 1) & 1];
-    const double logp = bad ? 0.0 : log_add(last[S - 1], S >= 2 ? last[S - 2] : -__builtin_inf());
-    const bool feasible = !bad && logp != -__builtin_inf();
-    __syncthreads();                                     // (everyone has read `last` before beta reuses the buffers)
-
-    // beta; wk[t][s] becomes alpha + beta (each thread owns the same states as in the alpha pass)
-    if (feasible) {
-        for (int s = tid; s < S; s += CTC_THREADS) {
-            const double bt = s >= S - 2 ? lp(T - 1, s_ext[s]) : -__builtin_inf();
-            s_a[(T - 1) & 1][s] = bt;
-            wk[(long)(T - 1) * sw + s] += bt;
-        }
-        __syncthreads();
-        for (int f = T - 2; f >= 0; --f) {
-            const double *next = s_a[(f + 1) & 1];
-            double *cur = s_a[f & 1];
-            for (int s = tid; s < S; s += CTC_THREADS) {
-                double bt = next[s];
-                if (s + 1 < S) bt = log_add(bt, next[s + 1]);
-                if (s + 2 < S && s_ext[s] != blank && s_ext[s + 2] != s_ext[s]) bt = log_add(bt, next[s + 2]);
-                if (bt != -__builtin_inf()) bt += lp(f, s_ext[s]);
-                cur[s] = bt;
-                wk[(long)f * sw + s] += bt;
-            }
-            __syncthreads();
-        }
-    }
-    if (tid == 0) nll[seq] = bad ? __builtin_nanf("") : (feasible ? (float)(-logp) : 0.0f);
-    if (grad == nullptr) return;
-
-    const double scale = 1.0 / ((double)gridDim.x * (double)max(L, 1));
-    float *g = grad + (long)seq * T * K;
-    for (long idx = tid; idx < (long)T * K; idx += CTC_THREADS) {
-        const int f = (int)(idx / K), k = (int)(idx % K);
-        float out = 0.0f;
-        if (bad) {
-            out = __builtin_nanf("");
-        } else if (feasible) {
-            const double l = lp(f, k);
-            double occ = -__builtin_inf();
-            const double *row = wk + (long)f * sw;
-            if (k == blank) {
-                for (int s = 0; s < S; s += 2) occ = log_add(occ, row[s]);
-            } else {
-                for (int s = 1; s < S; s += 2)
-                    if (s_ext[s] == k) occ = log_add(occ, row[s]);
-            }
-            const double o = occ == -__builtin_inf() ? 0.0 : exp(occ - logp - l);
-            out = (float)((exp(l) - o) * scale);
-        }
-        g[idx] = out;
-    }
-}
-
 }  // namespace
 }  // namespace cpc
 
@@ -323,7 +171,7 @@ extern "C" int cpc_probe_xent(float *logits, const int64_t *labels, long n, int 
     hipLaunchKernelGGL(cpc::probe_xent_kernel, dim3((unsigned)cpc::cdiv(n, cpc::PR_ROWS)), dim3(cpc::PR_THREADS), 0, st, logits,
                        labels, n, c, want_grad, nll, correct);
     CPC_CHECK_LAUNCH("probe_xent_kernel");
-    hipLaunchKernelGGL(cpc::probe_reduce_kernel, dim3(1), dim3(cpc::PR_THREADS), 0, st, nll, nullptr, correct, n, loss, acc);
+    hipLaunchKernelGGL(cpc::probe_reduce_kernel, dim3(1), dim3(cpc::PR_THREADS), 0, st, nll, correct, n, loss, acc);
     CPC_CHECK_LAUNCH("probe_reduce_kernel");
     return CPC_OK;
 }
@@ -350,27 +198,23 @@ extern "C" int cpc_probe_head_backward(float *dlogits, long n, int c, const floa
 
 extern "C" size_t cpc_probe_ctc_scratch_bytes(int b, int t, int max_l)
 {
-    if (b < 1 || t < 1 || t > cpc::CTC_MAX_T || max_l < 0 || max_l > t) return 0;
-    return cpc::align_up(sizeof(double) * (size_t)b * t * (2 * (size_t)max_l + 1), 256);
+    if (b < 1 || b > cpc::PR_CTC_MAX_B || t < 1 || t > cpc::PR_CTC_MAX_T || max_l < 0 || max_l > t) return 0;
+    return cpc_ctc_loss_scratch_bytes(b, t, max_l);      // (the same kernels' room: these sizes lie inside its limits)
 }
 
 extern "C" int cpc_probe_ctc(const float *logits, int b, int t, int k, const int64_t *targets, int max_l, const int64_t *lengths,
                              float *nll, float *loss, float *dlogits, void *scratch, size_t scratch_bytes, cpc_stream_t stream)
 {
-    CPC_REQUIRE(b >= 1 && t >= 1 && t <= cpc::CTC_MAX_T && k >= 2 && k <= cpc::CTC_MAX_K && max_l >= 0 && max_l <= t,
-                "probe_ctc: sizes outside the supported limits (b=%d t=%d k=%d max_l=%d; need 1 <= t <= %d, 2 <= k <= %d, "
-                "0 <= max_l <= t)", b, t, k, max_l, cpc::CTC_MAX_T, cpc::CTC_MAX_K);
+    CPC_REQUIRE(b >= 1 && b <= cpc::PR_CTC_MAX_B && t >= 1 && t <= cpc::PR_CTC_MAX_T && k >= 2 && k <= cpc::PR_CTC_MAX_K &&
+                max_l >= 0 && max_l <= t,
+                "probe_ctc: sizes outside the supported limits (b=%d t=%d k=%d max_l=%d; need 1 <= b <= %d, 1 <= t <= %d, "
+                "2 <= k <= %d, 0 <= max_l <= t)", b, t, k, max_l, cpc::PR_CTC_MAX_B, cpc::PR_CTC_MAX_T, cpc::PR_CTC_MAX_K);
     CPC_REQUIRE(logits && lengths && nll && loss && (targets || max_l == 0), "probe_ctc: null buffer");
     const size_t need = cpc_probe_ctc_scratch_bytes(b, t, max_l);
     CPC_REQUIRE(scratch != nullptr && scratch_bytes >= need, "probe_ctc: scratch of %zu bytes, %zu needed", scratch_bytes, need);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(cpc::probe_ctc_kernel, dim3((unsigned)b), dim3(cpc::CTC_THREADS), 0, st, logits, t, k, targets, max_l,
-                       lengths, static_cast<double *>(scratch), nll, dlogits);
-    CPC_CHECK_LAUNCH("probe_ctc_kernel");
-    hipLaunchKernelGGL(cpc::probe_reduce_kernel, dim3(1), dim3(cpc::PR_THREADS), 0, st, nll, lengths, nullptr, (long)b, loss,
-                       nullptr);
-    CPC_CHECK_LAUNCH("probe_reduce_kernel");
-    return CPC_OK;
+    // every frame of every sequence counts (no input lengths), mean reduction
+    return cpc::ctc_loss_run(logits, b, t, k, nullptr, targets, max_l, lengths, 1, nll, loss, dlogits, scratch,
+                             static_cast<hipStream_t>(stream));
 }
 
 extern "C" int cpc_probe_collapse(const int64_t *labels, int b, int t, int64_t *out, long ldo, int64_t *lengths,

@@ -56,7 +56,9 @@ int cpc_version(void);          /* 100 x major + minor; 105 = the entry points o
                                   * 119 = cpc_mfcc_tables_doubles / cpc_mfcc_tables_host / cpc_mfcc_frame_tile / cpc_melspec_scratch_bytes /
                                   * cpc_melspec_db / cpc_mfcc_finish / cpc_deltas;
                                   * 120 = cpc_ctc_align (+ scratch query) / cpc_ctc_align_segments;
-                                  * 121 = cpc_seq_moments_scratch_bytes / cpc_seq_moments_accumulate / cpc_center_scale_rows */
+                                  * 121 = cpc_seq_moments_scratch_bytes / cpc_seq_moments_accumulate / cpc_center_scale_rows;
+                                  * 122 = cpc_probe_ctc runs on cpc_ctc_loss's kernels: cpc_probe_ctc_scratch_bytes returns
+                                  * cpc_ctc_loss_scratch_bytes of the same sizes, and cpc_probe_ctc needs b <= 65535 */
 const char *cpc_last_error(void);
 
 /* In-situ kernel timing for bench.py: when enabled, the launchers bracket each launch of the named
@@ -648,11 +650,14 @@ int cpc_deltas(const float *in, long ldi, float *out, long ldo, int cols, const 
  * cpc_probe_head_backward: dlogits [n][c] *= dloss[0] when dloss is not NULL (the loss's incoming gradient, read on the
  *   device), then db[j] = sum_i dlogits[i][j] (fixed order) when db is not NULL.  scratch: cpc_probe_xent_backward_scratch_bytes(c).
  * cpc_probe_ctc: nn.CTCLoss(blank = k - 1, reduction = 'mean', zero_infinity = True) of log_softmax(logits) for logits
- *   [b][t][k] (t <= 1024, 2 <= k <= 65536), every input length t, targets [b][max_l] (max_l <= t, padding ignored) and
- *   lengths [b]:  nll[i] = -log p_i (0 when no alignment exists), loss[0] = (sum_i nll[i] / max(L_i, 1)) / b.  dlogits (may be
- *   NULL, may alias logits) = (softmax - occupancy) / (b * max(L_i, 1)), 0 for an infeasible sequence.  A length outside
- *   [0, max_l] or a label outside [0, k - 1) gives that sequence NaN loss and gradient.  alpha and beta are computed in f64;
- *   scratch: cpc_probe_ctc_scratch_bytes(b, t, max_l) (f64 [b][t][2 max_l + 1]; 0 for sizes outside the limits).
+ *   [b][t][k] (b <= 65535, t <= 1024, 2 <= k <= 65536), every input length t, targets [b][max_l] (max_l <= t, padding ignored)
+ *   and lengths [b]:  nll[i] = -log p_i (0 when no alignment exists), loss[0] = (sum_i nll[i] / max(L_i, 1)) / b.  dlogits (may
+ *   be NULL, may alias logits) = (softmax - occupancy) / (b * max(L_i, 1)), 0 for an infeasible sequence.  A length outside
+ *   [0, max_l] or a label outside [0, k - 1) gives that sequence NaN loss and gradient.  alpha and beta are computed in f64.
+ *   It is cpc_ctc_loss (below) without input lengths and with the mean: the same kernels (since version 122; b <= 65535 because
+ *   their gradient grid has the sequence on its second axis).
+ *   scratch: cpc_probe_ctc_scratch_bytes(b, t, max_l) = cpc_ctc_loss_scratch_bytes(b, t, max_l) since version 122 (before: f64
+ *   [b][t][2 max_l + 1] alone); 0, without a message, for sizes outside the limits above.
  * cpc_probe_collapse: collapseLabelChain (cpc/criterion/seq_alignment.py) of labels [b][t]: consecutive repeats removed,
  *   out [b][ldo] (ldo >= t) zero padded, lengths [b].
  * ------------------------------------------------------------------------------------------ */
@@ -787,8 +792,8 @@ int cpc_align_score(const int *seq1, long ld1, const int *len1, const int *seq2,
  *   exactly 0.  A sequence without an alignment (an input length of 0 included) has nll 0 and gradient 0.  An input length
  *   outside [0, t_max], a target length outside [0, max_l] or a label outside [0, k - 1) gives that sequence NaN nll and NaN
  *   in all of its dlogits, as cpc_probe_ctc does.  alpha and beta are f64 in log space, fused with the log-softmax (one workgroup
- *   per sequence); the gradient is a second launch over (sequence, 1024 elements) workgroups; b <= 65535.  With every
- *   input length = t_max and the mean the results equal cpc_probe_ctc's bit for bit.
+ *   per sequence); the gradient is a second launch over (sequence, 1024 elements) workgroups; b <= 65535.  cpc_probe_ctc is
+ *   these kernels with every input length = t_max and the mean, so the two give the same bits there.
  *   Limits: 1 <= t_max <= 4096 (164 s of audio behind a stride-4 head), 2 <= k <= 65536, 0 <= max_l <= min(t_max, 1024): the
  *   2 max_l + 1 extended states of a sequence are held in LDS at 20 bytes each, 40 KB at 1024 labels.
  *   scratch: cpc_ctc_loss_scratch_bytes(b, t_max, max_l) (f64 [b][t_max] + [b][t_max][2 max_l + 1] + [b], int [b]; 0 with a message in

@@ -338,6 +338,26 @@ def test_entries_refuse_by_name_before_any_gpu_call():
     assert b"gather_utterances:" in lib.cpc_last_error()
 
 
+def test_probe_ctc_shares_the_scratch_and_the_batch_limit_of_ctc_loss():
+    """cpc_probe_ctc runs on cpc_ctc_loss's kernels (version 122): the same room inside the probe's own limits, 0 outside them,
+    and b <= 65535.  Every pointer is NULL: nothing is launched."""
+    lib = _lib.load()
+    null = ctypes.c_void_p(0)
+    assert lib.cpc_version() >= 122
+    for b, t, max_l in [(1, 1, 0), (8, 128, 128), (3, 1024, 1024)]:
+        assert lib.cpc_probe_ctc_scratch_bytes(b, t, max_l) == lib.cpc_ctc_loss_scratch_bytes(b, t, max_l) > 0
+    for b, t, max_l in [(8, 1025, 128), (8, 128, 129), (0, 128, 128)]:
+        assert lib.cpc_probe_ctc_scratch_bytes(b, t, max_l) == 0
+    assert lib.cpc_probe_ctc(null, 65536, 37, 6, null, 9, null, null, null, null, null, 0, null) == -1
+    message = lib.cpc_last_error()
+    assert message.startswith(b"probe_ctc: sizes outside the supported limits") and b"b=65536" in message, message
+    # in_lengths is optional inside the library only: the public entry still refuses a call without it.  Sizes in range and the
+    # other required pointers non-NULL (never dereferenced); without scratch the call could not reach a launch in any case
+    some = ctypes.c_void_p(256)
+    assert lib.cpc_ctc_loss(some, 6, 37, 6, null, some, 9, some, 1, some, some, null, null, 0, null) == -1
+    assert lib.cpc_last_error() == b"ctc_loss: null buffer"
+
+
 def test_ctc_loss_and_conv_head_refuse_every_size_outside_their_limits_before_any_gpu_call():
     """The limits the GPU tests run AT (4096 frames, 1024 labels, max_l = t_max, 2 classes; even kernel sizes from 2 and
     s = ks), each passed by one.  Every pointer is NULL, as above."""

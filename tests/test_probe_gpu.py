@@ -126,12 +126,12 @@ def _ctc_case(B, K, seed, T=128):
     for i in range(B):
         kind = i % 6
         if kind == 0:
-            L = int(rng.integers(15, 41))
+            L = min(int(rng.integers(15, 41)), T)
             tg = rng.integers(0, K - 1, size=L)
         elif kind == 1:
             L, tg = 0, np.zeros(0, np.int64)
         elif kind == 2:                                # repeated labels
-            L = int(rng.integers(5, 30))
+            L = min(int(rng.integers(5, 30)), T)
             tg = np.repeat(rng.integers(0, K - 1, size=(L + 1) // 2), 2)[:L]
         elif kind == 3:                                # infeasible: T equal labels need 2T - 1 frames
             L, tg = T, np.full(T, int(rng.integers(0, K - 1)))
@@ -149,7 +149,8 @@ def _ctc_case(B, K, seed, T=128):
     return logits, padded, np.array(lengths, np.int64), targets
 
 
-def _ctc_run(logits, padded, lengths, grad=True):
+def _ctc_run(logits, padded, lengths, grad=True, in_place=False):
+    """in_place: the gradient overwrites the logits, which is how the criterion calls the entry."""
     lib = _lib.load()
     B, T, K = logits.shape
     lg = torch.from_numpy(logits).to(DEV)
@@ -157,7 +158,7 @@ def _ctc_run(logits, padded, lengths, grad=True):
     ln = torch.from_numpy(lengths).to(DEV)
     nll = torch.empty(B, device=DEV)
     loss = torch.empty(1, device=DEV)
-    dl = torch.empty_like(lg) if grad else None
+    dl = (lg if in_place else torch.empty_like(lg)) if grad else None
     nb = lib.cpc_probe_ctc_scratch_bytes(B, T, padded.shape[1])
     sc = torch.empty(nb, dtype=torch.uint8, device=DEV)
     _lib.check(lib.cpc_probe_ctc(_p(lg), B, T, K, _p(tg), padded.shape[1], _p(ln), _p(nll), _p(loss), _p(dl), _p(sc), nb, _st()),
@@ -167,9 +168,13 @@ def _ctc_run(logits, padded, lengths, grad=True):
 
 # Bound: alpha and beta are f64, so the only f32 roundings are the output's cast and the f32 sum of the per-sequence losses,
 # far below 2e-5 relative (an f32 alpha would not be: DESIGN.md section 9).
-@pytest.mark.parametrize("B,K", [(1, 42), (8, 42), (64, 42), (8, 100)])
-def test_ctc_vs_fp64(B, K):
-    logits, padded, lengths, targets = _ctc_case(B, K, seed=B * 31 + K)
+# (2, 2) at T = 3: one partial chunk of the gradient kernel and one label class; (3, 64) at T = 32: T K = 2 chunks exactly.
+@pytest.mark.parametrize("B,K,T", [pytest.param(1, 42, 128, id="1-42"), pytest.param(8, 42, 128, id="8-42"),
+                                   pytest.param(64, 42, 128, id="64-42"), pytest.param(8, 100, 128, id="8-100"),
+                                   pytest.param(2, 2, 3, id="2-2-T3"), pytest.param(3, 64, 32, id="3-64-T32")])
+def test_ctc_vs_fp64(B, K, T):
+    logits, padded, lengths, targets = _ctc_case(B, K, seed=B * 31 + K, T=T)
+    assert np.all((lengths >= 0) & (lengths <= T))
     ref_loss, ref_nll, ref_grad = PO.ctc(logits.astype(np.float64), targets, lengths)
     loss, nll, grad = _ctc_run(logits, padded, lengths)
     assert abs(loss - ref_loss) <= 2e-5 * abs(ref_loss)
@@ -183,6 +188,16 @@ def test_ctc_vs_fp64(B, K):
     # bitwise reproducible
     loss2, nll2, grad2 = _ctc_run(logits, padded, lengths)
     assert loss2 == loss and np.array_equal(nll2, nll) and np.array_equal(grad2, grad)
+
+
+def test_ctc_gradient_in_place_equals_out_of_place():
+    """The criterion passes the logits' buffer as the gradient's.  The forward and the gradient are two launches: an element of
+    the gradient reads the logits at its own place only, so writing over them changes nothing."""
+    logits, padded, lengths, _ = _ctc_case(6, 6, seed=11, T=20)
+    apart = _ctc_run(logits, padded, lengths)
+    over = _ctc_run(logits, padded, lengths, in_place=True)
+    assert apart[0] == over[0] and np.array_equal(apart[1], over[1]) and np.array_equal(apart[2], over[2])
+    assert not np.array_equal(over[2], logits)
 
 
 def test_ctc_padded_width_does_not_matter():
