@@ -5,7 +5,7 @@ libcpc2_hip.so (cpc_flac_decode_f32, MD5-verified), PCM / float WAV through a sm
 
 Sample-rate conversion (`resample`, `resample_pack`) is torchaudio's sinc_interp_hann resampler on the device
 (csrc/resample.hip; the definition is in include/cpc2_hip.h), and `save_wav` is the writer `load` reads back: PCM16 quantised on
-the device, or IEEE float."""
+the device, or IEEE float.  `pitch_shift` is the direct call of the `pitch_wsola` augmentation's kernels (csrc/pitch.hip)."""
 import collections
 import ctypes
 import struct
@@ -201,6 +201,33 @@ def resample_pack(signals, orig_freq, new_freq, lowpass_filter_width=6, rolloff=
     if flat.numel() and out.numel() and max(lengths) > 0:
         _launch(flat, offsets, lengths, out, out_offsets, plan, table)
     return [out[a:a + b] for a, b in zip(out_offsets, out_lens)]
+
+
+# --------------------------------------------------------------------------- pitch shift
+def pitch_shift(x, cents, return_offsets=False):
+    """The `pitch_wsola` pitch shift (data_augmentation.PitchShiftAugment states it; csrc/pitch.hip) of [..., W] float32 device
+    rows sampled at 16 kHz: `cents` is one int for all rows or one value per row, each within +-1200; 0 returns the row's bits.
+    The result has x's shape.  return_offsets: also the segment starts the search chose, [rows, J] int32 on the device.  This is
+    this package's definition of a pitch shift, not sox's; nothing is drawn here."""
+    from . import data_augmentation as da
+    _lib.require_gpu(x)
+    x = _lib.f32c(x)
+    window = x.shape[-1]
+    rows = x.numel() // window if window else 0
+    per_row = np.asarray(cents.cpu() if isinstance(cents, torch.Tensor) else cents)
+    if per_row.dtype.kind not in "iu":
+        raise TypeError("pitch_shift: cents are whole numbers (an int, or one per row)")
+    if per_row.ndim == 0:
+        per_row = np.full(rows, int(per_row), dtype=np.int64)
+    if per_row.size != rows:
+        raise ValueError(f"pitch_shift: {per_row.size} values of cents for {rows} rows")
+    out = torch.empty_like(x)
+    if rows == 0:
+        return (out, torch.empty(0, 1, dtype=torch.int32, device=x.device)) if return_offsets else out
+    tables = da.pitch_tables(per_row, window)
+    dev = {k: torch.from_numpy(tables[k]).to(x.device) for k in ("cents", "ratio", "cutoff", "nominal")}
+    q = da._pitch_launch(x.view(rows, window), dev, 0, rows, tables["cents_bound"], window, out.view(rows, window), "pitch_shift")
+    return (out, q) if return_offsets else out
 
 
 def to_pcm16(waveform):

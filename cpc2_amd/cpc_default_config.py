@@ -2,13 +2,14 @@
 
 Same flags, types, choices and defaults as the reference's cpc/cpc_default_config.py:13-162 -- all of them, the
 augmentation group included: cpc2_amd.train builds additive / natural_reverb / time_dropout (data_augmentation.py) and
+pitch_wsola (a choice of --augment_type the reference does not have: a pitch shift by this package's own definition), and
 refuses the sox-based types with a message (train.py, refuseUnsupported), and checkpoint_args.json carries the same keys as a reference run, so that either side can resume the other's run."""
 import argparse
 
 NAMING_CONVENTIONS = ['full_seedlings', 'no_speaker', 'id_spkr_onset_offset', 'spkr-id', 'spkr-id-nb',
                       'id_spkr_onset_offset_spkr_onset_offset', 'spkr_id_nb']
 AUGMENT_TYPES = ['none', 'bandreject', 'pitch', 'pitch_deropout', 'pitch_quick', 'additive', 'artificial_reverb',
-                 'time_dropout', 'artificial_reverb_dropout', 'natural_reverb']
+                 'time_dropout', 'artificial_reverb_dropout', 'natural_reverb', 'pitch_wsola']
 
 
 def get_default_cpc_config():
@@ -74,8 +75,10 @@ def set_default_cpc_config(parser):
     g.add_argument('--no_speaker', action='store_true', help='Collapse every speaker into one.')
     a = parser.add_argument_group('Data augmentation configuration',
                                   description="Device-side augmentation of the past / future half (cpc2_amd/data_augmentation.py): "
-                                  "additive, natural_reverb, time_dropout and none are built, alone or combined; the sox-based "
-                                  "types are parsed for checkpoint compatibility and refused by name.")
+                                  "additive, natural_reverb, time_dropout, pitch_wsola and none are built, alone or combined; the "
+                                  "sox-based types are parsed for checkpoint compatibility and refused by name.  pitch_wsola "
+                                  "shifts the pitch by up to --shift_max cents (a WSOLA stretch and a sinc resampling: this "
+                                  "package's definition, not sox's).")
     a.add_argument('--noise_extension', type=str, default='.wav')
     a.add_argument('--augment_future', action='store_true')
     a.add_argument('--augment_past', action='store_true')
@@ -87,7 +90,8 @@ def set_default_cpc_config(parser):
     a.add_argument('--past_equal_future', action='store_true')
     a.add_argument('--pathImpulseResponses', type=str, default=None)
     a.add_argument('--impulse_response_prob', type=float, default=1.0)
-    a.add_argument('--shift_max', type=float, default=300)
+    a.add_argument('--shift_max', type=float, default=300,
+                   help='pitch_wsola: cents drawn from [-shift_max, shift_max), a whole number from 1 to 1200.')
     a.add_argument('--min_snr_in_db', type=float, default=5.0)
     a.add_argument('--max_snr_in_db', type=float, default=20.0)
     a.add_argument('--ir_sample_rate', type=int, default=16000)

@@ -1,9 +1,13 @@
 """Audio augmentation on device batches: the reference's cpc/data_augmentation.py for the types whose arithmetic is fixed.
 
 Built: `additive` (AdditiveNoiseAugment :157-228), `natural_reverb` (NaturalReverb :278-318), `time_dropout`
-(TimeDropoutAugment :268-275), their combinations (CombinedTransforms :331-344) and the reverberated noise
-(`augmentation_factory(..., applied_on_noise=True)`).  The sox types (UNBUILT_TYPES) are refused by name: neither sox nor
-WavAugment is available, and their filters cannot be pinned to anything.
+(TimeDropoutAugment :268-275), `pitch_wsola` (PitchShiftAugment: a pitch shift by this package's own definition, below), their
+combinations (CombinedTransforms :331-344) and the reverberated noise (`augmentation_factory(..., applied_on_noise=True)`).
+The sox types (UNBUILT_TYPES: pitch, pitch_quick, pitch_dropout, pitch_deropout, bandreject, artificial_reverb, ...) are refused
+by name: neither sox nor WavAugment is available, and their filters cannot be pinned to anything.  `pitch_wsola` is NOT one of
+them under another name: it draws what the reference's PitchAugment draws and shifts the pitch, by an algorithm written down in
+PitchShiftAugment's docstring; its agreement with sox's `pitch` effect is unmeasured.  `--augment_type pitch_wsola time_dropout`
+stands in for the reference's `pitch_dropout`.
 
 The reference augments one window at a time on the CPU, inside DataLoader workers.  Here a pack of audio lives in HBM as one
 flat vector and so do the noise pack and the impulse responses; a batch's augmentation is a few kernels
@@ -26,6 +30,7 @@ Deviations from the reference, all deliberate:
   * sequence-wise NaturalReverb: the probability test is drawn from numpy and the file from `random` (the reference's library
     draws both from torch); a file is drawn only for a window the test lets through;
   * TimeDropoutAugment follows the definition in its docstring (the library the reference calls is not available);
+  * PitchShiftAugment likewise: a WSOLA stretch and a windowed-sinc resampling instead of sox's pitch / rate chain, no dither;
   * `--augment_type none` gives None (the reference's factory raises on the one-element list ['none']).
 """
 import collections
@@ -38,7 +43,7 @@ import torch
 from . import _lib
 from ._lib import check, ptr, stream_ptr
 
-BUILT_TYPES = ('additive', 'natural_reverb', 'time_dropout')
+BUILT_TYPES = ('additive', 'natural_reverb', 'time_dropout', 'pitch_wsola')
 UNBUILT_TYPES = ('bandreject', 'pitch', 'pitch_quick', 'pitch_dropout', 'pitch_deropout', 'artificial_reverb',
                  'artificial_reverb_dropout', 'random_noise')
 
@@ -373,6 +378,119 @@ class TimeDropoutAugment(_Transform):
         return src
 
 
+# --------------------------------------------------------------------------- pitch shift
+PITCH_SEGMENT, PITCH_OVERLAP, PITCH_SEARCH = 1312, 192, 234          # S, O, R in samples at 16 kHz: 82 ms, 12 ms, 14.68 ms
+PITCH_HOP = PITCH_SEGMENT - PITCH_OVERLAP                            # Ho, the output hop
+PITCH_SINC_WIDTH, PITCH_ROLLOFF = 6, 0.99                            # L and the low-pass cutoff factor
+PITCH_TAP_GUARD = 16                                                 # stretched samples allowed for beyond ceil(W r): > L / c - r
+PITCH_MAX_CENTS = 1200
+
+
+def pitch_segments(window, ratio):
+    """J(W, r): segments of Ho stretched samples that cover every tap of every output, ceil((ceil(W r) + 16) / Ho)."""
+    reach = int(np.ceil(window * ratio)) + PITCH_TAP_GUARD
+    return -(-reach // PITCH_HOP)
+
+
+def pitch_tables(cents, window, segments=None):
+    """The host tables of a batch of shifts (PitchShiftAugment's docstring): cents [n] i32, ratio [n] f64 (C's pow(2, cents / 1200)
+    in double), cutoff [n] f64, nominal [n, J] i32 with nominal[i, j] = floor(j Ho / ratio[i] + 0.5) and J the largest segment
+    count of the batch (or `segments` when that is larger)."""
+    cents = np.asarray(cents, dtype=np.int64).reshape(-1)
+    if cents.size and int(np.abs(cents).max()) > PITCH_MAX_CENTS:
+        raise ValueError(f"a pitch shift of {int(np.abs(cents).max())} cents: at most {PITCH_MAX_CENTS} (an octave) either way")
+    ratio = np.array([2.0 ** (int(c) / 1200.0) for c in cents], dtype=np.float64)
+    cutoff = PITCH_ROLLOFF * np.minimum(1.0, 1.0 / ratio)
+    reach = np.ceil(window * ratio).astype(np.int64) + PITCH_TAP_GUARD                  # pitch_segments, all rows at once
+    count = max([int((-(-reach // PITCH_HOP)).max()) if cents.size else 1, 1, int(segments or 1)])
+    nominal = np.floor(np.arange(count, dtype=np.float64)[None, :] * PITCH_HOP / ratio[:, None] + 0.5)
+    if nominal.size and nominal.max() + PITCH_SEARCH + PITCH_SEGMENT >= 2 ** 31:
+        raise ValueError(f"windows of {window} samples: the segment starts of a pitch shift no longer fit 32 bits")
+    return {"cents": cents.astype(np.int32), "ratio": ratio, "cutoff": cutoff, "nominal": nominal.astype(np.int32),
+            "cents_bound": int(np.abs(cents).max()) if cents.size else 0}
+
+
+def _pitch_launch(src, dev_tables, lo, hi, bound, window, out, what="augment_pitch"):
+    """cpc_augment_pitch on rows [lo, hi) of device tables; returns the chosen segment starts [b, J] (int32)."""
+    dev = _device_of(src)
+    nominal = dev_tables["nominal"]
+    q = torch.empty(hi - lo, nominal.shape[1], dtype=torch.int32, device=dev)
+    p, total, off = _operand(src)
+    check(_lib.load().cpc_augment_pitch(p, total, off, ptr(dev_tables["ratio"][lo:hi]), ptr(dev_tables["cutoff"][lo:hi]),
+                                        ptr(dev_tables["cents"][lo:hi]), int(bound), ptr(nominal[lo:hi]), nominal.shape[1],
+                                        ptr(out), ptr(q), hi - lo, window, stream_ptr(dev)), what)
+    return q
+
+
+class PitchShiftAugment(_Transform):
+    """`pitch_wsola`: a pitch shift of every window by a whole number of cents, drawn as the reference's PitchAugment
+    (data_augmentation.py:64-100) draws it -- ONE np.random.randint(-shift_max, shift_max) per window from numpy's global
+    generator; the output has the input's length and is not peak-normalised.  The reference hands the number to a sox effect chain
+    (pitch + rate + dither) that is not available; what happens to the window here is THIS PACKAGE'S definition, written down
+    below.  It is not sox's algorithm, there is no dither, and its agreement with sox is unmeasured.  The constants are in samples
+    and mean what they say at 16 kHz only; the three times are this package's choice (what sox `tempo`'s defaults are recalled to be,
+    which could not be checked).
+
+      S = 1312 (segment, 82 ms)   O = 192 (overlap, 12 ms)   R = 234 (search candidates, 14.68 ms)   Ho = S - O = 1120
+      L = 6 (sinc half-width in zero crossings)   rolloff = 0.99
+
+    The window x[0 .. W) is f32 and reads as zero outside [0, W), whatever lies beside it in a pack.  r = 2 ** (cents / 1200) in
+    f64 on the host.  cents == 0 returns the window bit for bit.  Otherwise:
+
+    Stage 1, a time stretch by r (WSOLA), stated as a function s(m), m >= 0.  Segment j = m // Ho, k = m - j Ho.
+      q_0 = 0.  For j >= 1 the nominal start is p_j = floor(j Ho / r + 0.5) (f64, a host table), the template is
+      t[k] = x[q_{j-1} + Ho + k], k < O (raw input: the tail of the previous segment), the candidates are p_j - R // 2 + d,
+      d = 0 .. R - 1, and a candidate's cost is D(d) = sum_{k < O} (x[cand + k] - t[k]) ** 2, in f64: both values converted, the
+      difference, its square, added with k ascending, nothing contracted.  q_j is the candidate of the smallest D, the lowest d on
+      a tie.
+      s(m) = x[q_j + k] for k >= O or j == 0; otherwise a + (k / O) (b - a) with a = x[q_{j-1} + Ho + k], b = x[q_j + k].
+    Stage 2, resampling by r.  y[n] = sum_{m >= 0} h(n r - m) s(m) for n in [0, W), with c = 0.99 min(1, 1 / r) and
+      h(t) = c sinc(c t) cos(pi c t / (2 L)) ** 2 for |c t| < L, else 0 (sinc(u) = sin(pi u) / (pi u)).
+
+    On the device (csrc/pitch.hip) the q_j are the statement's, exactly; the weights are evaluated in f64 and rounded once to f32,
+    the cross-fade likewise, and the sum is one f32 fmaf chain with m ascending, so a window's bits depend on nothing else in the
+    batch or the pack.  J = ceil((ceil(W r) + 16) / Ho) segments cover every tap.
+
+    Entry: cents.  Plan: cents [n] i32, ratio [n] f64, cutoff [n] f64, nominal [n, J] i32, window, cents_bound.  Out of place; the
+    starts the last `apply` chose stay in `last_offsets` ([b, J] int32 on the device)."""
+
+    def __init__(self, shift_max=300):
+        if shift_max != int(shift_max):
+            raise ValueError(f"--shift_max {shift_max}: pitch_wsola shifts by a whole number of cents")
+        if shift_max < 1:
+            raise ValueError(f"--shift_max {shift_max}: pitch_wsola draws from [-shift_max, shift_max) and needs at least 1 cent")
+        if shift_max > PITCH_MAX_CENTS:
+            raise ValueError(f"--shift_max {shift_max}: pitch_wsola shifts by at most {PITCH_MAX_CENTS} cents (an octave) either way")
+        self.shift_max = int(shift_max)
+        self.window = None
+        self.last_offsets = None
+
+    def draw_one(self, window):
+        self.window = window
+        return int(np.random.randint(-self.shift_max, self.shift_max))
+
+    def seal(self, entries, device, window=None):
+        window = window if window is not None else self.window
+        if window is None:
+            raise ValueError("pitch_wsola: a plan needs the window length (seal(..., window=W), or draw_one(W) before it)")
+        plan = {"kind": "pitch_wsola", "n": len(entries), "window": int(window)}
+        plan.update(pitch_tables(np.array(entries, dtype=np.int64).reshape(-1), window))
+        plan["_dev"] = {k: _upload(plan[k], device) for k in ("cents", "ratio", "cutoff", "nominal")}
+        return plan
+
+    def apply(self, plan, lo, hi, src, dst=None, window=None):
+        _check_src(src)
+        window = _window(src, dst, window if window is not None else plan["window"])
+        if window != plan["window"]:
+            raise ValueError(f"pitch_wsola: the plan was sealed for windows of {plan['window']} samples, not {window}")
+        b = hi - lo
+        if not isinstance(src, FlatWindows) and dst is not None and src.data_ptr() == dst.data_ptr():
+            src = src.clone()                                          # (out of place: every output reads many input samples)
+        out = dst if dst is not None else torch.empty(b, window, dtype=torch.float32, device=_device_of(src))
+        self.last_offsets = _pitch_launch(src, plan["_dev"], lo, hi, plan["cents_bound"], window, out)
+        return out
+
+
 # --------------------------------------------------------------------------- combinations
 class CombinedTransforms(_Transform):
     """data_augmentation.py:331-344: the transforms of `augment_cfgs`, applied in the order given ('none' entries skipped).
@@ -426,6 +544,8 @@ def get_augment(augment_type, **kwargs):
     if augment_type == 'natural_reverb':
         return NaturalReverb(ir_paths=kwargs['pathImpulseResponses'], p=kwargs['impulse_response_prob'],
                              batchSize=kwargs['batchSize'], sr=kwargs['ir_sample_rate'], batch_wise=kwargs['ir_batch_wise'])
+    if augment_type == 'pitch_wsola':
+        return PitchShiftAugment(kwargs['shift_max'])
     if augment_type in UNBUILT_TYPES:
         raise NotImplementedError(unbuilt_message(augment_type))
     raise RuntimeError(f'Unknown augment_type = {augment_type}')
@@ -456,6 +576,7 @@ def augmentation_factory(args, noise_dataset=None, applied_on_noise=False):
     batchSize = args.nGPU * args.batchSizeGPU
     additive_noise_sampling = "temporalsamespeaker" if args.temporal_additive_noise else "uniform"
     aug_args = {"t_ms": args.t_ms,
+                "shift_max": args.shift_max,
                 "noise_dataset": noise_dataset,
                 "additive_noise_snr_min": args.min_snr_in_db,
                 "additive_noise_snr_max": args.max_snr_in_db,

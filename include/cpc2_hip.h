@@ -58,7 +58,8 @@ int cpc_version(void);          /* 100 x major + minor; 105 = the entry points o
                                   * 120 = cpc_ctc_align (+ scratch query) / cpc_ctc_align_segments;
                                   * 121 = cpc_seq_moments_scratch_bytes / cpc_seq_moments_accumulate / cpc_center_scale_rows;
                                   * 122 = cpc_probe_ctc runs on cpc_ctc_loss's kernels: cpc_probe_ctc_scratch_bytes returns
-                                  * cpc_ctc_loss_scratch_bytes of the same sizes, and cpc_probe_ctc needs b <= 65535 */
+                                  * cpc_ctc_loss_scratch_bytes of the same sizes, and cpc_probe_ctc needs b <= 65535;
+                                  * 123 = cpc_augment_pitch */
 const char *cpc_last_error(void);
 
 /* In-situ kernel timing for bench.py: when enabled, the launchers bracket each launch of the named
@@ -696,6 +697,40 @@ size_t cpc_augment_fir_scratch_bytes(int batch, int window);
 int cpc_augment_fir(const float *x, const float *ir, long ir_total, const long *ir_off, const int *ir_len, float *out,
                     void *scratch, size_t scratch_bytes, int batch, int window, cpc_stream_t stream);
 int cpc_augment_time_dropout(float *x, const long *start, const long *length, int batch, int window, cpc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Pitch shift of windows by a whole number of cents (the `pitch_wsola` augmentation; cpc2_amd/data_augmentation.py
+ * PitchShiftAugment, csrc/pitch.hip).  version 123.  The reference's PitchAugment is a sox effect chain (pitch + rate + dither)
+ * that cannot be pinned to anything here; this is THIS LIBRARY'S definition of a pitch shift.  It is not sox's algorithm, it adds no
+ * dither, and its agreement with sox is unmeasured.  The constants are in samples and mean what they say at 16 kHz only; the three
+ * times are this library's choice.
+ *   S = 1312 (segment, 82 ms)  O = 192 (overlap, 12 ms)  R = 234 (search candidates, 14.68 ms)  Ho = S - O = 1120 (output hop)
+ *   L = 6 (sinc half-width in zero crossings)  rolloff 0.99
+ * Window i is x[0 .. W) of the source (f32), read as ZERO outside [0, W) -- whatever lies beside it in the vector -- and outside
+ * the vector.  r = ratio[i] (the caller's 2 ** (cents[i] / 1200), in double), c = cutoff[i] (0.99 min(1, 1 / r)).
+ * cents[i] == 0: out[i] = the window, bit for bit.  Otherwise:
+ *   Stage 1, a time stretch by r (WSOLA) stated as a function s(m), m >= 0; segment j = m / Ho, k = m - j Ho.
+ *     q_0 = 0.  For j >= 1: p_j = nominal[i][j] (the caller's floor(j Ho / r + 0.5), in double -- no division on the device); the
+ *     template is t[k] = x[q_{j-1} + Ho + k], k < O (raw input, the tail of the previous segment); the candidates are
+ *     p_j - R / 2 + d, d = 0 .. R - 1; the cost D(d) = sum_{k < O} (x[cand + k] - t[k])^2 is taken in double: both values
+ *     converted, subtracted, squared, added with k ascending, nothing contracted.  q_j = the candidate of the smallest D, the
+ *     lowest d on a tie.
+ *     s(m) = x[q_j + k] for k >= O or j == 0, else a + (k / O) (b - a) with a = x[q_{j-1} + Ho + k], b = x[q_j + k].
+ *   Stage 2, resampling by r: out[i][n] = sum_{m >= 0} h(n r - m) s(m), n in [0, W), h(t) = c sinc(c t) cos(pi c t / (2 L))^2 for
+ *     |c t| < L and 0 elsewhere (sinc(u) = sin(pi u) / (pi u)).
+ * q[i][j] receives q_j for every j < segments and equals the statement's, exactly.  The weights are evaluated in double and
+ * rounded once to f32 (sin and cos at an output's first tap, turned tap by tap in double from there; the tap nearest the centre
+ * evaluates its sine directly), the cross-fade is taken in double and rounded once, and the sum is ONE f32 fmaf chain with m
+ * ascending: an output's bits do not depend on the launch geometry, on the other windows or on what surrounds the window.
+ * `segments` (the row length of nominal and q) must cover every tap: ceil((ceil(W r) + 16) / Ho) for the largest r of the batch;
+ * segments nobody reads cost time only.  cents_bound is the HOST's bound on |cents[i]| (the device array is not read back).
+ * Refused with CPC_ERR_INVALID, nothing launched and nothing written: window <= 0, segments <= 0, cents_bound > 1200 (or < 0),
+ * batch < 0 or > 65535, a null pointer with batch > 0, out == src.  batch == 0 is a no-op.  The source is given as the other
+ * augment entries take it: (vector, total, offsets), or a [batch][window] buffer with offsets == NULL.
+ * ------------------------------------------------------------------------------------------ */
+int cpc_augment_pitch(const float *src, long src_total, const long *src_off, const double *ratio, const double *cutoff,
+                      const int *cents, int cents_bound, const int *nominal, int segments, float *out, int *q, int batch,
+                      int window, cpc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Sample-rate conversion (torchaudio's sinc_interp_hann resampler, the transform of the reference's
