@@ -45,6 +45,45 @@ def dtw(d):
     return cost[n - 1, m - 1] / length, length
 
 
+def dtw_margin(d):
+    """(cost / path length, path length, margin): dtw's recursion and backtrack, plus how close the backtrack came to
+    another path: the smallest (second smallest - smallest) / max(|second smallest|, 1e-30) among up, left and diag over
+    the steps it took; inf when the path never leaves the first row or column.  A pair whose margin is above the relative
+    error of an f32 running cost has the same path in f32.  (On lists of Python floats: the same fp64 operations as dtw,
+    without numpy's per-element overhead.)"""
+    d = np.asarray(d, dtype=np.float64)
+    n, m = d.shape
+    rows = d.tolist()
+    cost = []
+    for i in range(n):
+        di = rows[i]
+        ci = [0.0] * m
+        if i == 0:
+            prev = 0.0
+            for j in range(m):
+                prev = ci[j] = di[j] + prev
+        else:
+            up = cost[i - 1]
+            ci[0] = di[0] + up[0]
+            for j in range(1, m):
+                ci[j] = di[j] + min(up[j], up[j - 1], ci[j - 1])
+        cost.append(ci)
+    i, j, length, margin = n - 1, m - 1, 1, np.inf
+    while i > 0 and j > 0:
+        up, left, diag = cost[i - 1][j], cost[i][j - 1], cost[i - 1][j - 1]
+        lo, mid, _ = sorted((up, left, diag))
+        margin = min(margin, (mid - lo) / max(abs(mid), 1e-30))
+        if diag <= left and diag <= up:
+            i, j = i - 1, j - 1
+        elif left <= up:
+            j -= 1
+        else:
+            i -= 1
+        length += 1
+    length += i + j
+    return cost[n - 1][m - 1] / length, length, margin
+
+
 def dtw_items(x, y, distance):
     return dtw(frame_distances(x, y, distance))
 

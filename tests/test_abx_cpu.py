@@ -164,6 +164,32 @@ def test_oracle_matches_reference_dtw_cases(g19):
                 assert abs(v - ref[i, j]) < tol * max(1.0, abs(v)), (k, i, j, v, ref[i, j])
 
 
+def test_dtw_margin_agrees_with_dtw_and_sees_ties(g19):
+    n_paths = 0
+    for k in range(int(g19["dtw_n"])):
+        code, _sym = (int(v) for v in g19[f"dtw{k}_cfg"])
+        a, sa, b, sb = (g19[f"dtw{k}_{n}"] for n in ("a", "sa", "b", "sb"))
+        for i in range(a.shape[0]):
+            for j in range(b.shape[0]):
+                d = O.frame_distances(a[i, :sa[i]], b[j, :sb[j]], "cosine" if code == 0 else "euclidian")
+                v, n, margin = O.dtw_margin(d)
+                assert (v, n) == O.dtw(d)
+                assert margin >= 0 and (margin < np.inf) == (min(d.shape) > 1)
+                n_paths += 1
+    assert n_paths > 10
+    # hand-made: up = left = 1 behind the last cell, diag = 0: margin (1 - 0) / 1 there and nowhere else
+    assert O.dtw_margin(np.array([[0.0, 1.0], [1.0, 0.0]])) == (0.0, 2, 1.0)
+    # the tie: up = left = diag = 1 behind the last cell; diag wins, as in dtw
+    tie = np.array([[1.0, 0.0], [0.0, 5.0]])
+    assert O.dtw_margin(tie) == (3.0, 2, 0.0) and O.dtw(tie) == (3.0, 2)
+    # only the steps taken count: cost = [[1, 2, 4], [2, 1, 2]]; the path (1,2) (1,1) (0,0) sees (up 4, left 1, diag 2),
+    # then (up 2, left 2, diag 1): margins 1/2 and 1/2, and the tie between up and left at (1,1) is not the smallest two
+    off = np.array([[1.0, 1.0, 2.0], [1.0, 0.0, 1.0]])
+    assert O.dtw_margin(off) == (2.0 / 3.0, 3, 0.5)
+    # one row, one column: no step to choose
+    assert O.dtw_margin(np.ones((1, 4))) == (1.0, 4, np.inf) and O.dtw_margin(np.ones((3, 1))) == (1.0, 3, np.inf)
+
+
 def test_oracle_known_answers(g19):
     X, Xs, Y, Ys = g19["known_X"], g19["known_X_size"], g19["known_Y"], g19["known_Y_size"]
     for i in range(3):
