@@ -158,6 +158,9 @@ SIGNATURES = {
     "cpc_conv_head_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr] + [c_int] * 5 + [c_ptr, c_size_t, c_ptr]),
     "cpc_conv_head_backward_data": (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr]),
     "cpc_gather_utterances": (c_int, [c_ptr, c_long, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_long, c_ptr]),
+    "cpc_seg_lds_entries": (c_int, []),
+    "cpc_seg_dissimilarity": (c_int, [c_ptr, c_long, c_long, c_int, c_ptr, c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr]),
+    "cpc_seg_boundaries": (c_int, [c_ptr, c_long, c_ptr, c_ptr, c_int, c_ptr, c_int, c_ptr, c_long, c_ptr, c_ptr, c_ptr, c_int] + [c_ptr] * 7),
 }
 
 _lib = None

@@ -59,7 +59,8 @@ int cpc_version(void);          /* 100 x major + minor; 105 = the entry points o
                                   * 121 = cpc_seq_moments_scratch_bytes / cpc_seq_moments_accumulate / cpc_center_scale_rows;
                                   * 122 = cpc_probe_ctc runs on cpc_ctc_loss's kernels: cpc_probe_ctc_scratch_bytes returns
                                   * cpc_ctc_loss_scratch_bytes of the same sizes, and cpc_probe_ctc needs b <= 65535;
-                                  * 123 = cpc_augment_pitch */
+                                  * 123 = cpc_augment_pitch;
+                                  * 124 = cpc_seg_dissimilarity / cpc_seg_boundaries / cpc_seg_lds_entries */
 const char *cpc_last_error(void);
 
 /* In-situ kernel timing for bench.py: when enabled, the launchers bracket each launch of the named
@@ -914,6 +915,51 @@ int cpc_ctc_align(const float *logits, int b, int t_max, int k, const int64_t *i
 int cpc_ctc_align_segments(const float *logits, int b, int t_max, int k, const int64_t *targets, int max_l, const int64_t *tgt_lengths,
                            const int *path, const int *status, const double *lse, int *first, int *last, float *conf,
                            cpc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Unsupervised phone segmentation and its counts (csrc/segment.hip; cpc2_amd/segmentation.py).  version 124.
+ * Every pointer is a DEVICE pointer.  The reference has no such tool: the definition below is the specification (the recipe of
+ * Kreuk et al. 2020 with the R-value of Rasanen et al. 2009; peaks and prominences are those of scipy.signal.find_peaks /
+ * peak_prominences with wlen = None).
+ *
+ * Utterance i has L = lengths[i] frames (int32) of `dim` float32 columns: the rows offsets[i] .. offsets[i] + L - 1 (int64) of
+ * x [total_rows][ld], ld >= dim -- the layout of a packed feature buffer.  d, peak_pos and peak_prom are arrays of total_rows entries
+ * addressed by the same offsets.
+ * cpc_seg_dissimilarity: d[offsets[i] + t] = 1 - dot(x_t, x_t+1) / sqrt(|x_t|^2 |x_t+1|^2) for t < L - 1, and 1 when the product of
+ *   the squared norms is 0.  The three sums are f64 sums of exact products: lane j of a wave adds the columns j, j + 64, ... in
+ *   order and the 64 partial sums meet in a fixed butterfly; then ONE product, square root, division and subtraction, all f64.
+ *   d[t] is a function of the two rows alone and symmetric in them: equal pairs of rows give equal bits wherever they stand.
+ *   Slot offsets[i] + L - 1 and slots of no utterance are not written.
+ *   status [n_utt]: 0; 2 when the utterance holds a non-finite value (the pairs of that row are NaN, every other pair keeps its
+ *   value) or when its rows leave the buffer (length outside [0, max_len], offset < 0, offset + L > total_rows: nothing of it is
+ *   read or written).  Other utterances are unaffected.  max_len: no length exceeds it (it sizes the grid), at most 2^20.
+ * cpc_seg_boundaries: for each utterance, on the n = max(L - 1, 0) entries of d at its offset:
+ *   peaks    index i in [1, n - 2] starts a peak when d[i-1] < d[i] and the run of entries equal to d[i] ends before n with a
+ *            smaller entry behind it; the peak's position is (first + last) / 2 of the run (integer division).
+ *   prom     of a peak at q: walk left from q while d[i] <= d[q] keeping the minimum, the same to the right;
+ *            prom = d[q] - max(left minimum, right minimum): one subtraction of two stored values.
+ *   n_peaks [n_utt]; peak_pos / peak_prom: the peaks in increasing order in the first n_peaks slots at the utterance's offset (the
+ *            other slots are not written); range [n_utt] = max d - min d (0 when n = 0).
+ *   counts [n_utt][k][4] (int32) for threshold thresholds[j] (f64, 1 <= k <= 64): a peak is kept when prom >= thresholds[j] * range
+ *            (ONE product; the file is built with -ffp-contract=off) and its boundary frame h = q + 1 is < hyp_limit[i] (NULL: L).
+ *            [0] n_hyp = the kept boundaries; [1] hits = the one-to-one matching by two pointers over the two sorted lists (a pair
+ *            within tol is a hit and advances both, otherwise the smaller frame advances); [2] hyp_near = kept boundaries with a
+ *            reference within tol; [3] ref_near = references with a kept boundary within tol.  The references of utterance i are
+ *            ref[ref_offsets[i] .. + ref_counts[i]) (int32 frames in strictly increasing order, ref holds total_ref of them).
+ *            ref == NULL: no scoring, [1] .. [3] are 0.
+ *   status [n_utt]: 0; 2 when d holds a non-finite value there or an argument of the utterance is invalid (length outside
+ *            [0, 2^20], rows or references that leave their buffers): n_peaks 0, range NaN, counts 0, no peak slot written.
+ *   Up to cpc_seg_lds_entries() entries of d are staged in LDS; a longer utterance is read in place.  No workspace is needed.
+ * Limits: dim >= 1, ld >= dim, 1 <= n_utt <= 2^20, 0 <= tol <= 2^30; anything else is CPC_ERR_INVALID with a message naming the
+ *   entry point, before any launch.  No float atomic: two launches give the same bytes.
+ * ------------------------------------------------------------------------------------------ */
+int cpc_seg_lds_entries(void);
+int cpc_seg_dissimilarity(const float *x, long total_rows, long ld, int dim, const int64_t *offsets, const int *lengths, int n_utt,
+                          int max_len, double *d, int *status, cpc_stream_t stream);
+int cpc_seg_boundaries(const double *d, long total_rows, const int64_t *offsets, const int *lengths, int n_utt,
+                       const double *thresholds, int k, const int *ref /* may be NULL */, long total_ref, const int64_t *ref_offsets,
+                       const int *ref_counts, const int *hyp_limit /* may be NULL */, int tol, int *n_peaks, int *peak_pos,
+                       double *peak_prom, double *range, int *counts, int *status, cpc_stream_t stream);
 
 #ifdef __cplusplus
 }
