@@ -136,6 +136,8 @@ SIGNATURES = {
     "cpc_augment_fir": (c_int, [c_ptr, c_ptr, c_long, c_ptr, c_ptr, c_ptr, c_ptr, c_size_t, c_int, c_int, c_ptr]),
     "cpc_augment_time_dropout": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_int, c_ptr]),
     "cpc_augment_pitch": (c_int, [c_ptr, c_long, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_int, c_ptr, c_ptr, c_int, c_int, c_ptr]),
+    "cpc_augment_freeverb": (c_int, [c_ptr, c_long, c_ptr, c_ptr, c_int, ctypes.POINTER(c_int), ctypes.c_float, ctypes.c_float,
+                             ctypes.c_float, c_ptr, c_int, c_int, c_ptr]),
     "cpc_resample_plan": (c_int, [c_int, c_int, c_int, ctypes.c_double] + [ctypes.POINTER(c_int)] * 4),
     "cpc_resample_table_host": (c_int, [c_int, c_int, c_int, ctypes.c_double, c_ptr, c_long]),
     "cpc_resample": (c_int, [c_ptr, c_long, c_ptr, c_ptr, c_int, c_long, c_ptr, c_int, c_int, c_int, c_ptr, c_long, c_ptr, c_ptr]),

@@ -5,7 +5,8 @@ libcpc2_hip.so (cpc_flac_decode_f32, MD5-verified), PCM / float WAV through a sm
 
 Sample-rate conversion (`resample`, `resample_pack`) is torchaudio's sinc_interp_hann resampler on the device
 (csrc/resample.hip; the definition is in include/cpc2_hip.h), and `save_wav` is the writer `load` reads back: PCM16 quantised on
-the device, or IEEE float.  `pitch_shift` is the direct call of the `pitch_wsola` augmentation's kernels (csrc/pitch.hip)."""
+the device, or IEEE float.  `pitch_shift` is the direct call of the `pitch_wsola` augmentation's kernels (csrc/pitch.hip), `freeverb`
+that of the `freeverb` augmentation's kernel (csrc/freeverb.hip)."""
 import collections
 import ctypes
 import struct
@@ -228,6 +229,32 @@ def pitch_shift(x, cents, return_offsets=False):
     dev = {k: torch.from_numpy(tables[k]).to(x.device) for k in ("cents", "ratio", "cutoff", "nominal")}
     q = da._pitch_launch(x.view(rows, window), dev, 0, rows, tables["cents_bound"], window, out.view(rows, window), "pitch_shift")
     return (out, q) if return_offsets else out
+
+
+# --------------------------------------------------------------------------- artificial reverberation
+def freeverb(x, room, reverberance=100.0, hf_damping=100.0, wet_gain_dB=0.0):
+    """The `freeverb` reverberation (data_augmentation.FreeverbAugment states it; csrc/freeverb.hip) of [b, 1, W], [b, W] or [W]
+    float32 device rows sampled at 16 kHz: `room` is one room size (0 to 100) for all rows or one per row.  The result has x's
+    shape.  This is this package's statement of the Freeverb network, not sox's `reverb`; nothing is drawn here."""
+    from . import data_augmentation as da
+    _lib.require_gpu(x)
+    x = _lib.f32c(x)
+    window = x.shape[-1]
+    rows = x.numel() // window if window else 0
+    per_row = np.asarray(room.cpu() if isinstance(room, torch.Tensor) else room)
+    if per_row.dtype.kind not in "iu":
+        raise TypeError("freeverb: room sizes are whole numbers (an int, or one per row)")
+    if per_row.ndim == 0:
+        per_row = np.full(rows, int(per_row), dtype=np.int64)
+    if per_row.size != rows:
+        raise ValueError(f"freeverb: {per_row.size} room sizes for {rows} rows")
+    tables = da.freeverb_tables(per_row, reverberance, hf_damping, wet_gain_dB)
+    out = torch.empty_like(x)
+    if rows == 0:
+        return out
+    comb_len = torch.from_numpy(tables["comb_len"]).to(x.device)
+    da._freeverb_launch(x.view(rows, window), comb_len, 0, rows, tables, window, out.view(rows, window), "freeverb")
+    return out
 
 
 def to_pcm16(waveform):

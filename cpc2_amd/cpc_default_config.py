@@ -2,14 +2,15 @@
 
 Same flags, types, choices and defaults as the reference's cpc/cpc_default_config.py:13-162 -- all of them, the
 augmentation group included: cpc2_amd.train builds additive / natural_reverb / time_dropout (data_augmentation.py) and
-pitch_wsola (a choice of --augment_type the reference does not have: a pitch shift by this package's own definition), and
+pitch_wsola (a choice of --augment_type the reference does not have: a pitch shift by this package's own definition) and
+freeverb (likewise: the Freeverb network behind sox's reverb, by this package's own definition, with ReverbAugment's draw), and
 refuses the sox-based types with a message (train.py, refuseUnsupported), and checkpoint_args.json carries the same keys as a reference run, so that either side can resume the other's run."""
 import argparse
 
 NAMING_CONVENTIONS = ['full_seedlings', 'no_speaker', 'id_spkr_onset_offset', 'spkr-id', 'spkr-id-nb',
                       'id_spkr_onset_offset_spkr_onset_offset', 'spkr_id_nb']
 AUGMENT_TYPES = ['none', 'bandreject', 'pitch', 'pitch_deropout', 'pitch_quick', 'additive', 'artificial_reverb',
-                 'time_dropout', 'artificial_reverb_dropout', 'natural_reverb', 'pitch_wsola']
+                 'time_dropout', 'artificial_reverb_dropout', 'natural_reverb', 'pitch_wsola', 'freeverb']
 
 
 def get_default_cpc_config():
@@ -78,7 +79,9 @@ def set_default_cpc_config(parser):
                                   "additive, natural_reverb, time_dropout, pitch_wsola and none are built, alone or combined; the "
                                   "sox-based types are parsed for checkpoint compatibility and refused by name.  pitch_wsola "
                                   "shifts the pitch by up to --shift_max cents (a WSOLA stretch and a sinc resampling: this "
-                                  "package's definition, not sox's).")
+                                  "package's definition, not sox's).  freeverb reverberates without "
+                                  "impulse responses (the Freeverb comb / all-pass network with the room size drawn per window: "
+                                  "this package's definition, agreement with sox's reverb unmeasured).")
     a.add_argument('--noise_extension', type=str, default='.wav')
     a.add_argument('--augment_future', action='store_true')
     a.add_argument('--augment_past', action='store_true')
@@ -97,7 +100,7 @@ def set_default_cpc_config(parser):
     a.add_argument('--ir_sample_rate', type=int, default=16000)
     a.add_argument('--temporal_additive_noise', action='store_true')
     a.add_argument('--meta_aug', action='store_true')
-    a.add_argument('--meta_aug_type', type=str, choices=['none', 'natural_reverb'], nargs='+')
+    a.add_argument('--meta_aug_type', type=str, choices=['none', 'natural_reverb', 'freeverb'], nargs='+')
     a.add_argument('--ir_batch_wise', action='store_true')
     a.add_argument('--meta_ir_batch_wise', action='store_true')
     return parser

@@ -1,13 +1,17 @@
 """Audio augmentation on device batches: the reference's cpc/data_augmentation.py for the types whose arithmetic is fixed.
 
 Built: `additive` (AdditiveNoiseAugment :157-228), `natural_reverb` (NaturalReverb :278-318), `time_dropout`
-(TimeDropoutAugment :268-275), `pitch_wsola` (PitchShiftAugment: a pitch shift by this package's own definition, below), their
+(TimeDropoutAugment :268-275), `pitch_wsola` (PitchShiftAugment: a pitch shift by this package's own definition, below),
+`freeverb` (FreeverbAugment: artificial reverberation by this package's own definition, below), their
 combinations (CombinedTransforms :331-344) and the reverberated noise (`augmentation_factory(..., applied_on_noise=True)`).
 The sox types (UNBUILT_TYPES: pitch, pitch_quick, pitch_dropout, pitch_deropout, bandreject, artificial_reverb, ...) are refused
 by name: neither sox nor WavAugment is available, and their filters cannot be pinned to anything.  `pitch_wsola` is NOT one of
 them under another name: it draws what the reference's PitchAugment draws and shifts the pitch, by an algorithm written down in
 PitchShiftAugment's docstring; its agreement with sox's `pitch` effect is unmeasured.  `--augment_type pitch_wsola time_dropout`
-stands in for the reference's `pitch_dropout`.
+stands in for the reference's `pitch_dropout`.  `freeverb` likewise: it draws what the reference's ReverbAugment draws (one room
+size per window) and reverberates with the public-domain Freeverb network -- the algorithm behind sox's `reverb` -- as written down
+in FreeverbAugment's docstring; `artificial_reverb` and `artificial_reverb_dropout` stay refused, the agreement of `freeverb` with
+sox's output is unmeasured, and `--augment_type freeverb time_dropout` stands in for `artificial_reverb_dropout`.
 
 The reference augments one window at a time on the CPU, inside DataLoader workers.  Here a pack of audio lives in HBM as one
 flat vector and so do the noise pack and the impulse responses; a batch's augmentation is a few kernels
@@ -31,9 +35,13 @@ Deviations from the reference, all deliberate:
     draws both from torch); a file is drawn only for a window the test lets through;
   * TimeDropoutAugment follows the definition in its docstring (the library the reference calls is not available);
   * PitchShiftAugment likewise: a WSOLA stretch and a windowed-sinc resampling instead of sox's pitch / rate chain, no dither;
+  * FreeverbAugment: one mono bank of eight combs and four all-passes at 16 kHz instead of sox's `reverb` chain: no pre-delay, no
+    tone filters, no stereo spread, no dither, no clipping, no peak normalisation, and the tail beyond the window is cut off (as
+    natural_reverb cuts it);
   * `--augment_type none` gives None (the reference's factory raises on the one-element list ['none']).
 """
 import collections
+import ctypes
 import os
 import random
 
@@ -44,6 +52,7 @@ from . import _lib
 from ._lib import check, ptr, stream_ptr
 
 BUILT_TYPES = ('additive', 'natural_reverb', 'time_dropout', 'pitch_wsola')
+OWN_TYPES = ('freeverb',)              # built as well; a tuple of its own, listed after BUILT_TYPES wherever the types are named
 UNBUILT_TYPES = ('bandreject', 'pitch', 'pitch_quick', 'pitch_dropout', 'pitch_deropout', 'artificial_reverb',
                  'artificial_reverb_dropout', 'random_noise')
 
@@ -56,10 +65,10 @@ FlatWindows = collections.namedtuple("FlatWindows", "data offsets")     # window
 def unbuilt_message(augment_type):
     """The refusal of a request that names a type without a kernel path (train.refuseUnsupported, augmentation_factory)."""
     asked = [augment_type] if isinstance(augment_type, str) else list(augment_type)
-    missing = [t for t in asked if t not in BUILT_TYPES and t != 'none']
+    missing = [t for t in asked if t not in BUILT_TYPES + OWN_TYPES and t != 'none']
     return (f"--augment_past / --augment_future with --augment_type {' '.join(asked)}: {', '.join(missing)} "
             f"{'is' if len(missing) == 1 else 'are'} not built (sox / WavAugment effects); the augmentation types on the MI355X "
-            f"feeder path are {', '.join(BUILT_TYPES)} and none, alone or combined")
+            f"feeder path are {', '.join(BUILT_TYPES)}, {', '.join(OWN_TYPES)} and none, alone or combined")
 
 
 # --------------------------------------------------------------------------- device helpers
@@ -491,6 +500,118 @@ class PitchShiftAugment(_Transform):
         return out
 
 
+# --------------------------------------------------------------------------- artificial reverberation
+FREEVERB_COMB = (1116, 1188, 1277, 1356, 1422, 1491, 1557, 1617)     # comb delays in samples at 44.1 kHz (the Freeverb network's)
+FREEVERB_ALLPASS = (225, 341, 441, 556)                              # all-pass delays, likewise
+FREEVERB_RHO = 16000 / 44100                                         # the effect is defined at 16 kHz only
+
+
+def freeverb_tables(rooms, reverberance=100.0, hf_damping=100.0, wet_gain_dB=0.0):
+    """The host tables of a batch of room sizes (FreeverbAugment's docstring), in f64: room [n] i32, comb_len [n, 8] i32 with
+    D[c] = int(scale rho COMB[c] + 0.5) and scale = rs / 100 * 0.9 + 0.1, allpass_len (4 ints), feedback / damping / gain (each
+    rounded once to f32, held as Python floats), feedback64 (the feedback before that rounding) and len_bound, the largest comb
+    length (at least 1).  Refuses, by the argument's name, a room size outside [0, 100], reverberance or hf_damping outside
+    [0, 100] and a wet_gain_dB that is not finite or whose gain does not fit float32."""
+    rooms = np.asarray(rooms, dtype=np.int64).reshape(-1)
+    if rooms.size and (int(rooms.min()) < 0 or int(rooms.max()) > 100):
+        raise ValueError(f"a room size of {int(rooms.min() if rooms.min() < 0 else rooms.max())}: freeverb takes 0 to 100")
+    if not 0 <= reverberance <= 100:
+        raise ValueError(f"reverberance {reverberance}: freeverb takes 0 to 100")
+    if not 0 <= hf_damping <= 100:
+        raise ValueError(f"hf_damping {hf_damping}: freeverb takes 0 to 100")
+    if not np.isfinite(wet_gain_dB):
+        raise ValueError(f"wet_gain_dB {wet_gain_dB}: freeverb needs a finite gain")
+    scale = rooms.astype(np.float64) / 100 * 0.9 + 0.1
+    comb = (scale[:, None] * FREEVERB_RHO * np.array(FREEVERB_COMB, dtype=np.float64)[None, :] + 0.5).astype(np.int64)
+    allpass = tuple(int(FREEVERB_RHO * a + 0.5) for a in FREEVERB_ALLPASS)
+    a = -1 / np.log(0.7)
+    b = 100 / (np.log(0.02) * a + 1)
+    feedback = 1 - np.exp((reverberance - b) / (a * b))
+    damping = hf_damping / 100 * 0.3 + 0.2
+    gain = 0.015 * 10 ** (wet_gain_dB / 20)
+    if not abs(gain) <= float(np.finfo(np.float32).max):
+        raise ValueError(f"wet_gain_dB {wet_gain_dB}: the gain does not fit float32")
+    return {"room": rooms.astype(np.int32), "comb_len": comb.astype(np.int32), "allpass_len": allpass,
+            "feedback": float(np.float32(feedback)), "damping": float(np.float32(damping)), "gain": float(np.float32(gain)),
+            "feedback64": float(feedback), "len_bound": max(int(comb.max()) if comb.size else 1, 1)}
+
+
+def _freeverb_launch(src, comb_len, lo, hi, tables, window, out, what="augment_freeverb"):
+    """cpc_augment_freeverb on rows [lo, hi) of the device table comb_len [n, 8] (int32)."""
+    dev = _device_of(src)
+    p, total, off = _operand(src)
+    allpass = (ctypes.c_int * 4)(*tables["allpass_len"])
+    check(_lib.load().cpc_augment_freeverb(p, total, off, ptr(comb_len[lo:hi]), int(tables["len_bound"]), allpass,
+                                           tables["feedback"], tables["damping"], tables["gain"], ptr(out), hi - lo, window,
+                                           stream_ptr(dev)), what)
+    return out
+
+
+class FreeverbAugment(_Transform):
+    """`freeverb`: artificial reverberation of every window, with the room size drawn as the reference's ReverbAugment
+    (data_augmentation.py: `random_room_size`) draws it -- ONE np.random.randint(0, room_max) per window from numpy's global
+    generator, room_max = 100; the output has the input's length and is not peak-normalised.  The reference hands the number to
+    sox's `reverb` effect -- reverb(reverberance = 100, hf_damping = 100, room); ReverbDropout uses (50, 50) -- which is not
+    available.  The algorithm behind that effect is the public-domain Freeverb network, and what happens to the window here is
+    THIS PACKAGE'S statement of it, written down below.  Its agreement with sox's output is unmeasured.  The constants are delays
+    in samples at 44.1 kHz; the effect is defined at 16 kHz only.
+
+      COMB = (1116, 1188, 1277, 1356, 1422, 1491, 1557, 1617)    ALLPASS = (225, 341, 441, 556)    rho = 16000 / 44100
+
+    Per window, on the host in f64 (`freeverb_tables`): rs the draw, scale = rs / 100 * 0.9 + 0.1,
+      D[c] = int(scale * rho * COMB[c] + 0.5)        A[a] = int(rho * ALLPASS[a] + 0.5) = (82, 124, 160, 202)
+      a = -1 / ln(0.7)    b = 100 / (ln(0.02) * a + 1)    fb = 1 - exp((reverberance - b) / (a * b))
+      dmp = hf_damping / 100 * 0.3 + 0.2                g = 0.015 * 10 ** (wet_gain_dB / 20)
+    and fb, dmp, g are rounded once to f32.  The defaults (100, 100, 0 dB) give fb = 0.98 and dmp = 0.5; (50, 50) gives
+    fb = 0.8816784043380077 and dmp = 0.35.  rs = 0 gives D = (40, 43, 46, 49, 52, 54, 56, 59), rs = 99 gives
+    D = (401, 427, 459, 488, 511, 536, 560, 581).
+
+    The window x[0 .. W) is f32; all state is zero at n = 0 and nothing outside the window is read, whatever lies beside it in a
+    pack.  For n = 0 .. W - 1, in f32:
+
+      u = g * x[n];  acc = 0
+      for c in 0..7:   o = line_c[p_c];  s_c = o + (s_c - o) * dmp;  line_c[p_c] = u + s_c * fb;  p_c = (p_c + 1) % D[c];  acc = acc + o
+      v = acc
+      for a in 0..3:   o = line_a[p_a];  line_a[p_a] = v + o * 0.5;  v = o - v;  p_a = (p_a + 1) % A[a]
+      y[n] = x[n] + v
+
+    No pre-delay, no tone filters, no stereo spread (one mono bank), no dither, no clipping, no peak normalisation; the tail beyond
+    W is cut off, as natural_reverb cuts it.  On the device (csrc/freeverb.hip) one workgroup per window keeps the twelve lines in
+    LDS and performs exactly these operations in this order, so a window's bits depend on nothing else in the batch or the pack.
+
+    Entry: rs.  Plan: room [n] i32, comb_len [n, 8] i32, allpass_len, feedback, damping, gain, len_bound.  Out of place."""
+
+    def __init__(self, room_max=100, reverberance=100.0, hf_damping=100.0, wet_gain_dB=0.0):
+        if not np.isfinite(room_max) or room_max != int(room_max):
+            raise ValueError(f"room_max {room_max}: freeverb draws a whole room size from [0, room_max)")
+        if not 1 <= room_max <= 100:
+            raise ValueError(f"room_max {room_max}: freeverb draws the room size from [0, room_max), room_max from 1 to 100")
+        freeverb_tables([], reverberance, hf_damping, wet_gain_dB)      # (refuses the other three by name, a gain beyond float32 too)
+        self.room_max = int(room_max)
+        self.reverberance = float(reverberance)
+        self.hf_damping = float(hf_damping)
+        self.wet_gain_dB = float(wet_gain_dB)
+
+    def draw_one(self, window):
+        return int(np.random.randint(0, self.room_max))
+
+    def seal(self, entries, device):
+        plan = {"kind": "freeverb", "n": len(entries)}
+        plan.update(freeverb_tables(np.array(entries, dtype=np.int64).reshape(-1), self.reverberance, self.hf_damping,
+                                    self.wet_gain_dB))
+        plan["_dev"] = {"comb_len": _upload(plan["comb_len"], device)}
+        return plan
+
+    def apply(self, plan, lo, hi, src, dst=None, window=None):
+        _check_src(src)
+        window = _window(src, dst, window)
+        if not isinstance(src, FlatWindows) and dst is not None and src.data_ptr() == dst.data_ptr():
+            src = src.clone()                                          # (out of place: the kernel refuses out == src)
+        out = dst if dst is not None else torch.empty(hi - lo, window, dtype=torch.float32, device=_device_of(src))
+        _freeverb_launch(src, plan["_dev"]["comb_len"], lo, hi, plan, window, out)
+        return out
+
+
 # --------------------------------------------------------------------------- combinations
 class CombinedTransforms(_Transform):
     """data_augmentation.py:331-344: the transforms of `augment_cfgs`, applied in the order given ('none' entries skipped).
@@ -546,6 +667,8 @@ def get_augment(augment_type, **kwargs):
                              batchSize=kwargs['batchSize'], sr=kwargs['ir_sample_rate'], batch_wise=kwargs['ir_batch_wise'])
     if augment_type == 'pitch_wsola':
         return PitchShiftAugment(kwargs['shift_max'])
+    if augment_type == 'freeverb':
+        return FreeverbAugment()
     if augment_type in UNBUILT_TYPES:
         raise NotImplementedError(unbuilt_message(augment_type))
     raise RuntimeError(f'Unknown augment_type = {augment_type}')

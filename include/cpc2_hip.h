@@ -60,7 +60,8 @@ int cpc_version(void);          /* 100 x major + minor; 105 = the entry points o
                                   * 122 = cpc_probe_ctc runs on cpc_ctc_loss's kernels: cpc_probe_ctc_scratch_bytes returns
                                   * cpc_ctc_loss_scratch_bytes of the same sizes, and cpc_probe_ctc needs b <= 65535;
                                   * 123 = cpc_augment_pitch;
-                                  * 124 = cpc_seg_dissimilarity / cpc_seg_boundaries / cpc_seg_lds_entries */
+                                  * 124 = cpc_seg_dissimilarity / cpc_seg_boundaries / cpc_seg_lds_entries;
+                                  * 125 = cpc_augment_freeverb */
 const char *cpc_last_error(void);
 
 /* In-situ kernel timing for bench.py: when enabled, the launchers bracket each launch of the named
@@ -732,6 +733,39 @@ int cpc_augment_time_dropout(float *x, const long *start, const long *length, in
 int cpc_augment_pitch(const float *src, long src_total, const long *src_off, const double *ratio, const double *cutoff,
                       const int *cents, int cents_bound, const int *nominal, int segments, float *out, int *q, int batch,
                       int window, cpc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Artificial reverberation of windows (the `freeverb` augmentation; cpc2_amd/data_augmentation.py FreeverbAugment,
+ * csrc/freeverb.hip).  version 125.  The reference's ReverbAugment is a sox effect chain (`reverb`) that is not available; the
+ * algorithm behind it is the public-domain Freeverb network, and this is THIS LIBRARY'S statement of it: eight parallel feedback
+ * comb filters with a one-pole low-pass in the loop, then four all-pass filters in series.  Its agreement with sox's output is
+ * unmeasured.  The effect is defined at 16 kHz only.  The caller's tables (data_augmentation.freeverb_tables, in double):
+ *   COMB = (1116, 1188, 1277, 1356, 1422, 1491, 1557, 1617)  ALLPASS = (225, 341, 441, 556)  (samples at 44.1 kHz)
+ *   rho = 16000 / 44100;  per window a room size rs in [0, 100):  scale = rs / 100 * 0.9 + 0.1
+ *   comb_len[i][c] = D[c] = int(scale * rho * COMB[c] + 0.5)      allpass_len[a] = A[a] = int(rho * ALLPASS[a] + 0.5) = (82, 124, 160, 202)
+ *   a = -1 / ln(0.7);  b = 100 / (ln(0.02) * a + 1);  feedback fb = 1 - exp((reverberance - b) / (a * b))
+ *   damping dmp = hf_damping / 100 * 0.3 + 0.2;  gain g = 0.015 * 10 ** (wet_gain_dB / 20);  fb, dmp, g rounded once to f32
+ *   (reverberance = hf_damping = 100, the reference's reverb(100, 100, room): fb = 0.98, dmp = 0.5)
+ * Window i is x[0 .. W) of the source (f32); nothing outside it is read, whatever lies beside it in the vector.  All state is
+ * zero at n = 0.  For n = 0 .. W - 1, every operation in f32 and in this order, nothing contracted:
+ *   u = g * x[n];  acc = 0
+ *   for c in 0..7:  o = line_c[p_c];  s_c = o + (s_c - o) * dmp;  line_c[p_c] = u + s_c * fb;  p_c = (p_c + 1) % D[c];  acc = acc + o
+ *   v = acc
+ *   for a in 0..3:  o = line_a[p_a];  line_a[p_a] = v + o * 0.5;  v = o - v;  p_a = (p_a + 1) % A[a]
+ *   out[i][n] = x[n] + v
+ * No pre-delay, no tone filters, no stereo spread (one mono bank), no dither, no clipping, no peak normalisation; the tail beyond
+ * W is cut off.  The kernel performs exactly these operations (one workgroup per window, the twelve lines in LDS), so out equals a
+ * float32 evaluation of the statement and a window's bits depend on nothing else in the batch, the vector or the launch.
+ * comb_len is a DEVICE table [batch][8]; len_bound is the HOST's bound on its entries (the table is not read back) and sizes the
+ * lines: the kernel clamps every entry into [1, len_bound].  allpass_len[4] is a HOST array.
+ * Refused with CPC_ERR_INVALID, nothing launched and nothing written: window <= 0, batch < 0 or > 65535, len_bound or an all-pass
+ * length outside [1, 1024], feedback outside [0, 1), damping outside [0, 1], a scalar that is not finite, a null pointer with
+ * batch > 0 (allpass_len always), out == src.  batch == 0 is a no-op.  The source is given as the other augment entries take it:
+ * (vector, total, offsets) with zeros outside [0, total), or a [batch][window] buffer with offsets == NULL.
+ * ------------------------------------------------------------------------------------------ */
+int cpc_augment_freeverb(const float *src, long src_total, const long *src_off, const int *comb_len, int len_bound,
+                         const int *allpass_len, float feedback, float damping, float gain, float *out, int batch, int window,
+                         cpc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Sample-rate conversion (torchaudio's sinc_interp_hann resampler, the transform of the reference's
