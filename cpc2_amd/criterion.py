@@ -62,7 +62,8 @@ def _infonce_forward(z, ext_idx, weights, n_neg, c=None, wpred=None, preds=None)
     if weights is not None and weights.numel() != b * (t - k):
         raise ValueError(f"weights must hold one value per (window, frame): {b * (t - k)}, got {weights.numel()}")
     nsaved = lib.cpc_infonce_saved_bytes(b, t, k, dim_ar, dim_enc, n_neg)
-    nscratch = lib.cpc_infonce_scratch_bytes(b, t, k, dim_ar, dim_enc, n_neg)
+    # (-dim_ar: the linear entry points' own need -- without the contribution rows where dz comes from per-row context sums)
+    nscratch = lib.cpc_infonce_scratch_bytes(b, t, k, -dim_ar if preds is None else dim_ar, dim_enc, n_neg)
     if nsaved == 0:
         check(-1, "infonce shape query")
     losses = torch.empty(k, dtype=torch.float32, device=z.device)
@@ -127,7 +128,7 @@ class _InfoNCEFn(torch.autograd.Function):
         direct = dw is not None
         if not direct:
             dw = torch.empty_like(wpred)
-        nscratch = lib.cpc_infonce_scratch_bytes(b, t, k, dim_ar, dim_enc, n_neg)
+        nscratch = lib.cpc_infonce_scratch_bytes(b, t, k, -dim_ar, dim_enc, n_neg)
         # (the weight gradients may only be late when nothing reads them before the end of the backward pass: written in place
         #  into the flat gradient buffer.  A private buffer is added to .grad by autograd as soon as this function returns.)
         defer = defer and direct

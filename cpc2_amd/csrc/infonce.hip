@@ -22,6 +22,7 @@
 #include <cstdlib>
 #include <map>
 #include <mutex>
+#include <string>
 
 namespace cpc {
 
@@ -669,7 +670,10 @@ template <int H> __global__ __launch_bounds__(64) void infonce_dz_store_kernel(N
 //            sweeps the gathered z rows out of L2 (PMC: 928 MB fetched per launch for 970 MB of gathers).
 // NKK = ceil(K / 4).  Needs Nneg % 16 == 0, lw <= 320 and K * (Nneg + 1) floats within the staging tiles.
 constexpr int NCE_SROW = 68;               // staging tile row: 64 channels + 4 floats
-template <int H, int NKK> __global__ __launch_bounds__(H / 2) void infonce_bwd_fused_kernel(NceArgs a)
+// ROWS = false (linear predictors, infonce_dz_q_kernel below): phase 2 is left out -- no contribution row is formed and vbuf is
+// not touched; dS leaves instead, NCE_POS + Nneg rows of 16 floats per (b,t), for the kernel that sums it per z row.  Phases 0 and
+// 1 are the same instructions in the same order, so dP does not change by a bit.
+template <int H, int NKK, bool ROWS> __global__ __launch_bounds__(H / 2) void infonce_bwd_fused_kernel(NceArgs a)
 {
     constexpr int NW = H / 128;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -743,6 +747,10 @@ template <int H, int NKK> __global__ __launch_bounds__(H / 2) void infonce_bwd_f
         }
     }
     __syncthreads();
+    if (!ROWS) {
+        float *dsq = a.ds_buf + bt * (long)ncand * NCE_ROWS;      // [NCE_POS + Nneg][16]: a candidate's coefficients side by side
+        for (int i = threadIdx.x; i < ncand * NCE_ROWS; i += 64 * NW) dsq[i] = dS[(i & 15) * a.lw + (i >> 4)];
+    }
 
     // ---- phases 1 and 2, one loop over groups of 16 candidates: the rows of group i + 1 are requested, the contribution rows
     // of group i are formed and stored (no gathered row needed), THEN the gathered rows of group i are multiplied into dP --
@@ -751,7 +759,7 @@ template <int H, int NKK> __global__ __launch_bounds__(H / 2) void infonce_bwd_f
     const long prow_off = ((long)bb * a.p_rows + t) * a.p_stride + d0;
     float pa[8][NKK];                                              // phase 2's A: P_{4kk + q}[d0 + 16*tile + r]
 #pragma unroll
-    for (int kk = 0; kk < NKK; ++kk) {
+    for (int kk = 0; ROWS && kk < NKK; ++kk) {
         const int k = 4 * kk + q;
         const float *pk = a.Pk[min(k, a.K - 1)] + prow_off + r;
 #pragma unroll
@@ -824,10 +832,10 @@ template <int H, int NKK> __global__ __launch_bounds__(H / 2) void infonce_bwd_f
         request(0, 0);
         for (int ib = 0; ib < nb; ib += 2) {
             request(1, 4 * (ib + 1));
-            NCE_ROWS_GROUP(16 * ib)
+            if (ROWS) NCE_ROWS_GROUP(16 * ib)
             multiply(0);
             if (ib + 2 < nb) request(0, 4 * (ib + 2));
-            if (16 * (ib + 1) < ncand) NCE_ROWS_GROUP(16 * (ib + 1))
+            if (ROWS && 16 * (ib + 1) < ncand) NCE_ROWS_GROUP(16 * (ib + 1))
             multiply(1);
         }
         // dp[T4][e][reg] = dP[k = r][d = d0 + 64*T4 + 4*(4q + reg) + e]
@@ -976,6 +984,105 @@ template <int H> __global__ __launch_bounds__(256, 8) void infonce_dz_gather_ker
     }
 }
 
+// ---- dz with LINEAR predictors: the predictor leaves the sum.  P_k[bt] = W_k c[bt] (criterion.py:163, nn.Linear(..., bias=False):
+// no bias column), so
+//   dz[r] = sum_{(bt,cand) -> r} sum_k dS[bt][k][cand] W_k c[bt]  =  sum_k W_k Q[r][k],   Q[r][k][:] = sum_{(bt,cand) -> r} dS[bt][k][cand] c[bt][:]
+// (dS carries the 1 / H, the sample weight and 1 / (b W): infonce_bwd_fused_kernel's coef).  Q is [b*T][K][HA] -- 100 MB at the
+// benchmark shape against the 1.06 GB of contribution rows -- and is summed from rows of c, a table that stays in the caches;
+// dz is then one product [b*T, K*HA] x [K*HA, H].
+// HA / 128 waves per z row, 128 channels each.  A wave walks the row's reference list in list order, then the row's positives
+// (z row (bb, tp) is the positive of step k at (bb, tp - 1 - k): slot k of that (b,t), whose other K - 1 coefficients are zeros
+// of the dS tile), four entries per f32 MFMA: Q[k][ch] += dS[entry][k] * c[entry][ch] is a 16 x 16 x 4 product per 16 channels
+// (M = k, N = channel), one instruction where the vector ALU needs 4 x 12 FMAs per lane and a lane-to-lane hand-over per
+// coefficient (that form, measured beside the recurrent backward: 270-370 us, at its instruction issue bound).  No atomics, one
+// order, and a row nobody refers to leaves as zeros.  Rows come only from the lists nce_fill_kernel built out of the block-sorted
+// (range-checked) indices.
+// 64 entries are decoded at once, one per lane (the two divisions cost a 64th); a shuffle hands entry i0 + q's two offsets to the
+// 16 lanes of quarter q.  Per four entries: one dword of coefficients (dS[bt][slot][r]) and eight dwords of context (channels
+// 16 j + r) per lane, two such groups in flight.  Offsets are 32-bit: nce_dz_q_wanted.
+template <int HA> __global__ __launch_bounds__(256, 4) void infonce_dz_q_kernel(const float *c, const float *dsq, const int *offsets,
+                                                                                const int *entries, float *Q, int b, int T, int W,
+                                                                                int K, int Nneg, int Pr)
+{
+    constexpr int WPR = HA / 128, RPB = 4 / WPR;     // waves per row, rows per workgroup
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4;
+    const unsigned r16 = lane & 15;
+    const int r = __builtin_amdgcn_readfirstlane(blockIdx.x * RPB + wave / WPR);
+    if (r >= b * T) return;
+    const unsigned ch = 128 * (wave % WPR) + r16;
+    const int ncand = NCE_POS + Nneg;
+    const int bb = r / T, tp = r - bb * T;
+    f32x4 acc[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    // n <= 64 entries, lane i < n holding entry i: coff = where its context row starts in c, doff = its 16 coefficients in dsq
+    auto chunk = [&](int n, int coff, int doff) {
+        for (int i0 = 0; i0 < n; i0 += 8) {
+            float av[2], bv[2][8];
+#pragma unroll
+            for (int g = 0; g < 2; ++g) {            // (past the end: entry n - 1 again, with zeros for its coefficients)
+                const int i = i0 + 4 * g + q, ic = min(i, n - 1);
+                const int co = __shfl(coff, ic), dof = __shfl(doff, ic);
+                const float a = dsq[(unsigned)dof + r16];
+                av[g] = i < n ? a : 0.f;
+                const float *crow = c + ((unsigned)co + ch);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) bv[g][j] = crow[16 * j];
+            }
+#pragma unroll
+            for (int g = 0; g < 2; ++g)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[g], bv[g][j], acc[j], 0, 0, 0);
+        }
+    };
+    const int beg = offsets[r], end = offsets[r + 1];
+    for (int e0 = beg; e0 < end; e0 += 64) {
+        const int n = min(64, end - e0);
+        int coff = 0, doff = 0;
+        if (lane < n) {
+            const int o = entries[e0 + lane];
+            const int bt = o / Nneg, eb = bt / W;
+            coff = (eb * Pr + bt - eb * W) * HA;
+            doff = (bt * ncand + NCE_POS + o - bt * Nneg) * NCE_ROWS;
+        }
+        chunk(n, coff, doff);
+    }
+    // the positives, steps k0 .. k1 (t = tp - 1 - k within [0, W)), as entries of slot k
+    const int k0 = max(0, tp - W), k1 = min(K - 1, tp - 1);
+    if (k1 >= k0) {
+        const int n = k1 - k0 + 1;
+        int coff = 0, doff = 0;
+        if (lane < n) {
+            const int k = k0 + lane, t = tp - 1 - k;
+            coff = (bb * Pr + t) * HA;
+            doff = ((bb * W + t) * ncand + k) * NCE_ROWS;
+        }
+        chunk(n, coff, doff);
+    }
+    // acc[j][e] = Q[k = 4q + e][channel 16 j + r16 of this wave's 128]
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int k = 4 * q + e;
+        if (k < K) {
+            float *out = Q + ((long)r * K + k) * HA + ch;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) out[16 * j] = acc[j][e];
+        }
+    }
+}
+
+// wq[e][k*Har + a] = wpred[k][e][a]: the predictors side by side, the B operand of dz = Q . wq^T
+__global__ void nce_wq_kernel(const float *wpred, float *wq, int K, int Henc, int Har)
+{
+    const long n = (long)K * Henc * Har;
+    for (long o = (long)blockIdx.x * blockDim.x + threadIdx.x; o < n; o += (long)gridDim.x * blockDim.x) {
+        const int a = (int)(o % Har);
+        const long ke = o / Har;
+        const int e = (int)(ke % Henc), k = (int)(ke / Henc);
+        wq[((long)e * K + k) * Har + a] = wpred[o];
+    }
+}
+
 // raw[0..n) -> batchIdx = raw % b, raw[n..2n) -> seqIdx = raw % (T-1) + 1 (draw order i = (bb*Nneg + nn)*W + t);
 // ext[(bb*W + t)*Nneg + nn] = (seqIdx + t) mod T + batchIdx*T      (criterion.py:247-266, integer-exact)
 __global__ void negidx_expand_kernel(const uint32_t *raw, int32_t *ext, int b, int T, int W, int Nneg)
@@ -1005,6 +1112,8 @@ struct NceLayout {
     float *lossp, *hit, *dP, *wt, *tn, *tn_late;  // scratch
     float *vbuf;                        // scratch: [b*W][K + Nneg][Henc] contribution rows of the dz product
     float *ds_buf;                      // scratch: [b*W][17][lw]
+    bool dz_q;                          // dz through per-row context sums (infonce_dz_q_kernel): no vbuf; ds_buf is [b*W][16 + Nneg][16]
+    float *Q, *wq;                      // scratch (dz_q): [b*T][K][Har] and the predictors as [Henc][K*Har]
     int *counts, *offsets, *entries;    // scratch: reference lists (counts doubles as the fill cursor)
     size_t tn_bytes, scratch_bytes;
     size_t lds_fwd, lds_bwd, lds_bwd_fused;
@@ -1012,7 +1121,29 @@ struct NceLayout {
 
 static bool nce_supported(int H) { return H == 32 || H == 64 || H == 128 || H == 256 || H == 512; }
 
-static int nce_layout(NceLayout &l, int b, int T, int K, int Har, int Henc, int Nneg, void *saved, void *scratch)
+// the fused backward kernel's shapes (infonce_bwd_fused_kernel)
+static bool nce_fused_ok(int K, int Henc, int Nneg)
+{
+    const int lw = (int)cdiv(NCE_POS + Nneg, 32) * 32 + 4;
+    return (Henc == 256 || Henc == 512) && lw <= 320 && Nneg % 16 == 0 && (size_t)K * (Nneg + 1) <= (size_t)(Henc / 128) * 16 * NCE_SROW;
+}
+
+// dz through per-row context sums: linear predictors at the fused kernel's shapes, a context width the sum kernel is built for.
+// Chosen with CPC_NCE_DZ=q (read at every call).  The default, and `rows`, keep the contribution rows: dz of the sums differs from
+// theirs in its last bits (another association of the same f32 sum), and a training run started from the same seed does not
+// stay within rounding of the earlier one -- after 25 Adam steps at the ln 129 plateau the parameters are 0.7 % rms apart, from
+// 1e-7 after one step -- for a step that is 1.6-1.9 % shorter
+static bool nce_dz_q_wanted(int b, int T, int K, int Har, int Henc, int Nneg)
+{
+    const char *env = std::getenv("CPC_NCE_DZ");
+    if (env == nullptr || std::string(env) != "q") return false;
+    // (infonce_dz_q_kernel's 32-bit offsets into c and into dS)
+    const bool small = b > 0 && T > K && (size_t)b * T * Har < (1u << 31) && (size_t)b * (T - K) * (NCE_POS + Nneg) * NCE_ROWS < (1u << 31);
+    return small && nce_fused_ok(K, Henc, Nneg) && (Har == 256 || Har == 512);
+}
+
+// dz_q: the layout of the linear entry points on the per-row-sums path; false: with the contribution rows (every other case)
+static int nce_layout(NceLayout &l, int b, int T, int K, int Har, int Henc, int Nneg, void *saved, void *scratch, bool dz_q = false)
 {
     CPC_REQUIRE(nce_supported(Henc), "infonce: encoder dim %d not supported (32, 64, 128, 256, 512)", Henc);
     CPC_REQUIRE(b > 0 && K >= 1 && K <= 16 && T > K && Nneg >= 1 && Har >= 1,
@@ -1036,13 +1167,22 @@ static int nce_layout(NceLayout &l, int b, int T, int K, int Har, int Henc, int 
     l.dP = sc.take<float>((size_t)b * T * K * Henc);
     l.wt = sc.take<float>((size_t)K * Henc * Har);
     l.tn_bytes = std::max(gemm_tn_scratch_bytes(K * Henc, Har, (long)b * T), gemm_nt_scratch_bytes((long)b * T, Har, K * Henc));
+    if (dz_q) l.tn_bytes = std::max(l.tn_bytes, gemm_nt_scratch_bytes((long)b * T, Henc, K * Har));
     l.tn = sc.take<float>(l.tn_bytes / sizeof(float));
     l.tn_late = sc.take<float>(l.tn_bytes / sizeof(float));   // the weight gradient's slabs when it runs beside dc's K split (deferred form)
     l.counts = sc.take<int>((size_t)b * T);
     l.offsets = sc.take<int>((size_t)b * T + 1);
     l.entries = sc.take<int>((size_t)b * l.W * Nneg);
-    l.vbuf = sc.take<float>((size_t)b * l.W * (NCE_POS + Nneg) * Henc);
-    l.ds_buf = sc.take<float>((size_t)b * l.W * (NCE_ROWS + 1) * l.lw);
+    l.dz_q = dz_q;
+    l.vbuf = l.Q = l.wq = nullptr;
+    if (dz_q) {
+        l.Q = sc.take<float>((size_t)b * T * K * Har);
+        l.wq = sc.take<float>((size_t)K * Henc * Har);
+        l.ds_buf = sc.take<float>((size_t)b * l.W * (NCE_POS + Nneg) * NCE_ROWS);
+    } else {
+        l.vbuf = sc.take<float>((size_t)b * l.W * (NCE_POS + Nneg) * Henc);
+        l.ds_buf = sc.take<float>((size_t)b * l.W * (NCE_ROWS + 1) * l.lw);
+    }
     l.scratch_bytes = sc.used();
     l.lds_fwd = align_up(sizeof(int) * (size_t)Nneg + sizeof(unsigned short) * (size_t)Nneg, 16);
     l.lds_bwd = sizeof(float) * (size_t)NCE_ROWS * l.lw + sizeof(int) * (size_t)l.lw;
@@ -1142,7 +1282,7 @@ struct NceSide {
     bool marked = false, started = false, late_fused = false;     // marked: `mid` recorded
     NceLayout l;
     float *dz = nullptr, *dwpred = nullptr;
-    const float *c = nullptr;
+    const float *c = nullptr, *wpred = nullptr;
 };
 
 static int nce_side(NceSide **out, hipStream_t caller)
@@ -1165,9 +1305,29 @@ static int nce_side(NceSide **out, hipStream_t caller)
 }
 
 // dz of the criterion: the sum per target row of the stored contribution rows (see infonce_bwd_kernel)
-static int nce_launch_gather(const NceLayout &l, float *dz, bool fused, hipStream_t st)
+// or, with linear predictors (l.dz_q; c the context, wpred the packed predictors): Q from the reference lists and the context rows,
+// then dz = Q . wq^T through the exact f32 GEMM, its K split ordered in tn_late (free on whichever stream this is queued on: the
+// weight gradient that uses it follows on the same stream)
+static int nce_launch_gather(const NceLayout &l, const float *c, const float *wpred, float *dz, bool fused, hipStream_t st)
 {
     const int rows = l.b * l.T;
+    if (l.dz_q) {
+        CPC_REQUIRE(c != nullptr && wpred != nullptr && fused, "infonce: the per-row sums need linear predictors and the fused backward kernel");
+        const unsigned grid = (unsigned)cdiv(rows, 512 / l.Har);
+        if (l.Har == 256)
+            hipLaunchKernelGGL(infonce_dz_q_kernel<256>, dim3(grid), dim3(256), 0, st, c, l.ds_buf, l.offsets, l.entries, l.Q, l.b, l.T, l.W, l.K,
+                               l.Nneg, l.Pr);
+        else
+            hipLaunchKernelGGL(infonce_dz_q_kernel<512>, dim3(grid), dim3(256), 0, st, c, l.ds_buf, l.offsets, l.entries, l.Q, l.b, l.T, l.W, l.K,
+                               l.Nneg, l.Pr);
+        CPC_CHECK_LAUNCH("infonce_dz_q_kernel");
+        const long nw = (long)l.K * l.Henc * l.Har;
+        hipLaunchKernelGGL(nce_wq_kernel, dim3((unsigned)std::min<long>(cdiv(nw, 256), 2048)), dim3(256), 0, st, wpred, l.wq, l.K, l.Henc, l.Har);
+        CPC_CHECK_LAUNCH("nce_wq_kernel");
+        RowMap map{};
+        map.splitk_scratch = l.tn_late; map.splitk_bytes = l.tn_bytes;
+        return gemm_nt(l.Q, (long)l.K * l.Har, l.wq, (long)l.K * l.Har, dz, l.Henc, nullptr, rows, l.Henc, l.K * l.Har, map, st);
+    }
     // (one workgroup per four rows.  Fewer, persistent workgroups -- so that only a few waves per CU stream beside the recurrent
     //  backward -- were measured again in round 4: 256 / 512 / 1024 workgroups cost CPC-large +1.2 / +0.35 / 0 ms per step and
     //  CPC-small 0 .. +0.15, as in round 3)
@@ -1180,7 +1340,9 @@ static int nce_launch_gather(const NceLayout &l, float *dz, bool fused, hipStrea
 
 // `late` (deferred form): the sum of the contribution rows into dz is NOT launched; *late is left pointing at the side record
 // (the reference lists are queued on its stream) and the caller launches nce_launch_gather there when it wants it to start
-static int nce_launch_bwd(NceArgs &a, const NceLayout &l, float *dz, hipStream_t st, NceSide **late = nullptr)
+// c, wpred: the linear entry's context and packed predictors (l.dz_q needs them), null from the module-predictor entry
+static int nce_launch_bwd(NceArgs &a, const NceLayout &l, float *dz, hipStream_t st, NceSide **late = nullptr, const float *c = nullptr,
+                          const float *wpred = nullptr)
 {
     const long n = (long)l.b * l.W * l.Nneg;
     const int rows = l.b * l.T;
@@ -1201,15 +1363,16 @@ static int nce_launch_bwd(NceArgs &a, const NceLayout &l, float *dz, hipStream_t
     CPC_CHECK_LAUNCH("infonce reference lists");
     CPC_CHECK_HIP(hipEventRecord(side->join, side->stream));
     int status = CPC_OK;
-    const bool fused = (l.Henc == 256 || l.Henc == 512) && a.perm != nullptr && l.lw <= 320 &&
-                       l.Nneg % 16 == 0 && (size_t)l.K * (l.Nneg + 1) <= (size_t)(l.Henc / 128) * 16 * NCE_SROW;
+    const bool fused = nce_fused_ok(l.K, l.Henc, l.Nneg) && a.perm != nullptr;
+    CPC_REQUIRE(fused || !l.dz_q, "infonce: the per-row sums need the fused backward kernel");
     if (fused) {
         const unsigned grid = (unsigned)(l.b * a.p_rows);
-#define NCE_FUSED(HH, NKK)                                                                                                  \
+#define NCE_FUSED_AS(HH, NKK, ROWS)                                                                                         \
     {                                                                                                                       \
-        status = allow_lds(infonce_bwd_fused_kernel<HH, NKK>, l.lds_bwd_fused);                                             \
-        if (status == CPC_OK) hipLaunchKernelGGL((infonce_bwd_fused_kernel<HH, NKK>), dim3(grid), dim3(HH / 2), l.lds_bwd_fused, st, a); \
+        status = allow_lds(infonce_bwd_fused_kernel<HH, NKK, ROWS>, l.lds_bwd_fused);                                       \
+        if (status == CPC_OK) hipLaunchKernelGGL((infonce_bwd_fused_kernel<HH, NKK, ROWS>), dim3(grid), dim3(HH / 2), l.lds_bwd_fused, st, a); \
     }
+#define NCE_FUSED(HH, NKK) { if (l.dz_q) NCE_FUSED_AS(HH, NKK, false) else NCE_FUSED_AS(HH, NKK, true) }
         const int nkk = (l.K + 3) / 4;
         if (l.Henc == 256) {
             if (nkk == 1) NCE_FUSED(256, 1) else if (nkk == 2) NCE_FUSED(256, 2) else if (nkk == 3) NCE_FUSED(256, 3) else NCE_FUSED(256, 4)
@@ -1217,6 +1380,7 @@ static int nce_launch_bwd(NceArgs &a, const NceLayout &l, float *dz, hipStream_t
             if (nkk == 1) NCE_FUSED(512, 1) else if (nkk == 2) NCE_FUSED(512, 2) else if (nkk == 3) NCE_FUSED(512, 3) else NCE_FUSED(512, 4)
         }
 #undef NCE_FUSED
+#undef NCE_FUSED_AS
     } else {
         NCE_DISPATCH(l.Henc, {
             status = allow_lds(infonce_bwd_kernel<HH>, l.lds_bwd);
@@ -1235,7 +1399,7 @@ static int nce_launch_bwd(NceArgs &a, const NceLayout &l, float *dz, hipStream_t
         return CPC_OK;
     }
     CPC_CHECK_HIP(hipStreamWaitEvent(st, side->join, 0));
-    CPC_TRY(nce_launch_gather(l, dz, fused, st));
+    CPC_TRY(nce_launch_gather(l, c, wpred, dz, fused, st));
     return CPC_OK;
 }
 
@@ -1266,7 +1430,7 @@ static int infonce_backward(const float *c, const float *z, const float *wpred, 
                             int K, int Har, int Henc, int Nneg, int c_frames, bool defer, hipStream_t st)
 {
     NceLayout l;
-    CPC_TRY(nce_layout(l, b, T, K, Har, Henc, Nneg, saved, scratch));
+    CPC_TRY(nce_layout(l, b, T, K, Har, Henc, Nneg, saved, scratch, nce_dz_q_wanted(b, T, K, Har, Henc, Nneg)));
     CPC_REQUIRE(c_frames == T || c_frames == l.W, "infonce: the context holds %d frames per window (expected %d or %d)", c_frames, T, l.W);
     l.Pr = c_frames;
     NceArgs a{};
@@ -1274,11 +1438,11 @@ static int infonce_backward(const float *c, const float *z, const float *wpred, 
     for (int k = 0; k < K; ++k) { a.Pk[k] = l.P + (size_t)k * Henc; a.dPk[k] = l.dP + (size_t)k * Henc; }
     a.p_stride = (long)K * Henc; a.p_rows = l.Pr;
     a.dloss = dlosses;
-    // Deferred form: only dc -- what the context network's backward waits for -- is produced on `st`.  dz (a memory-bound sum
-    // over ~1 GB of contribution rows) and the predictors' weight gradients run on the side stream, beside whatever the caller
+    // Deferred form: only dc -- what the context network's backward waits for -- is produced on `st`.  dz (the per-row context
+    // sums and their product, or a sum over ~1 GB of contribution rows) and the predictors' weight gradients run on the side stream, beside whatever the caller
     // queues on `st` next (the recurrent backward: latency-bound, the chip mostly idle), until cpc_infonce_join.
     NceSide *late = nullptr;
-    CPC_TRY(nce_launch_bwd(a, l, dz, st, defer ? &late : nullptr));
+    CPC_TRY(nce_launch_bwd(a, l, dz, st, defer ? &late : nullptr, c, wpred));
     // dc = dP . W  (rows t >= W of dP are zero)
     CPC_TRY(transpose2d(wpred, l.wt, K * Henc, Har, st));                        // [Har][K*Henc]
     RowMap none{};
@@ -1288,7 +1452,7 @@ static int infonce_backward(const float *c, const float *z, const float *wpred, 
     if (late != nullptr) {
         // nothing is queued on the side stream yet: queued here, beside the product above, it took the chip from it (85 -> 280 us)
         // and then stood in the way of the small kernels in front of the recurrent backward instead of filling its idle time
-        late->l = l; late->dz = dz; late->dwpred = dwpred; late->c = c;
+        late->l = l; late->dz = dz; late->dwpred = dwpred; late->c = c; late->wpred = wpred;
         late->started = false; late->marked = false;
         late->pending.store(true);
     } else {
@@ -1319,7 +1483,7 @@ int infonce_deferred_start(hipStream_t st)
     const NceLayout &l = side->l;
     CPC_TRY(infonce_deferred_mark(st));
     CPC_CHECK_HIP(hipStreamWaitEvent(side->stream, side->mid, 0));
-    CPC_TRY(nce_launch_gather(l, side->dz, side->late_fused, side->stream));
+    CPC_TRY(nce_launch_gather(l, side->c, side->wpred, side->dz, side->late_fused, side->stream));
     CPC_TRY(gemm_tn(l.dP, (long)l.K * l.Henc, side->c, l.Har, side->dwpred, l.Har, l.K * l.Henc, l.Har, (long)l.b * l.Pr, l.tn_late, l.tn_bytes, 0,
                     0, side->stream));
     CPC_CHECK_HIP(hipEventRecord(side->late, side->stream));
@@ -1411,9 +1575,17 @@ extern "C" size_t cpc_infonce_perm_offset(int b, int t, int k, int dim_ar, int d
 
 extern "C" size_t cpc_infonce_scratch_bytes(int b, int t, int k, int dim_ar, int dim_enc, int n_neg)
 {
+    // dim_ar > 0: enough for every entry point (the module-predictor ones keep the contribution rows).  dim_ar < 0: for
+    // cpc_infonce_forward / cpc_infonce_backward alone, context width -dim_ar -- without the contribution rows where their dz
+    // comes from per-row sums
+    const bool linear_only = dim_ar < 0;
+    if (linear_only) dim_ar = -dim_ar;
     cpc::NceLayout l;
     if (cpc::nce_layout(l, b, t, k, dim_ar, dim_enc, n_neg, nullptr, nullptr) != CPC_OK) return 0;
-    return l.scratch_bytes;
+    if (!cpc::nce_dz_q_wanted(b, t, k, dim_ar, dim_enc, n_neg)) return l.scratch_bytes;
+    const size_t rows_bytes = l.scratch_bytes;
+    if (cpc::nce_layout(l, b, t, k, dim_ar, dim_enc, n_neg, nullptr, nullptr, true) != CPC_OK) return 0;
+    return linear_only ? l.scratch_bytes : std::max(rows_bytes, l.scratch_bytes);
 }
 
 extern "C" int cpc_infonce_forward(const float *c, const float *z, const float *wpred, const int32_t *ext_idx, const float *weights,

@@ -393,6 +393,10 @@ int cpc_negidx_expand(const uint32_t *raw, int32_t *ext_idx, int batch, int seq_
  *           is identical from run to run)
  * ------------------------------------------------------------------------------------------ */
 size_t cpc_infonce_saved_bytes(int b, int t, int k, int dim_ar, int dim_enc, int n_neg);
+/* scratch: dim_ar > 0 gives what ANY entry point of the criterion may use (the module-predictor entries below keep one
+ * contribution row per candidate, 1.06 GB at the benchmark shape).  dim_ar < 0 (context width -dim_ar) gives what
+ * cpc_infonce_forward / cpc_infonce_backward ALONE need: where their dz comes from per-row context sums (the environment's
+ * CPC_NCE_DZ=q, read at every call; linear predictors, dim_enc and dim_ar 256 or 512) the contribution rows are not part of it. */
 size_t cpc_infonce_scratch_bytes(int b, int t, int k, int dim_ar, int dim_enc, int n_neg);
 /* byte offset, inside `saved`, of the logits the forward pass leaves there: float [b, W, K, 1 + n_neg], candidate 0 = the
  * positive, the negatives in slot order (cpc_infonce_perm_offset) -- what getPrediction (criterion.py:291-302) returns once
