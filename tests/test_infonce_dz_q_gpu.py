@@ -3,106 +3,20 @@ infonce_dz_q_kernel, dz = Q . wq^T; chosen with CPC_NCE_DZ=q) against the contri
 also the module predictors' path).  Every case runs the SAME inputs through both paths: dc, dP and dW_k are bit-identical (their
 kernels' arithmetic has not changed), dz is held to the fp64 oracle within TWICE the contribution-row path's own maximum element
 error on those inputs (the factor covers the extra rounding of the final product; the summation length is the same), z rows nobody
-refers to are exactly zero, and two launches give the same dz bit for bit.  H = 256 (once 512), K = 12."""
-import numpy as np
+refers to are exactly zero, and two launches give the same dz bit for bit.  H = 256 (once 512), K = 12.  The helpers, with a guard
+of 4096 bytes behind `saved` and `scratch` that no launch may touch, are in tests/infonce_dz_harness.py; the rest of the path's domain
+is in tests/test_infonce_dz_q_domain_gpu.py."""
 import pytest
 import torch
 
 import cpc2_amd
-from cpc2_amd import _lib
 from cpc2_amd.train import buildOptimizer, cpcStep
 from oracle import cpc_oracle as O
 from oracle import synth
+from tests.infonce_dz_harness import DEV, _check, _random_ext
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 K = 12
-
-
-def _random_ext(b, t_len, nn, seed, rows=None):
-    """Negatives in negative_indices' [b, n_neg, W] order (int64, flat), drawn uniformly from `rows` (default: every z row)."""
-    rs = np.random.RandomState(seed)
-    rows = np.arange(b * t_len) if rows is None else np.asarray(rows)
-    return rows[rs.randint(0, len(rows), size=(b, nn, t_len - K))].astype(np.int64)
-
-
-def _time_major(ext, b, w_len, nn):
-    return torch.as_tensor(np.asarray(ext).reshape(b, nn, w_len).transpose(0, 2, 1).copy(), dtype=torch.int32)
-
-
-def _inputs(b, t_len, h, seed):
-    cp = synth.predictor_params(K, h, h, seed=seed, scale=2.0)
-    wk = [cp[f"wPrediction.predictors.{i}.weight"] for i in range(K)]
-    return synth.features((b, t_len, h), seed + 1), synth.features((b, t_len, h), seed + 2, relu=True), wk
-
-
-def _backward(mode, monkeypatch, c, z, wk, ext, nn, weights, launches=1):
-    """cpc_infonce_forward + cpc_infonce_backward (immediate form, T context frames) with CPC_NCE_DZ = mode: dc, dz, dW, dP and the
-    dz of every further launch on the same inputs."""
-    monkeypatch.setenv("CPC_NCE_DZ", mode)
-    lib = _lib.load()
-    b, t_len, h = z.shape
-    w_len = t_len - K
-    cd, zd, wpred = c.to(DEV), z.to(DEV), torch.stack(wk).to(DEV)
-    ext_tm = _time_major(ext, b, w_len, nn).to(DEV)
-    wd = None if weights is None else weights.float().to(DEV)
-    dl = torch.linspace(0.5, 1.5, K).to(DEV)
-    st = _lib.stream_ptr(cd.device)
-    saved = torch.empty(lib.cpc_infonce_saved_bytes(b, t_len, K, h, h, nn), dtype=torch.uint8, device=DEV)
-    nscr = lib.cpc_infonce_scratch_bytes(b, t_len, K, -h, h, nn)          # (the linear entries' own need, path by path)
-    full = lib.cpc_infonce_scratch_bytes(b, t_len, K, h, h, nn)
-    assert 0 < nscr <= full
-    if mode == "q":
-        monkeypatch.setenv("CPC_NCE_DZ", "rows")
-        rows_bytes = lib.cpc_infonce_scratch_bytes(b, t_len, K, -h, h, nn)
-        monkeypatch.setenv("CPC_NCE_DZ", "q")
-        # the contribution rows [b W][16 + n_neg][H] are gone from it (Q, [b T][K][H], and the re-laid predictors take their place)
-        assert rows_bytes - nscr >= 4 * h * (b * w_len * (16 + nn) - b * t_len * K - K * h) - 4096
-    losses, acc = torch.empty(K, device=DEV), torch.empty(K, device=DEV)
-    outs = []
-    for _ in range(launches):
-        scr = torch.full((nscr,), 0xFF, dtype=torch.uint8, device=DEV)    # (NaN patterns: nothing may be read before it is written)
-        _lib.check(lib.cpc_infonce_forward(_lib.ptr(cd), _lib.ptr(zd), _lib.ptr(wpred), _lib.ptr(ext_tm), _lib.ptr(wd), _lib.ptr(losses),
-                                           _lib.ptr(acc), _lib.ptr(saved), _lib.ptr(scr), b, t_len, t_len, K, h, h, nn, st), "fwd")
-        dc, dz, dw = torch.full_like(cd, float("nan")), torch.full_like(zd, float("nan")), torch.full_like(wpred, float("nan"))
-        _lib.check(lib.cpc_infonce_backward(_lib.ptr(cd), _lib.ptr(zd), _lib.ptr(wpred), _lib.ptr(ext_tm), _lib.ptr(wd), _lib.ptr(dl),
-                                            _lib.ptr(saved), _lib.ptr(scr), _lib.ptr(dc), _lib.ptr(dz), _lib.ptr(dw), b, t_len, t_len, K, h, h,
-                                            nn, 0, st), "bwd")
-        torch.cuda.synchronize()
-        _lib.check(lib.cpc_async_error_check(st), "async errors")
-        # dP [b T][K H] sits behind the two [b W][K] loss / hit planes of the scratch layout (256-byte carves: nce_layout)
-        plane = -(-(b * w_len * K * 4) // 256) * 256
-        dp = scr[2 * plane:2 * plane + 4 * b * t_len * K * h].view(torch.float32).clone()
-        outs.append((dc, dz, dw, dp))
-    return outs
-
-
-def _check(monkeypatch, b, t_len, h, nn, ext, seed, weights=None):
-    """The checks of the module docstring for one set of inputs; returns the number of z rows without a reference."""
-    c, z, wk = _inputs(b, t_len, h, seed)
-    rows = _backward("rows", monkeypatch, c, z, wk, ext, nn, weights)[0]
-    new, again = _backward("q", monkeypatch, c, z, wk, ext, nn, weights, launches=2)
-    for name, a, bb in zip(("dc", "dz (unused)", "dW", "dP"), rows, new):
-        if name != "dz (unused)":
-            assert torch.equal(a, bb), f"{name} differs between the two dz paths"
-    assert torch.equal(new[1], again[1]), "dz differs between two launches on the same inputs"
-    ref = O.criterion_forward_sparse(c.double(), z.double(), [w.double() for w in wk], ext.reshape(-1), nn, weights=weights,
-                                     dlosses=torch.linspace(0.5, 1.5, K, dtype=torch.float64))
-    ref_dz = ref["dz"]
-    assert float(ref_dz.abs().max()) > 0
-    err_rows = float((rows[1].cpu().double() - ref_dz).abs().max())
-    err_new = float((new[1].cpu().double() - ref_dz).abs().max())
-    print(f"dz b{b} T{t_len} H{h} n{nn}: max element error rows path {err_rows:.3e}, per-row sums {err_new:.3e} "
-          f"(max |dz| {float(ref_dz.abs().max()):.3e})")
-    # rows nobody refers to: frame 0 of a window is no step's positive (the positive of step k at t is frame t + 1 + k)
-    referred = np.zeros(b * t_len, dtype=bool)
-    referred[np.asarray(ext).reshape(-1)] = True
-    referred.reshape(b, t_len)[:, 1:] = True
-    dead = torch.as_tensor(~referred)
-    for name, dz in (("rows", rows[1]), ("per-row sums", new[1])):
-        assert bool((dz.cpu().view(b * t_len, h)[dead] == 0).all()), f"{name}: a z row without a reference is not zero"
-    assert err_new <= 2.0 * err_rows, f"dz error {err_new:.3e} against the fp64 oracle exceeds twice the rows path's {err_rows:.3e}"
-    return int(dead.sum())
 
 
 def test_small_base_case(monkeypatch):
