@@ -163,6 +163,14 @@ SIGNATURES = {
     "cpc_seg_lds_entries": (c_int, []),
     "cpc_seg_dissimilarity": (c_int, [c_ptr, c_long, c_long, c_int, c_ptr, c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr]),
     "cpc_seg_boundaries": (c_int, [c_ptr, c_long, c_ptr, c_ptr, c_int, c_ptr, c_int, c_ptr, c_long, c_ptr, c_ptr, c_ptr, c_int] + [c_ptr] * 7),
+    "cpc_unit_counts_lds_cells": (c_int, []),
+    "cpc_unit_counts_chunk": (c_int, []),
+    "cpc_unit_counts_scratch_bytes": (c_size_t, [c_int]),
+    "cpc_unit_counts": (c_int, [c_ptr, c_long, c_ptr, c_ptr, c_long, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr,
+                                c_ptr, c_ptr, c_size_t, c_ptr]),
+    "cpc_unit_boundaries_scratch_bytes": (c_size_t, [c_int, c_long]),
+    "cpc_unit_boundaries": (c_int, [c_ptr, c_long, c_ptr, c_ptr, c_long, c_ptr, c_ptr, c_int, c_long, c_int, c_ptr, c_ptr, c_size_t,
+                                    c_ptr]),
 }
 
 _lib = None

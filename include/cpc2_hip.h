@@ -61,7 +61,9 @@ int cpc_version(void);          /* 100 x major + minor; 105 = the entry points o
                                   * cpc_ctc_loss_scratch_bytes of the same sizes, and cpc_probe_ctc needs b <= 65535;
                                   * 123 = cpc_augment_pitch;
                                   * 124 = cpc_seg_dissimilarity / cpc_seg_boundaries / cpc_seg_lds_entries;
-                                  * 125 = cpc_augment_freeverb */
+                                  * 125 = cpc_augment_freeverb;
+                                  * 126 = cpc_unit_counts / cpc_unit_boundaries (+ scratch queries) / cpc_unit_counts_lds_cells /
+                                  * cpc_unit_counts_chunk */
 const char *cpc_last_error(void);
 
 /* In-situ kernel timing for bench.py: when enabled, the launchers bracket each launch of the named
@@ -998,6 +1000,60 @@ int cpc_seg_boundaries(const double *d, long total_rows, const int64_t *offsets,
                        const double *thresholds, int k, const int *ref /* may be NULL */, long total_ref, const int64_t *ref_offsets,
                        const int *ref_counts, const int *hyp_limit /* may be NULL */, int tol, int *n_peaks, int *peak_pos,
                        double *peak_prom, double *range, int *counts, int *status, cpc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Quantized units against frame-level phone labels (csrc/unit_scores.hip; cpc2_amd/unit_scores.py).
+ * version 126.  Every pointer is a DEVICE pointer.  The reference has no counterpart: the definition below is the specification.
+ * All inputs and outputs are integers and integer sums do not depend on their order: every output EQUALS the definition, bit
+ * for bit, on every launch.
+ *
+ * Utterance i compares L = lengths[i] frames (int32; a value <= 0 compares nothing): the unit of frame f is
+ * units[unit_off[i] + f] and its label labels[label_off[i] + f] (int32 packs of n_unit_words and n_label_words words, int64
+ * offsets).  The packs are separate because a unit line and a label line of one utterance may differ by a frame or two: the caller
+ * passes the common length.  The packs may have gaps and the utterances any order; words outside [off, off + L) are never read.
+ * labels == NULL: every frame has label 0 and n_phones must be 1.  An utterance whose frames leave a pack (offset < 0 or
+ * offset + L beyond the pack) is not read at all: cpc_unit_counts adds its L frames to `invalid`, cpc_unit_boundaries writes five
+ * times -1 for it.
+ * cpc_unit_counts ADDS into caller-zeroed tables, so that a corpus goes through in batches:
+ *   joint [n_units][n_phones] (int64)  frames with that (unit, phone)
+ *   unit_runs [n_units] (int64)        frames f with f == 0 or units[f] != units[f-1], by units[f]: a run never continues across
+ *                                      an utterance boundary
+ *   phone_runs [n_phones] (int64)      the same for the labels
+ *   invalid [1] (int64)                frames whose unit is outside [0, n_units) or whose label is outside [0, n_phones): such a
+ *                                      frame is counted nowhere else and never used as an index (the frame behind it still
+ *                                      compares itself with it)
+ *   form: 0 = chosen from the shape alone: 1 (the whole table in LDS as 32-bit words, flushed once per workgroup) when
+ *   n_units * n_phones <= cpc_unit_counts_lds_cells() = 16384, else 2 (64-bit atomics on the table in global memory); 1 or 2 force
+ *   a form (1 is refused for a table that does not fit).  Equal cells on adjacent lanes can be folded into one add of their
+ *   number: the global form does that and the LDS form does not, which is what was measured to be faster;
+ *   + 4 forces no folding, + 8 forces folding (for measurements; same outputs).  The run-start tables live in LDS in both forms.  The table and the run words are dynamic LDS
+ *   sized by the shape, at most 132 KiB of the 160 KiB a gfx950 workgroup may take.  The work is cut into chunks of
+ *   cpc_unit_counts_chunk() = 4096 compared frames of the concatenated utterances, whatever their lengths.
+ *   scratch: cpc_unit_counts_scratch_bytes(n_utt) (the prefix of the lengths; 0 with a message for n_utt outside the limits);
+ *   too little gives CPC_ERR_WORKSPACE.
+ * cpc_unit_boundaries OVERWRITES out [n_utt][5] (int32) = (n_ref, n_hyp, hits, hyp_near, ref_near) at one tolerance tol in frames:
+ *   hypotheses are the frames f in [1, L - 1] with units[f] != units[f-1], references the same for the labels (none when labels ==
+ *   NULL); hits = the one-to-one matching by two pointers over the two sorted lists (a pair within tol is a hit and advances both,
+ *   otherwise the smaller frame advances); hyp_near = hypotheses with a reference within tol, ref_near = references with a
+ *   hypothesis within tol.  L <= 1: five zeros.  One wave per utterance; the matching is cpc_seg_boundaries', kept as a second copy
+ *   so that segment.hip's code does not move.  total_frames: at least the sum of the lengths (it sizes the two lists in scratch;
+ *   an utterance whose lists would not fit gets five times -1).  scratch: cpc_unit_boundaries_scratch_bytes(n_utt, total_frames).
+ * Limits: 0 <= n_utt <= 2^20 (n_utt == 0: nothing is done, CPC_OK), 1 <= n_units <= 16384, 1 <= n_phones <= 1024, 0 <= tol <= 2^30,
+ *   pack sizes and total_frames >= 0; those, labels == NULL with n_phones != 1 and a NULL pointer where one is required are
+ *   CPC_ERR_INVALID with a message naming the entry point, before any launch, nothing written.
+ *   No float atomic, no floating point at all.
+ * ------------------------------------------------------------------------------------------ */
+int cpc_unit_counts_lds_cells(void);
+int cpc_unit_counts_chunk(void);
+size_t cpc_unit_counts_scratch_bytes(int n_utt);
+int cpc_unit_counts(const int *units, long n_unit_words, const int64_t *unit_off, const int *labels /* may be NULL */,
+                    long n_label_words, const int64_t *label_off, const int *lengths, int n_utt, int n_units, int n_phones, int form,
+                    int64_t *joint, int64_t *unit_runs, int64_t *phone_runs, int64_t *invalid, void *scratch, size_t scratch_bytes,
+                    cpc_stream_t stream);
+size_t cpc_unit_boundaries_scratch_bytes(int n_utt, long total_frames);
+int cpc_unit_boundaries(const int *units, long n_unit_words, const int64_t *unit_off, const int *labels /* may be NULL */,
+                        long n_label_words, const int64_t *label_off, const int *lengths, int n_utt, long total_frames, int tol,
+                        int *out, void *scratch, size_t scratch_bytes, cpc_stream_t stream);
 
 #ifdef __cplusplus
 }
