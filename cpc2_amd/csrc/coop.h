@@ -141,4 +141,143 @@ template <typename K> static inline bool coop_fits(K kernel, unsigned grid, int 
     return per_cu >= 1 && (int)grid <= n_cus;   // one workgroup per CU is what the grouping assumes
 }
 
+// ---- the hand-off ---------------------------------------------------------------------------------------------------
+// The members of a group exchange a step's results through 8-byte {epoch, value} granules in L2: one relaxed agent-scope
+// store each, polled with relaxed agent-scope loads (MI355X guide, Guideline 16 R2).  A member can be at most one step
+// ahead of another, so two granule sets (epoch parity) suffice.  Every spin is bounded: on time-out the thread poisons
+// what it hands on with NaN, reports, and never waits again.  This is the only place that stores, loads or waits for a
+// granule; the kernels of gru.hip and lstm.hip say where a value comes from and where it goes.
+// What the functions need of a launch (comm, epoch, err) they take as scalars, and the thread's `dead` flag goes in and
+// comes back by value.  Handed over by reference -- the argument struct, a flag the callee sets -- the compiler finds
+// them a pass later than the kernels' own locals and makes other code of the same text.  Measured at this change
+// (gfx950, -Rpass-analysis=kernel-resource-usage; VGPRs by value, as here and as with the hand-off written out in the
+// kernel, against `bool &dead`):  lstm_bwd_coop_kernel<512,1> 227 / 228, <512,2> 229 / 230, <512,4> 228 / 229,
+// lstm_fwd_coop_kernel<256,8> 198 / 199, gru_fwd_coop_kernel<256,8> 193 / 194; and with `bool &dead` every poll of one to
+// three granules came out unrolled eight times (lstm_fwd_coop_kernel<256,1>: 772 instructions -> 868, eight s_sleep).
+
+// what a cooperative kernel is launched with (recurrent.h fills it in): the cell's own arguments and the hand-off's
+template <typename Args> struct CoopArgs {
+    Args g;
+    gu64_t *comm;          // granules (coop_comm_acquire: the library's own buffer): fwd [groups][2][G][U][NB] (coop_fwd_slot), bwd [groups][2][G][NB][H]
+    unsigned epoch0;       // this launch's epochs are epoch0 + 1 .. epoch0 + T: no granule of an earlier launch carries one of them
+    int groups, xcd_map;
+    int *err;              // host-visible error word, or nullptr
+    int fault;             // tests: member 0 of group 0 withholds its publish of step 1
+};
+
+__device__ __forceinline__ float coop_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
+
+__device__ __forceinline__ void coop_publish(gu64_t *granule, unsigned epoch, float v)
+{
+    __hip_atomic_store((COOP_GLOBAL gu64_t *)granule, ((gu64_t)epoch << 32) | (gu64_t)__float_as_uint(v), __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The one bounded wait: until all N granules carry `epoch`.  They are loaded together -- one L2 round trip per attempt,
+// not N in a row -- and x[] holds what was loaded last.  Returns the thread's new `dead`: true when the wait ran out, now
+// (the code is reported) or at an earlier step -- a dead thread never waits again, and the caller poisons what it derives
+// from x.  N is a compile-time constant and every loop is unrolled: slot and x stay in registers.
+template <int N>
+__device__ __forceinline__ bool coop_poll(COOP_GLOBAL gu64_t *const (&slot)[N], unsigned epoch, gu64_t (&x)[N], bool dead, int *err,
+                                          int code)
+{
+    constexpr unsigned BOUND = 1u << 22;
+    unsigned spins = dead ? BOUND : 0u;
+    for (;;) {
+        bool ready = true;
+#pragma unroll
+        for (int i = 0; i < N; ++i) x[i] = __hip_atomic_load(slot[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+        for (int i = 0; i < N; ++i) ready = ready && (unsigned)(x[i] >> 32) == epoch;
+        if (ready) break;
+        if (++spins > BOUND) { dead = true; coop_report(err, code); break; }
+        __builtin_amdgcn_s_sleep(1);
+    }
+    return dead;
+}
+
+// Forward, the lane that finishes (window q, unit u) of step t: publish the new h into set `nxt` under the step's epoch
+// (epoch0 + t + 1, formed by the caller, as the backward kernels form theirs: formed in here from epoch0 and t, the same
+// arithmetic scheduled differently and gru_fwd's in-situ class time at CPC-large read 0.826-0.835 ms in five alternating
+// runs against the parent's 0.801-0.834; formed by the caller, 0.807-0.821).  Padding windows
+// (!mine) publish 0, so that every granule of the epoch gets written.  Call it BEFORE the saved activations are stored:
+// the other members wait for this store, nobody waits for those.
+template <int H, int NB>
+__device__ __forceinline__ void coop_fwd_publish(gu64_t *comm, unsigned epoch, int fault, int group, int nxt, int member, int u, int q,
+                                                 int t, bool mine, float hv)
+{
+    if (!(fault && group == 0 && member == 0 && t == 1))
+        coop_publish(comm + coop_fwd_slot<H, NB>(group, nxt, member, u, q), epoch, mine ? hv : 0.f);
+}
+
+// Forward, all threads: gather the whole new h of the step with this epoch (all members) from set `nxt`; sink(window, k, value) puts it
+// into the other LDS buffer, NaN where the wait ran out.  Returns the new `dead`, which stays with the thread that timed
+// out.  A thread takes the granules tid, tid + 512, .. of the set: memory order, coalesced.  The caller's
+// coop_lds_barrier() follows.
+template <int H, int NB, typename Sink>
+__device__ __forceinline__ bool coop_fwd_gather(gu64_t *comm, unsigned epoch, int *err, int group, int nxt, bool dead,
+                                                Sink &&sink)
+{
+    constexpr int KP = NB * H / 512 > 0 ? NB * H / 512 : 1;          // granules gathered per thread and step
+    const int tid = threadIdx.x;
+    if (tid < NB * H) {
+        COOP_GLOBAL gu64_t *slot[KP];
+#pragma unroll
+        for (int i = 0; i < KP; ++i)
+            slot[i] = (COOP_GLOBAL gu64_t *)(comm + ((long)group * 2 + nxt) * (NB * H) + (tid + 512 * i));
+        gu64_t x[KP];
+        dead = coop_poll(slot, epoch, x, dead, err, COOP_ERR_FWD_WAIT);
+#pragma unroll
+        for (int i = 0; i < KP; ++i) {
+            int window, k;
+            coop_fwd_who<H, NB>(tid + 512 * i, window, k);
+            sink(window, k, dead ? NAN : __uint_as_float((unsigned)x[i]));
+        }
+    }
+    return dead;
+}
+
+// Backward granules: [group][set][sender][window][H]; the first granule of a window's row
+template <int H, int NB> __device__ __forceinline__ long coop_bwd_row(int group, int par, int sender, int s)
+{
+    return ((((long)group * 2 + par) * CoopCfg<H>::G + sender) * NB + s) * H;
+}
+
+// Backward, all threads: publish the columns of this member's partial W_hh^T dG that other members own (its own stay in
+// LDS); column(s, k) reads one of them.
+template <int H, int NB, typename Column>
+__device__ __forceinline__ void coop_bwd_publish(gu64_t *comm, unsigned epoch, int group, int par, int member, bool dead,
+                                                 Column &&column)
+{
+    for (int idx = threadIdx.x; idx < NB * H; idx += 512) {
+        const int s = idx / H, k = idx - s * H;
+        if (k / CoopCfg<H>::U == member) continue;
+        const float v = column(s, k);
+        coop_publish(comm + coop_bwd_row<H, NB>(group, par, member, s) + k, epoch, dead ? NAN : v);
+    }
+}
+
+// Backward, the elementwise thread of (window es, column ej): wait for the G - 1 partners' pieces and add them to `sum`
+// (the thread's own part), in the order they are polled.  Returns the new `dead`; the caller poisons its carry with it.
+// `sum` comes in holding the caller's own terms and the pieces are added ONTO it, one by one: float addition does not
+// associate, and ((own + x0) + x1) + .. is the order the carry has always been summed in -- returning x0 + x1 + .. for
+// the caller to add would change its last bits.
+// No barrier is needed behind this: the kernels rewrite dgs before the next step's first barrier and part after it, and
+// every thread has finished reading both when it gets there.
+template <int H, int NB>
+__device__ __forceinline__ bool coop_bwd_collect(gu64_t *comm, unsigned epoch, int *err, int group, int par, int member, int es, int ej,
+                                                 bool dead, float &sum)
+{
+    constexpr int G = CoopCfg<H>::G;
+    COOP_GLOBAL gu64_t *slot[G - 1];
+#pragma unroll
+    for (int d = 1; d < G; ++d)
+        slot[d - 1] = (COOP_GLOBAL gu64_t *)(comm + coop_bwd_row<H, NB>(group, par, (member + d) & (G - 1), es) + ej);
+    gu64_t x[G - 1];
+    dead = coop_poll(slot, epoch, x, dead, err, COOP_ERR_BWD_WAIT);
+#pragma unroll
+    for (int d = 0; d < G - 1; ++d) sum += __uint_as_float((unsigned)x[d]);
+    return dead;
+}
+
 }  // namespace cpc

@@ -42,8 +42,6 @@ __global__ void gru_pack_bwd_kernel(const float *w, float4 *wb, int H)
     }
 }
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
-
 struct GruArgs {
     const float *gi;      // [N*T][3H]   input projections incl. b_ih
     const float4 *wpack;  // packed W_hh
@@ -62,6 +60,33 @@ struct GruArgs {
     float *dgi;           // [N*T][3H]
     float *dgh;           // [N][T+1][3H], row T zero
 };
+
+// ---- the cell, once: every forward kernel finishes a (window, unit) pair with gru_gates, every backward kernel starts one
+// with gru_grad; the kernels differ in how they form the products with W_hh
+struct GruGates { float r, z, c, hv; };
+// gi: the input projections (b_ih included), g: W_h. h + b_h. of the three gates
+__device__ __forceinline__ GruGates gru_gates(float gi0, float gi1, float gi2, float g0, float g1, float g2, float hprev)
+{
+    GruGates v;
+    v.r = coop_sigmoid(gi0 + g0);
+    v.z = coop_sigmoid(gi1 + g1);
+    v.c = tanhf(gi2 + v.r * g2);
+    v.hv = (1.f - v.z) * v.c + v.z * hprev;
+    return v;
+}
+struct GruGrad { float dpr, dpz, dpn, dhn, keep; };      // d pre-activations (dhn: of W_hn h + b_hn), keep = dh z
+__device__ __forceinline__ GruGrad gru_grad(float dh, float r, float z, float c, float hnv, float hp_)
+{
+    GruGrad d;
+    const float dc = dh * (1.f - z);
+    const float dz = dh * (hp_ - c);
+    d.dpn = dc * (1.f - c * c);
+    d.dpr = d.dpn * hnv * r * (1.f - r);
+    d.dpz = dz * z * (1.f - z);
+    d.dhn = d.dpn * r;
+    d.keep = dh * z;
+    return d;
+}
 
 // One workgroup per window; thread (j, q): hidden unit j, K slice q.  The K split puts kq x more waves
 // (and W_hh loads) in flight per CU: the step time is the L2 -> CU stream of W_hh (3H*H*4 bytes).
@@ -115,17 +140,14 @@ __global__ void gru_fwd_kernel(GruArgs a)
             }
             const long row = (long)n * T + t;
             const float *g = a.gi + row * 3 * H;
-            const float r = sigmoidf_(g[j] + g0);
-            const float z = sigmoidf_(g[H + j] + g1);
-            const float c = tanhf(g[2 * H + j] + r * g2);
-            const float hv = (1.f - z) * c + z * hprev;
+            const GruGates v = gru_gates(g[j], g[H + j], g[2 * H + j], g0, g1, g2, hprev);
             float *gs = a.gates + row * 3 * H;
-            gs[j] = r; gs[H + j] = z; gs[2 * H + j] = c;
+            gs[j] = v.r; gs[H + j] = v.z; gs[2 * H + j] = v.c;
             a.hn[row * H + j] = g2;
-            a.out[row * H + j] = hv;
-            a.hall[((long)n * (T + 1) + t + 1) * H + j] = hv;
-            hs[j] = hv;
-            hprev = hv;
+            a.out[row * H + j] = v.hv;
+            a.hall[((long)n * (T + 1) + t + 1) * H + j] = v.hv;
+            hs[j] = v.hv;
+            hprev = v.hv;
         }
         __syncthreads();
     }
@@ -157,20 +179,13 @@ __global__ void gru_bwd_kernel(GruArgs a)
             const float dh = a.dout[row * H + j] + carry;
             const float *gs = a.gates + row * 3 * H;
             const float r = gs[j], z = gs[H + j], c = gs[2 * H + j];
-            const float hnv = a.hn[row * H + j];
-            const float hp_ = a.hall[((long)n * (T + 1) + t) * H + j];
-            const float dc = dh * (1.f - z);
-            const float dz = dh * (hp_ - c);
-            const float dpn = dc * (1.f - c * c);
-            const float dpr = dpn * hnv * r * (1.f - r);
-            const float dpz = dz * z * (1.f - z);
-            const float dhn = dpn * r;
-            keep = dh * z;
+            const GruGrad d = gru_grad(dh, r, z, c, a.hn[row * H + j], a.hall[((long)n * (T + 1) + t) * H + j]);
+            keep = d.keep;
             float *gi = a.dgi + row * 3 * H;
-            gi[j] = dpr; gi[H + j] = dpz; gi[2 * H + j] = dpn;
+            gi[j] = d.dpr; gi[H + j] = d.dpz; gi[2 * H + j] = d.dpn;
             float *gh = a.dgh + ((long)n * (T + 1) + t) * 3 * H;
-            gh[j] = dpr; gh[H + j] = dpz; gh[2 * H + j] = dhn;
-            dg[j] = dpr; dg[H + j] = dpz; dg[2 * H + j] = dhn;
+            gh[j] = d.dpr; gh[H + j] = d.dpz; gh[2 * H + j] = d.dhn;
+            dg[j] = d.dpr; dg[H + j] = d.dpz; dg[2 * H + j] = d.dhn;
         }
         __syncthreads();
         if (act) {
@@ -200,24 +215,14 @@ __global__ void gru_bwd_kernel(GruArgs a)
 // threads each, one per CU) shares NB windows; every thread holds 96 weights: thread (u, q) = unit u of the member's
 // U units, K slice q of 32 columns, 3 gates.  H = 256: 8 slices, U = 64, G = 4;  H = 512: 16 slices, U = 32, G = 16.
 // Per step every member multiplies its slice by the full h (LDS), finishes the K reduction with wave shuffles,
-// applies the gates for its U units and publishes them; the members exchange the new h through 8-byte
-// {epoch, value} granules in L2 (one sc1 store each, polled with relaxed agent-scope loads: MI355X guide,
-// Guideline 16 R2).  A member can be at most one step ahead of another, so two granule sets (epoch parity)
-// suffice.  Every spin is bounded: on time-out the workgroup poisons its outputs with NaN and leaves.
-struct GruCoopArgs {
-    GruArgs g;
-    gu64_t *comm;          // granules (coop_comm_acquire: the library's own buffer): fwd [groups][2][G][U][NB] (coop_fwd_slot), bwd [groups][2][G][NB][H]
-    unsigned epoch0;       // this launch's epochs are epoch0 + 1 .. epoch0 + T: no granule of an earlier launch carries one of them
-    int groups, xcd_map;
-    int *err;              // host-visible error word (coop.h), or nullptr
-    int fault;             // tests: member 0 of group 0 withholds its publish of step 1
-};
+// applies the gates for its U units and publishes them; the members exchange the new h through the granules of
+// coop.h ("the hand-off": coop_fwd_publish / coop_fwd_gather, backward coop_bwd_publish / coop_bwd_collect).
+using GruCoopArgs = CoopArgs<GruArgs>;
 
 template <int H, int NB> __global__ __launch_bounds__(512) void gru_fwd_coop_kernel(GruCoopArgs ca)
 {
     using C = CoopCfg<H>;
     constexpr int QS = C::QS, U = C::U, G = C::G;
-    constexpr int KP = NB * H / 512 > 0 ? NB * H / 512 : 1;          // granules gathered per thread and step
     static_assert(NB <= QS, "one finishing lane per window");
     __shared__ __attribute__((aligned(16))) float hs[2][NB][C::LDH];
     const GruArgs &a = ca.g;
@@ -286,58 +291,24 @@ template <int H, int NB> __global__ __launch_bounds__(512) void gru_fwd_coop_ker
             for (int s = 0; s < NB; ++s)
                 if (s == q) { g0 = acc[s][0]; g1 = acc[s][1]; g2 = acc[s][2]; }
             g0 += bh0; g1 += bh1; g2 += bh2;
-            const float hp = hs[cur][q][coop_pad(j)];
-            const float r = sigmoidf_(gi0 + g0);
-            const float z = sigmoidf_(gi1 + g1);
-            const float c = tanhf(gi2 + r * g2);
-            float hv = (1.f - z) * c + z * hp;
-            if (dead) hv = NAN;
-            // publish first (also for padding windows, so that every granule of the epoch gets written): the other
-            // members wait for this store, nobody waits for the saved activations below
-            COOP_GLOBAL gu64_t *slot = (COOP_GLOBAL gu64_t *)(ca.comm + coop_fwd_slot<H, NB>(group, nxt, member, u, q));
-            if (!(ca.fault && group == 0 && member == 0 && t == 1))
-                __hip_atomic_store(slot, ((gu64_t)(ca.epoch0 + (unsigned)(t + 1)) << 32) | (gu64_t)__float_as_uint(mine ? hv : 0.f),
-                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const GruGates v = gru_gates(gi0, gi1, gi2, g0, g1, g2, hs[cur][q][coop_pad(j)]);
+            const float hv = dead ? NAN : v.hv;
+            // publish first: the other members wait for this store, nobody waits for the saved activations below
+            coop_fwd_publish<H, NB>(ca.comm, ca.epoch0 + (unsigned)(t + 1), ca.fault, group, nxt, member, u, q, t, mine,
+                                    hv);
             if (mine) {
                 const long row = (long)ns * T + t;
                 float *gs = a.gates + row * 3 * H;
-                gs[j] = r; gs[H + j] = z; gs[2 * H + j] = c;
+                gs[j] = v.r; gs[H + j] = v.z; gs[2 * H + j] = v.c;
                 a.hn[row * H + j] = g2;
                 a.out[row * H + j] = hv;
                 a.hall[((long)ns * (T + 1) + t + 1) * H + j] = hv;
             }
         }
-        // gather the whole new h (all members) into the other LDS buffer; a thread's KP granules are polled together
-        // (one L2 round trip per attempt, not KP in a row)
         if (t + 1 < T) {
-            COOP_GLOBAL gu64_t *slot[KP];
-#pragma unroll
-            for (int i = 0; i < KP; ++i) {
-                const int idx = tid + 512 * i;
-                slot[i] = (COOP_GLOBAL gu64_t *)(ca.comm + ((long)group * 2 + nxt) * (NB * H) + idx);      // memory order: coalesced
-            }
-            gu64_t x[KP];
-            unsigned spins = dead ? (1u << 22) : 0u;            // once timed out, never wait again
-            if (tid < NB * H) {
-                for (;;) {
-                    bool ready = true;
-#pragma unroll
-                    for (int i = 0; i < KP; ++i) x[i] = __hip_atomic_load(slot[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-                    for (int i = 0; i < KP; ++i) ready = ready && (unsigned)(x[i] >> 32) == ca.epoch0 + (unsigned)(t + 1);
-                    if (ready) break;
-                    if (++spins > (1u << 22)) { dead = true; coop_report(ca.err, COOP_ERR_FWD_WAIT); break; }
-                    __builtin_amdgcn_s_sleep(1);
-                }
-#pragma unroll
-                for (int i = 0; i < KP; ++i) {
-                    const int idx = tid + 512 * i;
-                    int gw, gk;
-                    coop_fwd_who<H, NB>(idx, gw, gk);
-                    hs[nxt][gw][coop_pad(gk)] = dead ? NAN : __uint_as_float((unsigned)x[i]);
-                }
-            }
-            coop_lds_barrier();            // `dead` stays with the thread that timed out: what it gathered is poisoned above
+            dead = coop_fwd_gather<H, NB>(ca.comm, ca.epoch0 + (unsigned)(t + 1), ca.err, group, nxt, dead,
+                                          [&](int window, int k, float h) { hs[nxt][window][coop_pad(k)] = h; });
+            coop_lds_barrier();
         }
     }
     if (a.hlast != nullptr && q < NB && n0 + q < a.N)
@@ -370,6 +341,25 @@ __device__ __forceinline__ void split3(float v, unsigned short (&t)[3])
     v -= __uint_as_float((unsigned)t[1] << 16);
     t[2] = bf16_rne(v);
 }
+// eight f32 weights, consecutive in K -> the B operand of each of their three bf16 terms
+__device__ __forceinline__ void mfma_pack(const float (&v)[8], MfmaFrag (&w)[3])
+{
+    unsigned short t[8][3];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) split3(v[e], t[e]);
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl)
+#pragma unroll
+        for (int d = 0; d < 4; ++d) w[pl].d[d] = (unsigned)t[2 * d][pl] | ((unsigned)t[2 * d + 1][pl] << 16);
+}
+// the four products of one K step (the note above) into one accumulator: a1 = [x0 | x1], a2 = [x0 | x2], a3 = [x2 | 0]
+__device__ __forceinline__ f32x4_t mfma_kstep(bf16x8_t a1, bf16x8_t a2, bf16x8_t a3, const MfmaFrag (&w)[3], f32x4_t acc)
+{
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, __builtin_bit_cast(bf16x8_t, w[0]), acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, __builtin_bit_cast(bf16x8_t, w[1]), acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, __builtin_bit_cast(bf16x8_t, w[2]), acc, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a3, __builtin_bit_cast(bf16x8_t, w[0]), acc, 0, 0, 0);
+}
 
 template <int H> struct MfmaCfg {
     using C = CoopCfg<H>;
@@ -386,7 +376,6 @@ template <int H, int NB> __global__ __launch_bounds__(512) void gru_fwd_mfma_ker
     using C = CoopCfg<H>;
     using M = MfmaCfg<H>;
     constexpr int QS = C::QS, U = C::U, G = C::G;
-    constexpr int KP = NB * H / 512 > 0 ? NB * H / 512 : 1;
     constexpr int LDK = M::LDK;
     static_assert(NB <= 8 && NB <= QS, "eight windows fill half the rows of a 16-row tile");
     __shared__ __attribute__((aligned(16))) unsigned short hp[2][3][8][LDK];     // the three terms of h, two steps
@@ -418,13 +407,7 @@ template <int H, int NB> __global__ __launch_bounds__(512) void gru_fwd_mfma_ker
             const float4 v0 = *reinterpret_cast<const float4 *>(a.whh + row + k);
             const float4 v1 = *reinterpret_cast<const float4 *>(a.whh + row + k + 4);
             const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-            unsigned short t[8][3];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) split3(v[e], t[e]);
-#pragma unroll
-            for (int pl = 0; pl < 3; ++pl)
-#pragma unroll
-                for (int d = 0; d < 4; ++d) bw[i][ks][pl].d[d] = (unsigned)t[2 * d][pl] | ((unsigned)t[2 * d + 1][pl] << 16);
+            mfma_pack(v, bw[i][ks]);
         }
     }
     const float bh0 = a.bhh[j], bh1 = a.bhh[H + j], bh2 = a.bhh[2 * H + j];
@@ -483,12 +466,7 @@ template <int H, int NB> __global__ __launch_bounds__(512) void gru_fwd_mfma_ker
             const bf16x8_t a2 = *reinterpret_cast<const bf16x8_t *>(pa2 + kb);
             const bf16x8_t a3 = *reinterpret_cast<const bf16x8_t *>(pa3 + (upper ? 0 : kb));
 #pragma unroll
-            for (int i = 0; i < 3; ++i) {                                               // three independent accumulator chains
-                acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, __builtin_bit_cast(bf16x8_t, bw[i][ks][0]), acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, __builtin_bit_cast(bf16x8_t, bw[i][ks][1]), acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, __builtin_bit_cast(bf16x8_t, bw[i][ks][2]), acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a3, __builtin_bit_cast(bf16x8_t, bw[i][ks][0]), acc[i], 0, 0, 0);
-            }
+            for (int i = 0; i < 3; ++i) acc[i] = mfma_kstep(a1, a2, a3, bw[i][ks], acc[i]);    // three independent accumulator chains
         }
         // lane: column lane % 16, rows 4 (lane / 16) .. + 3 of unit (tile, kpart)
 #pragma unroll
@@ -508,58 +486,85 @@ template <int H, int NB> __global__ __launch_bounds__(512) void gru_fwd_mfma_ker
                 gs[g] = v;
             }
             const float g0 = gs[0] + bh0, g1 = gs[1] + bh1, g2 = gs[2] + bh2;
-            const float r = sigmoidf_(gi0 + g0);
-            const float z = sigmoidf_(gi1 + g1);
-            const float c = tanhf(gi2 + r * g2);
-            float hv = (1.f - z) * c + z * hprev;
-            if (dead) hv = NAN;
-            hprev = hv;
-            COOP_GLOBAL gu64_t *slot = (COOP_GLOBAL gu64_t *)(ca.comm + coop_fwd_slot<H, NB>(group, nxt, member, u, q));
-            if (!(ca.fault && group == 0 && member == 0 && t == 1))
-                __hip_atomic_store(slot, ((gu64_t)(ca.epoch0 + (unsigned)(t + 1)) << 32) | (gu64_t)__float_as_uint(mine ? hv : 0.f),
-                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const GruGates v = gru_gates(gi0, gi1, gi2, g0, g1, g2, hprev);
+            hprev = dead ? NAN : v.hv;
+            // before the stores
+            coop_fwd_publish<H, NB>(ca.comm, ca.epoch0 + (unsigned)(t + 1), ca.fault, group, nxt, member, u, q, t, mine,
+                                    hprev);
             if (mine) {
                 const long row = (long)ns * T + t;
                 float *gsv = a.gates + row * 3 * H;
-                gsv[j] = r; gsv[H + j] = z; gsv[2 * H + j] = c;
+                gsv[j] = v.r; gsv[H + j] = v.z; gsv[2 * H + j] = v.c;
                 a.hn[row * H + j] = g2;
-                a.out[row * H + j] = hv;
-                a.hall[((long)ns * (T + 1) + t + 1) * H + j] = hv;
+                a.out[row * H + j] = hprev;
+                a.hall[((long)ns * (T + 1) + t + 1) * H + j] = hprev;
             }
         }
         if (t + 1 < T) {
-            COOP_GLOBAL gu64_t *slot[KP];
+            dead = coop_fwd_gather<H, NB>(ca.comm, ca.epoch0 + (unsigned)(t + 1), ca.err, group, nxt, dead,
+                                          [&](int window, int k, float h) {
+                unsigned short tt[3];
+                split3(h, tt);
 #pragma unroll
-            for (int i = 0; i < KP; ++i)
-                slot[i] = (COOP_GLOBAL gu64_t *)(ca.comm + ((long)group * 2 + nxt) * (NB * H) + tid + 512 * i);
-            gu64_t x[KP];
-            unsigned spins = dead ? (1u << 22) : 0u;
-            if (tid < NB * H) {
-                for (;;) {
-                    bool ready = true;
-#pragma unroll
-                    for (int i = 0; i < KP; ++i) x[i] = __hip_atomic_load(slot[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-                    for (int i = 0; i < KP; ++i) ready = ready && (unsigned)(x[i] >> 32) == ca.epoch0 + (unsigned)(t + 1);
-                    if (ready) break;
-                    if (++spins > (1u << 22)) { dead = true; coop_report(ca.err, COOP_ERR_FWD_WAIT); break; }
-                    __builtin_amdgcn_s_sleep(1);
-                }
-#pragma unroll
-                for (int i = 0; i < KP; ++i) {
-                    int gw, gk;
-                    coop_fwd_who<H, NB>(tid + 512 * i, gw, gk);
-                    unsigned short tt[3];
-                    split3(dead ? NAN : __uint_as_float((unsigned)x[i]), tt);
-#pragma unroll
-                    for (int pl = 0; pl < 3; ++pl) hp[nxt][pl][gw][gk] = tt[pl];
-                }
-            }
+                for (int pl = 0; pl < 3; ++pl) hp[nxt][pl][window][k] = tt[pl];
+            });
             coop_lds_barrier();
         }
     }
     if (a.hlast != nullptr && q < NB && n0 + q < a.N) a.hlast[(long)(n0 + q) * H + j] = hprev;
 }
+
+// The elementwise role of the cooperative backward kernels: thread (es, eu), tid < NB * U, turns dh of window n0 + es,
+// unit ej = member * U + eu into the step's d pre-activations.  The saved activations of step t - 1 are requested while
+// step t runs (p_*: same reason as the forward kernels' gi -- no L2/HBM round trip on a step's serial path).
+template <int H, int NB> struct GruBwdRole {
+    static constexpr int U = CoopCfg<H>::U;
+    int es, eu, ej, en;
+    bool ew, emine;                 // has the role; and its window exists
+    float p_dout = 0.f, p_r = 0.f, p_z = 0.f, p_c = 0.f, p_hn = 0.f, p_hp = 0.f;
+
+    __device__ __forceinline__ GruBwdRole(const GruArgs &a, int member, int n0)
+    {
+        const int tid = threadIdx.x;
+        es = tid / U; eu = tid - es * U;
+        ej = member * U + eu;
+        en = n0 + es;
+        ew = tid < NB * U;
+        emine = ew && en < a.N;
+        if (emine) {
+            float *zr = a.dgh + ((long)en * (a.T + 1) + a.T) * 3 * H;      // zero junk row T of dGH
+            zr[ej] = 0.f; zr[H + ej] = 0.f; zr[2 * H + ej] = 0.f;
+            request(a, a.T - 1);
+        }
+    }
+    __device__ __forceinline__ void request(const GruArgs &a, int t)
+    {
+        const long row = (long)en * a.T + t;
+        const float *gs = a.gates + row * 3 * H;
+        p_dout = a.dout[row * H + ej];
+        p_r = gs[ej]; p_z = gs[H + ej]; p_c = gs[2 * H + ej];
+        p_hn = a.hn[row * H + ej];
+        p_hp = a.hall[((long)en * (a.T + 1) + t) * H + ej];
+    }
+    // step t, dh = dout + carry: stores dGI and dGH, hands the member's dGH entries to lds(dpr, dpz, dhn) (zeros for a
+    // window that does not exist) and returns dh z, the part of dh_{t-1} that does not go through W_hh
+    template <typename Lds> __device__ __forceinline__ float step(const GruArgs &a, int t, float carry, Lds &&lds)
+    {
+        if (!ew) return 0.f;
+        GruGrad d{0.f, 0.f, 0.f, 0.f, 0.f};
+        if (emine) {
+            d = gru_grad(p_dout + carry, p_r, p_z, p_c, p_hn, p_hp);
+            float *gi = a.dgi + ((long)en * a.T + t) * 3 * H;
+            gi[ej] = d.dpr; gi[H + ej] = d.dpz; gi[2 * H + ej] = d.dpn;
+            float *gh = a.dgh + ((long)en * (a.T + 1) + t) * 3 * H;
+            gh[ej] = d.dpr; gh[H + ej] = d.dpz; gh[2 * H + ej] = d.dhn;
+        }
+        lds(d.dpr, d.dpz, d.dhn);
+        // behind the stores: a request in front of them made the compiler wait for it (vmcnt) where a store reused a register
+        if (emine && t > 0) request(a, t - 1);
+        return d.keep;
+    }
+};
 
 // Backward twin of gru_fwd_coop_kernel: member m keeps the SAME 3 U rows of W_hh (its U units x 3 gates) in
 // registers, now one COLUMN j' per thread (thread (j', half): 96 rows), forms its partial W_hh^T dGH for all H
@@ -587,58 +592,18 @@ template <int H, int NB> __global__ __launch_bounds__(512) void gru_bwd_coop_ker
         const int lr = half * 96 + i;                          // local row = gate*U + unit
         w[i / 2][i % 2] = a.whh[(long)((lr / U) * H + member * U + (lr % U)) * H + jc];
     }
-    // elementwise role: thread (es, eu) for tid < NB*U
-    const int es = tid / U, eu = tid - es * U;
-    const int ej = member * U + eu;
-    const int en = n0 + es;
-    const bool ew = tid < NB * U;
-    const bool emine = ew && en < a.N;
+    // not a plain declaration: zeroes row T of dGH and requests step T - 1's saved activations, in front of the time loop
+    GruBwdRole<H, NB> e(a, member, n0);
+    const int es = e.es, eu = e.eu;
+    coop_weights_ready(w);                                     // behind the request above, in front of the time loop
     float carry = 0.f;
-    if (emine) {                                               // zero junk row T of dGH
-        float *zr = a.dgh + ((long)en * (T + 1) + T) * 3 * H;
-        zr[ej] = 0.f; zr[H + ej] = 0.f; zr[2 * H + ej] = 0.f;
-    }
-    // the saved activations of step t-1 are requested while step t runs (same reason as in the forward kernel)
-    float p_dout = 0.f, p_r = 0.f, p_z = 0.f, p_c = 0.f, p_hn = 0.f, p_hp = 0.f;
-    auto request = [&](int t) {
-        const long row = (long)en * T + t;
-        const float *gs = a.gates + row * 3 * H;
-        p_dout = a.dout[row * H + ej];
-        p_r = gs[ej]; p_z = gs[H + ej]; p_c = gs[2 * H + ej];
-        p_hn = a.hn[row * H + ej];
-        p_hp = a.hall[((long)en * (T + 1) + t) * H + ej];
-    };
-    if (emine) request(T - 1);
-    coop_weights_ready(w);
     bool dead = false;
     for (int t = T - 1; t >= 0; --t) {
         const int par = t & 1;
         const unsigned epoch = ca.epoch0 + (unsigned)(T - t);              // 1, 2, ...
-        float keep = 0.f;
-        if (ew) {
-            float dpr = 0.f, dpz = 0.f, dhn = 0.f;
-            if (emine) {
-                const long row = (long)en * T + t;
-                const float dh = p_dout + carry;
-                const float r = p_r, z = p_z, c = p_c;
-                const float hnv = p_hn;
-                const float hp_ = p_hp;
-                const float dc = dh * (1.f - z);
-                const float dz = dh * (hp_ - c);
-                const float dpn = dc * (1.f - c * c);
-                dpr = dpn * hnv * r * (1.f - r);
-                dpz = dz * z * (1.f - z);
-                dhn = dpn * r;
-                keep = dh * z;
-                float *gi = a.dgi + row * 3 * H;
-                gi[ej] = dpr; gi[H + ej] = dpz; gi[2 * H + ej] = dpn;
-                float *gh = a.dgh + ((long)en * (T + 1) + t) * 3 * H;
-                gh[ej] = dpr; gh[H + ej] = dpz; gh[2 * H + ej] = dhn;
-            }
+        const float keep = e.step(a, t, carry, [&](float dpr, float dpz, float dhn) {
             dgs[es][eu] = dpr; dgs[es][U + eu] = dpz; dgs[es][2 * U + eu] = dhn;
-            // behind the stores: a request in front of them made the compiler wait for it (vmcnt) where a store reused a register
-            if (emine && t > 0) request(t - 1);
-        }
+        });
         coop_lds_barrier();
         // partial[jc] over this thread's 96 rows, all NB windows
         f32x2 acc[NB];                                         // even / odd rows
@@ -661,44 +626,13 @@ template <int H, int NB> __global__ __launch_bounds__(512) void gru_bwd_coop_ker
             for (int hh = 1; hh < HALVES; ++hh) v += part[hh][s][k];
             return v;
         };
-        // publish the columns other members own (this member's own columns stay in LDS)
         if (t > 0) {
-            for (int idx = tid; idx < NB * H; idx += 512) {
-                const int s = idx / H, k = idx - s * H;
-                if (k / U == member) continue;
-                const float v = column(s, k);
-                COOP_GLOBAL gu64_t *slot =
-                    (COOP_GLOBAL gu64_t *)(ca.comm + ((((long)group * 2 + par) * G + member) * NB + s) * H + k);
-                __hip_atomic_store(slot, ((gu64_t)epoch << 32) | (gu64_t)__float_as_uint(dead ? NAN : v), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-            }
-            if (ew) {
-                float sum = keep + column(es, ej);
-                // the partners' pieces are polled together: one L2 round trip per attempt, not G - 1 in a row
-                COOP_GLOBAL gu64_t *slot[G - 1];
-#pragma unroll
-                for (int d = 1; d < G; ++d) {
-                    const int src = (member + d) & (G - 1);
-                    slot[d - 1] = (COOP_GLOBAL gu64_t *)(ca.comm + ((((long)group * 2 + par) * G + src) * NB + es) * H + ej);
-                }
-                gu64_t x[G - 1];
-                unsigned spins = dead ? (1u << 22) : 0u;
-                for (;;) {
-                    bool ready = true;
-#pragma unroll
-                    for (int d = 0; d < G - 1; ++d) x[d] = __hip_atomic_load(slot[d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-                    for (int d = 0; d < G - 1; ++d) ready = ready && (unsigned)(x[d] >> 32) == epoch;
-                    if (ready) break;
-                    if (++spins > (1u << 22)) { dead = true; coop_report(ca.err, COOP_ERR_BWD_WAIT); break; }
-                    __builtin_amdgcn_s_sleep(1);
-                }
-#pragma unroll
-                for (int d = 0; d < G - 1; ++d) sum += __uint_as_float((unsigned)x[d]);
+            coop_bwd_publish<H, NB>(ca.comm, epoch, group, par, member, dead, column);
+            if (e.ew) {
+                float sum = keep + column(es, e.ej);
+                dead = coop_bwd_collect<H, NB>(ca.comm, epoch, ca.err, group, par, member, es, e.ej, dead, sum);
                 carry = dead ? NAN : sum;
             }
-            // no barrier here: dgs is rewritten before the next step's first barrier, part after it, and every thread has
-            // finished reading both when it gets there; `dead` stays with the thread that timed out (its carry is poisoned)
         }
     }
 }
@@ -730,16 +664,13 @@ template <int H, int NB> __global__ __launch_bounds__(512) void gru_bwd_mfma_ker
         const int jcol = (wave * TW + i) * 16 + (lane & 15);
 #pragma unroll
         for (int ks = 0; ks < K3 / 32; ++ks) {
-            unsigned short t[8][3];
+            float v[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const int lr = ks * 32 + 8 * (lane >> 4) + e;
-                split3(a.whh[(long)((lr / U) * H + member * U + (lr % U)) * H + jcol], t[e]);
+                v[e] = a.whh[(long)((lr / U) * H + member * U + (lr % U)) * H + jcol];
             }
-#pragma unroll
-            for (int pl = 0; pl < 3; ++pl)
-#pragma unroll
-                for (int d = 0; d < 4; ++d) bw[i][ks][pl].d[d] = (unsigned)t[2 * d][pl] | ((unsigned)t[2 * d + 1][pl] << 16);
+            mfma_pack(v, bw[i][ks]);
         }
     }
     for (int idx = tid; idx < 3 * 8 * LDK; idx += 512) (&dgp[0][0][0])[idx] = 0;
@@ -751,65 +682,23 @@ template <int H, int NB> __global__ __launch_bounds__(512) void gru_bwd_mfma_ker
     const char *const pa1 = planes + (((upper ? 1 : 0) * 8 + (arow & 7)) * LDK + 8 * akg) * 2;      // [d0 | d1]
     const char *const pa2 = planes + (((upper ? 2 : 0) * 8 + (arow & 7)) * LDK + 8 * akg) * 2;      // [d0 | d2]
     const char *const pa3 = upper ? reinterpret_cast<const char *>(zrow) + 16 * akg : planes + ((2 * 8 + arow) * LDK + 8 * akg) * 2;   // [d2 | 0]
-    // elementwise role: thread (es, eu) for tid < NB*U
-    const int es = tid / U, eu = tid - es * U;
-    const int ej = member * U + eu;
-    const int en = n0 + es;
-    const bool ew = tid < NB * U;
-    const bool emine = ew && en < a.N;
+    // not a plain declaration: zeroes row T of dGH and requests step T - 1's saved activations, in front of the time loop
+    GruBwdRole<H, NB> e(a, member, n0);
+    const int es = e.es, eu = e.eu;
     float carry = 0.f;
-    if (emine) {                                               // zero junk row T of dGH
-        float *zr = a.dgh + ((long)en * (T + 1) + T) * 3 * H;
-        zr[ej] = 0.f; zr[H + ej] = 0.f; zr[2 * H + ej] = 0.f;
-    }
-    // the saved activations of step t-1 are requested while step t runs (same reason as in the forward kernel)
-    float p_dout = 0.f, p_r = 0.f, p_z = 0.f, p_c = 0.f, p_hn = 0.f, p_hp = 0.f;
-    auto request = [&](int t) {
-        const long row = (long)en * T + t;
-        const float *gs = a.gates + row * 3 * H;
-        p_dout = a.dout[row * H + ej];
-        p_r = gs[ej]; p_z = gs[H + ej]; p_c = gs[2 * H + ej];
-        p_hn = a.hn[row * H + ej];
-        p_hp = a.hall[((long)en * (T + 1) + t) * H + ej];
-    };
-    if (emine) request(T - 1);
     bool dead = false;
     for (int t = T - 1; t >= 0; --t) {
         const int par = t & 1;
         const unsigned epoch = ca.epoch0 + (unsigned)(T - t);              // 1, 2, ...
-        float keep = 0.f;
-        if (ew) {
-            float dpr = 0.f, dpz = 0.f, dhn = 0.f;
-            if (emine) {
-                const long row = (long)en * T + t;
-                const float dh = p_dout + carry;
-                const float r = p_r, z = p_z, c = p_c;
-                const float hnv = p_hn;
-                const float hp_ = p_hp;
-                const float dc = dh * (1.f - z);
-                const float dz = dh * (hp_ - c);
-                const float dpn = dc * (1.f - c * c);
-                dpr = dpn * hnv * r * (1.f - r);
-                dpz = dz * z * (1.f - z);
-                dhn = dpn * r;
-                keep = dh * z;
-                float *gi = a.dgi + row * 3 * H;
-                gi[ej] = dpr; gi[H + ej] = dpz; gi[2 * H + ej] = dpn;
-                float *gh = a.dgh + ((long)en * (T + 1) + t) * 3 * H;
-                gh[ej] = dpr; gh[H + ej] = dpz; gh[2 * H + ej] = dhn;
-            }
-            {
-                unsigned short t0[3], t1[3], t2[3];
-                split3(dpr, t0); split3(dpz, t1); split3(dhn, t2);
+        const float keep = e.step(a, t, carry, [&](float dpr, float dpz, float dhn) {
+            unsigned short t0[3], t1[3], t2[3];
+            split3(dpr, t0); split3(dpz, t1); split3(dhn, t2);
 #pragma unroll
-                for (int pl = 0; pl < 3; ++pl) { dgp[pl][es][eu] = t0[pl]; dgp[pl][es][U + eu] = t1[pl]; dgp[pl][es][2 * U + eu] = t2[pl]; }
-            }
-            // behind the stores: a request in front of them made the compiler wait for it (vmcnt) where a store reused a register
-            if (emine && t > 0) request(t - 1);
-        }
+            for (int pl = 0; pl < 3; ++pl) { dgp[pl][es][eu] = t0[pl]; dgp[pl][es][U + eu] = t1[pl]; dgp[pl][es][2 * U + eu] = t2[pl]; }
+        });
         coop_lds_barrier();
-        // out[window][column] = sum over the member's rows: four products per K step (see gru_fwd_mfma_kernel), four column
-        // tiles per wave sharing the A fragments
+        // out[window][column] = sum over the member's rows: four products per K step (mfma_kstep), four column tiles per
+        // wave sharing the A fragments
         {
             f32x4_t acc[TW];
 #pragma unroll
@@ -820,61 +709,25 @@ template <int H, int NB> __global__ __launch_bounds__(512) void gru_bwd_mfma_ker
                 const bf16x8_t a2 = *reinterpret_cast<const bf16x8_t *>(pa2 + ks * 64);
                 const bf16x8_t a3 = *reinterpret_cast<const bf16x8_t *>(pa3 + (upper ? 0 : ks * 64));
 #pragma unroll
-                for (int i = 0; i < TW; ++i) {
-                    acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, __builtin_bit_cast(bf16x8_t, bw[i][ks][0]), acc[i], 0, 0, 0);
-                    acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, __builtin_bit_cast(bf16x8_t, bw[i][ks][1]), acc[i], 0, 0, 0);
-                    acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, __builtin_bit_cast(bf16x8_t, bw[i][ks][2]), acc[i], 0, 0, 0);
-                    acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a3, __builtin_bit_cast(bf16x8_t, bw[i][ks][0]), acc[i], 0, 0, 0);
-                }
+                for (int i = 0; i < TW; ++i) acc[i] = mfma_kstep(a1, a2, a3, bw[i][ks], acc[i]);
             }
             // lane: column lane % 16 of the tile, rows 4 (lane / 16) .. + 3: rows 0-7 = the windows, rows 8-15 = the second half
 #pragma unroll
             for (int i = 0; i < TW; ++i) {
                 const int col = (wave * TW + i) * 16 + (lane & 15);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) part[lane >> 5][4 * ((lane >> 4) & 1) + e][col] = acc[i][e];
+                for (int e4 = 0; e4 < 4; ++e4) part[lane >> 5][4 * ((lane >> 4) & 1) + e4][col] = acc[i][e4];
             }
         }
         coop_lds_barrier();
         auto column = [&](int s, int k) { return part[0][s][k] + part[1][s][k]; };
-        // publish the columns other members own (this member's own columns stay in LDS)
         if (t > 0) {
-            for (int idx = tid; idx < NB * H; idx += 512) {
-                const int s = idx / H, k = idx - s * H;
-                if (k / U == member) continue;
-                const float v = column(s, k);
-                COOP_GLOBAL gu64_t *slot =
-                    (COOP_GLOBAL gu64_t *)(ca.comm + ((((long)group * 2 + par) * G + member) * NB + s) * H + k);
-                __hip_atomic_store(slot, ((gu64_t)epoch << 32) | (gu64_t)__float_as_uint(dead ? NAN : v), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-            }
-            if (ew) {
-                float sum = keep + column(es, ej);
-                // the partners' pieces are polled together: one L2 round trip per attempt, not G - 1 in a row
-                COOP_GLOBAL gu64_t *slot[G - 1];
-#pragma unroll
-                for (int d = 1; d < G; ++d) {
-                    const int src = (member + d) & (G - 1);
-                    slot[d - 1] = (COOP_GLOBAL gu64_t *)(ca.comm + ((((long)group * 2 + par) * G + src) * NB + es) * H + ej);
-                }
-                gu64_t x[G - 1];
-                unsigned spins = dead ? (1u << 22) : 0u;
-                for (;;) {
-                    bool ready = true;
-#pragma unroll
-                    for (int d = 0; d < G - 1; ++d) x[d] = __hip_atomic_load(slot[d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-                    for (int d = 0; d < G - 1; ++d) ready = ready && (unsigned)(x[d] >> 32) == epoch;
-                    if (ready) break;
-                    if (++spins > (1u << 22)) { dead = true; coop_report(ca.err, COOP_ERR_BWD_WAIT); break; }
-                    __builtin_amdgcn_s_sleep(1);
-                }
-#pragma unroll
-                for (int d = 0; d < G - 1; ++d) sum += __uint_as_float((unsigned)x[d]);
+            coop_bwd_publish<H, NB>(ca.comm, epoch, group, par, member, dead, column);
+            if (e.ew) {
+                float sum = keep + column(es, e.ej);
+                dead = coop_bwd_collect<H, NB>(ca.comm, epoch, ca.err, group, par, member, es, e.ej, dead, sum);
                 carry = dead ? NAN : sum;
             }
-            // no barrier here: dgs is rewritten before the next step's first barrier, part after it, and every thread has
-            // finished reading both when it gets there; `dead` stays with the thread that timed out (its carry is poisoned)
         }
     }
 }

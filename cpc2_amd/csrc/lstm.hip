@@ -23,8 +23,6 @@ namespace cpc {
 
 namespace {
 
-__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
-
 // W_hh [G*H][H] -> wf[(k4*G + g)*H + j] = W[g*H + j][4*k4 .. 4*k4+3]   (forward: thread j, all k)
 __global__ void lstm_pack_fwd_kernel(const float *w, float4 *wf, int H, int G)
 {
@@ -130,10 +128,10 @@ __global__ void lstm_fwd_kernel(LstmArgs a)
             const float *gin = a.gi + row * G * H;
             float hv;
             if (G == 4) {
-                const float ig = sigm(gin[j] + pre[0]);
-                const float fg = sigm(gin[H + j] + pre[G > 1 ? 1 : 0]);
+                const float ig = coop_sigmoid(gin[j] + pre[0]);
+                const float fg = coop_sigmoid(gin[H + j] + pre[G > 1 ? 1 : 0]);
                 const float gg = tanhf(gin[2 * H + j] + pre[G > 2 ? 2 : 0]);
-                const float og = sigm(gin[3 * H + j] + pre[G > 3 ? 3 : 0]);
+                const float og = coop_sigmoid(gin[3 * H + j] + pre[G > 3 ? 3 : 0]);
                 const float cv = fg * cprev + ig * gg;
                 hv = og * tanhf(cv);
                 float *gs = a.gates + row * 4 * H;
@@ -233,20 +231,12 @@ __global__ void lstm_bwd_kernel(LstmArgs a)
 // On-chip LSTM recurrence for H = 256 and 512 (same scheme as gru.hip's cooperative kernels, see coop.h): a group of
 // G workgroups shares NB windows and W_hh never leaves the register file -- 4 gates x 32 columns = 128 weights per
 // thread.  The cell state of (window q, unit j) stays in the register of the lane that finishes that pair.
-struct LstmCoopArgs {
-    LstmArgs g;
-    gu64_t *comm;          // granules (coop_comm_acquire: the library's own buffer): fwd [groups][2][G][U][NB] (coop_fwd_slot), bwd [groups][2][G][NB][H]
-    unsigned epoch0;       // this launch's epochs are epoch0 + 1 .. epoch0 + T: no granule of an earlier launch carries one of them
-    int groups, xcd_map;
-    int *err;              // host-visible error word (coop.h), or nullptr
-    int fault;             // tests: member 0 of group 0 withholds its publish of step 1
-};
+using LstmCoopArgs = CoopArgs<LstmArgs>;
 
 template <int H, int NB> __global__ __launch_bounds__(512) void lstm_fwd_coop_kernel(LstmCoopArgs ca)
 {
     using C = CoopCfg<H>;
     constexpr int QS = C::QS, U = C::U, G = C::G;
-    constexpr int KP = NB * H / 512 > 0 ? NB * H / 512 : 1;          // granules gathered per thread and step
     static_assert(NB <= QS, "one finishing lane per window");
     __shared__ __attribute__((aligned(16))) float hs[2][NB][C::LDH];
     const LstmArgs &a = ca.g;
@@ -314,20 +304,17 @@ template <int H, int NB> __global__ __launch_bounds__(512) void lstm_fwd_coop_ke
             if (s == q) { g0 = acc[0]; g1 = acc[1]; g2 = acc[2]; g3 = acc[3]; }
         }
         if (q < NB) {
-            const float ig = sigm(gi0 + g0 + bh0);
-            const float fg = sigm(gi1 + g1 + bh1);
+            const float ig = coop_sigmoid(gi0 + g0 + bh0);
+            const float fg = coop_sigmoid(gi1 + g1 + bh1);
             const float gg = tanhf(gi2 + g2 + bh2);
-            const float og = sigm(gi3 + g3 + bh3);
+            const float og = coop_sigmoid(gi3 + g3 + bh3);
             const float cv = fg * cprev + ig * gg;
             float hv = og * tanhf(cv);
             cprev = cv;
             if (dead) hv = NAN;
-            // publish first (also for padding windows, so that every granule of the epoch gets written): the other
-            // members wait for this store, nobody waits for the saved activations below
-            COOP_GLOBAL gu64_t *slot = (COOP_GLOBAL gu64_t *)(ca.comm + coop_fwd_slot<H, NB>(group, nxt, member, u, q));
-            if (!(ca.fault && group == 0 && member == 0 && t == 1))
-                __hip_atomic_store(slot, ((gu64_t)(ca.epoch0 + (unsigned)(t + 1)) << 32) | (gu64_t)__float_as_uint(mine ? hv : 0.f),
-                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            // publish first: the other members wait for this store, nobody waits for the saved activations below
+            coop_fwd_publish<H, NB>(ca.comm, ca.epoch0 + (unsigned)(t + 1), ca.fault, group, nxt, member, u, q, t, mine,
+                                    hv);
             if (mine) {
                 const long row = (long)ns * T + t;
                 float *gs = a.gates + row * 4 * H;
@@ -337,36 +324,10 @@ template <int H, int NB> __global__ __launch_bounds__(512) void lstm_fwd_coop_ke
                 a.call[((long)ns * (T + 1) + t + 1) * H + j] = cv;
             }
         }
-        // gather the whole new h (all members) into the other LDS buffer; a thread's KP granules are polled together
         if (t + 1 < T) {
-            COOP_GLOBAL gu64_t *slot[KP];
-#pragma unroll
-            for (int i = 0; i < KP; ++i) {
-                const int idx = tid + 512 * i;
-                slot[i] = (COOP_GLOBAL gu64_t *)(ca.comm + ((long)group * 2 + nxt) * (NB * H) + idx);      // memory order: coalesced
-            }
-            gu64_t x[KP];
-            unsigned spins = dead ? (1u << 22) : 0u;            // once timed out, never wait again
-            if (tid < NB * H) {
-                for (;;) {
-                    bool ready = true;
-#pragma unroll
-                    for (int i = 0; i < KP; ++i) x[i] = __hip_atomic_load(slot[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-                    for (int i = 0; i < KP; ++i) ready = ready && (unsigned)(x[i] >> 32) == ca.epoch0 + (unsigned)(t + 1);
-                    if (ready) break;
-                    if (++spins > (1u << 22)) { dead = true; coop_report(ca.err, COOP_ERR_FWD_WAIT); break; }
-                    __builtin_amdgcn_s_sleep(1);
-                }
-#pragma unroll
-                for (int i = 0; i < KP; ++i) {
-                    const int idx = tid + 512 * i;
-                    int gw, gk;
-                    coop_fwd_who<H, NB>(idx, gw, gk);
-                    hs[nxt][gw][coop_pad(gk)] = dead ? NAN : __uint_as_float((unsigned)x[i]);
-                }
-            }
-            coop_lds_barrier();            // `dead` stays with the thread that timed out: what it gathered is poisoned above
+            dead = coop_fwd_gather<H, NB>(ca.comm, ca.epoch0 + (unsigned)(t + 1), ca.err, group, nxt, dead,
+                                          [&](int window, int k, float h) { hs[nxt][window][coop_pad(k)] = h; });
+            coop_lds_barrier();
         }
     }
     if (mine) {
@@ -451,7 +412,7 @@ template <int H, int NB> __global__ __launch_bounds__(512) void lstm_bwd_coop_ke
                 gh[ej] = dpi; gh[H + ej] = dpf; gh[2 * H + ej] = dpg; gh[3 * H + ej] = dpo;
             }
             dgs[es][eu] = dpi; dgs[es][U + eu] = dpf; dgs[es][2 * U + eu] = dpg; dgs[es][3 * U + eu] = dpo;
-            if (emine && t > 0) request(t - 1);                 // behind the stores (see gru_bwd_coop_kernel)
+            if (emine && t > 0) request(t - 1);                 // behind the stores (see GruBwdRole::step, gru.hip)
         }
         coop_lds_barrier();
         if (t == 0) break;                                      // dh_{-1} is not needed
@@ -476,43 +437,12 @@ template <int H, int NB> __global__ __launch_bounds__(512) void lstm_bwd_coop_ke
             for (int hh = 1; hh < HALVES; ++hh) v += part[hh][s][k];
             return v;
         };
-        // publish the columns other members own (this member's own columns stay in LDS)
-        for (int idx = tid; idx < NB * H; idx += 512) {
-            const int s = idx / H, k = idx - s * H;
-            if (k / U == member) continue;
-            const float v = column(s, k);
-            COOP_GLOBAL gu64_t *slot =
-                (COOP_GLOBAL gu64_t *)(ca.comm + ((((long)group * 2 + par) * G + member) * NB + s) * H + k);
-            __hip_atomic_store(slot, ((gu64_t)epoch << 32) | (gu64_t)__float_as_uint(dead ? NAN : v), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-        }
+        coop_bwd_publish<H, NB>(ca.comm, epoch, group, par, member, dead, column);
         if (ew) {
             float sum = column(es, ej);
-            // the partners' pieces are polled together: one L2 round trip per attempt, not G - 1 in a row
-            COOP_GLOBAL gu64_t *slot[G - 1];
-#pragma unroll
-            for (int d = 1; d < G; ++d) {
-                const int src = (member + d) & (G - 1);
-                slot[d - 1] = (COOP_GLOBAL gu64_t *)(ca.comm + ((((long)group * 2 + par) * G + src) * NB + es) * H + ej);
-            }
-            gu64_t x[G - 1];
-            unsigned spins = dead ? (1u << 22) : 0u;
-            for (;;) {
-                bool ready = true;
-#pragma unroll
-                for (int d = 0; d < G - 1; ++d) x[d] = __hip_atomic_load(slot[d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-                for (int d = 0; d < G - 1; ++d) ready = ready && (unsigned)(x[d] >> 32) == epoch;
-                if (ready) break;
-                if (++spins > (1u << 22)) { dead = true; coop_report(ca.err, COOP_ERR_BWD_WAIT); break; }
-                __builtin_amdgcn_s_sleep(1);
-            }
-#pragma unroll
-            for (int d = 0; d < G - 1; ++d) sum += __uint_as_float((unsigned)x[d]);
+            dead = coop_bwd_collect<H, NB>(ca.comm, epoch, ca.err, group, par, member, es, ej, dead, sum);
             carry = dead ? NAN : sum;
         }
-        // no barrier here: dgs is rewritten before the next step's first barrier, part after it, and every thread has
-        // finished reading both when it gets there; `dead` stays with the thread that timed out (its carry is poisoned)
     }
 }
 

@@ -4,7 +4,7 @@
 //     struct Cell {
 //         static constexpr int G;                          // gate blocks: rows of W_ih / W_hh are G * H
 //         static constexpr const char *name, *kernel_names[2], *pack_names[2];      // error messages: the cell; [backward]: its kernels
-//         using Args, CoopArgs, CoopKernel;                // the kernels' argument structs; void (*)(CoopArgs)
+//         using Args, CoopArgs, CoopKernel;                // the kernels' arguments; coop.h's CoopArgs<Args>; void (*)(CoopArgs)
 //         static constexpr auto fwd_kernel, bwd_kernel;    // the streaming kernels: void (*)(Args)
 //         static void take_saved(RecLayout &, Carver &, int l);         // layer l's saved tensors besides outl
 //         static void cell_args(Args &, float *extra, const float *c0, float *clast);       // what only this cell's kernels read
