@@ -138,6 +138,11 @@ SIGNATURES = {
     "cpc_augment_pitch": (c_int, [c_ptr, c_long, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_int, c_ptr, c_ptr, c_int, c_int, c_ptr]),
     "cpc_augment_freeverb": (c_int, [c_ptr, c_long, c_ptr, c_ptr, c_int, ctypes.POINTER(c_int), ctypes.c_float, ctypes.c_float,
                              ctypes.c_float, c_ptr, c_int, c_int, c_ptr]),
+    "cpc_bandreject_tile": (c_int, []),
+    "cpc_bandreject_max_half": (c_int, []),
+    "cpc_bandreject_taps": (c_int, [c_ptr, c_int, c_int, ctypes.c_double, ctypes.c_double, c_ptr, c_ptr]),
+    "cpc_augment_bandreject": (c_int, [c_ptr, c_long, c_ptr, c_ptr, c_int, ctypes.c_double, ctypes.c_double, c_ptr, c_int, c_int,
+                                       c_ptr]),
     "cpc_resample_plan": (c_int, [c_int, c_int, c_int, ctypes.c_double] + [ctypes.POINTER(c_int)] * 4),
     "cpc_resample_table_host": (c_int, [c_int, c_int, c_int, ctypes.c_double, c_ptr, c_long]),
     "cpc_resample": (c_int, [c_ptr, c_long, c_ptr, c_ptr, c_int, c_long, c_ptr, c_int, c_int, c_int, c_ptr, c_long, c_ptr, c_ptr]),

@@ -6,7 +6,8 @@ libcpc2_hip.so (cpc_flac_decode_f32, MD5-verified), PCM / float WAV through a sm
 Sample-rate conversion (`resample`, `resample_pack`) is torchaudio's sinc_interp_hann resampler on the device
 (csrc/resample.hip; the definition is in include/cpc2_hip.h), and `save_wav` is the writer `load` reads back: PCM16 quantised on
 the device, or IEEE float.  `pitch_shift` is the direct call of the `pitch_wsola` augmentation's kernels (csrc/pitch.hip), `freeverb`
-that of the `freeverb` augmentation's kernel (csrc/freeverb.hip)."""
+that of the `freeverb` augmentation's kernel (csrc/freeverb.hip), `bandreject` that of the `bandreject_sinc` augmentation's
+(csrc/bandreject.hip)."""
 import collections
 import ctypes
 import struct
@@ -254,6 +255,34 @@ def freeverb(x, room, reverberance=100.0, hf_damping=100.0, wet_gain_dB=0.0):
         return out
     comb_len = torch.from_numpy(tables["comb_len"]).to(x.device)
     da._freeverb_launch(x.view(rows, window), comb_len, 0, rows, tables, window, out.view(rows, window), "freeverb")
+    return out
+
+
+# --------------------------------------------------------------------------- band reject
+def bandreject(x, low, high, attenuation_dB=120.0, transition_hz=400.0):
+    """The `bandreject_sinc` filter (data_augmentation.BandrejectSincAugment states it; csrc/bandreject.hip) of [b, 1, W], [b, W] or
+    [W] float32 device rows sampled at 16 kHz: the band `low` .. `high` in Hz (0 <= low <= high <= 8000) is one pair for all rows
+    or one per row.  The result has x's shape.  This is this package's Kaiser-windowed sinc filter, not sox's `sinc`; nothing is
+    drawn here and there is no dither."""
+    from . import data_augmentation as da
+    _lib.require_gpu(x)
+    x = _lib.f32c(x)
+    window = x.shape[-1]
+    rows = x.numel() // window if window else 0
+    edges = []
+    for name, value in (("low", low), ("high", high)):
+        per_row = np.asarray(value.cpu() if isinstance(value, torch.Tensor) else value, dtype=np.float64)
+        if per_row.ndim == 0:
+            per_row = np.full(rows, float(per_row), dtype=np.float64)
+        if per_row.size != rows:
+            raise ValueError(f"bandreject: {per_row.size} {name} edges for {rows} rows")
+        edges.append(per_row.reshape(-1))
+    tables = da.bandreject_tables(edges[0], edges[1], attenuation_dB, transition_hz)
+    out = torch.empty_like(x)
+    if rows == 0:
+        return out
+    band = torch.from_numpy(tables["band"]).to(x.device)
+    da._bandreject_launch(x.view(rows, window), band, 0, rows, tables, window, out.view(rows, window), "bandreject")
     return out
 
 

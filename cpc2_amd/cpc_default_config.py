@@ -3,14 +3,15 @@
 Same flags, types, choices and defaults as the reference's cpc/cpc_default_config.py:13-162 -- all of them, the
 augmentation group included: cpc2_amd.train builds additive / natural_reverb / time_dropout (data_augmentation.py) and
 pitch_wsola (a choice of --augment_type the reference does not have: a pitch shift by this package's own definition) and
-freeverb (likewise: the Freeverb network behind sox's reverb, by this package's own definition, with ReverbAugment's draw), and
+freeverb (likewise: the Freeverb network behind sox's reverb, by this package's own definition, with ReverbAugment's draw) and
+bandreject_sinc (likewise: a Kaiser-windowed sinc band-reject filter, by this package's own definition, with BandrejectAugment's draw), and
 refuses the sox-based types with a message (train.py, refuseUnsupported), and checkpoint_args.json carries the same keys as a reference run, so that either side can resume the other's run."""
 import argparse
 
 NAMING_CONVENTIONS = ['full_seedlings', 'no_speaker', 'id_spkr_onset_offset', 'spkr-id', 'spkr-id-nb',
                       'id_spkr_onset_offset_spkr_onset_offset', 'spkr_id_nb']
 AUGMENT_TYPES = ['none', 'bandreject', 'pitch', 'pitch_deropout', 'pitch_quick', 'additive', 'artificial_reverb',
-                 'time_dropout', 'artificial_reverb_dropout', 'natural_reverb', 'pitch_wsola', 'freeverb']
+                 'time_dropout', 'artificial_reverb_dropout', 'natural_reverb', 'pitch_wsola', 'freeverb', 'bandreject_sinc']
 
 
 def get_default_cpc_config():
@@ -81,12 +82,16 @@ def set_default_cpc_config(parser):
                                   "shifts the pitch by up to --shift_max cents (a WSOLA stretch and a sinc resampling: this "
                                   "package's definition, not sox's).  freeverb reverberates without "
                                   "impulse responses (the Freeverb comb / all-pass network with the room size drawn per window: "
-                                  "this package's definition, agreement with sox's reverb unmeasured).")
+                                  "this package's definition, agreement with sox's reverb unmeasured).  bandreject_sinc rejects one "
+                                  "frequency band per window, drawn on the mel scale and scaled by --bandreject_scaler (a "
+                                  "Kaiser-windowed sinc FIR in float64: this package's definition, agreement with sox's sinc "
+                                  "unmeasured, no dither).")
     a.add_argument('--noise_extension', type=str, default='.wav')
     a.add_argument('--augment_future', action='store_true')
     a.add_argument('--augment_past', action='store_true')
     a.add_argument('--augment_type', type=str, choices=AUGMENT_TYPES, nargs='+')
-    a.add_argument('--bandreject_scaler', type=float, default=1.0)
+    a.add_argument('--bandreject_scaler', type=float, default=1.0,
+                   help='bandreject_sinc: the band is at most 27 x this many of 256 mel steps wide; from 0 to 256 / 27.')
     a.add_argument('--t_ms', type=int, default=100)
     a.add_argument('--pathDBNoise', type=str, default=None)
     a.add_argument('--pathSeqNoise', type=str, default=None)

@@ -2,7 +2,8 @@
 
 Built: `additive` (AdditiveNoiseAugment :157-228), `natural_reverb` (NaturalReverb :278-318), `time_dropout`
 (TimeDropoutAugment :268-275), `pitch_wsola` (PitchShiftAugment: a pitch shift by this package's own definition, below),
-`freeverb` (FreeverbAugment: artificial reverberation by this package's own definition, below), their
+`freeverb` (FreeverbAugment: artificial reverberation by this package's own definition, below), `bandreject_sinc`
+(BandrejectSincAugment: a band-reject filter by this package's own definition, below), their
 combinations (CombinedTransforms :331-344) and the reverberated noise (`augmentation_factory(..., applied_on_noise=True)`).
 The sox types (UNBUILT_TYPES: pitch, pitch_quick, pitch_dropout, pitch_deropout, bandreject, artificial_reverb, ...) are refused
 by name: neither sox nor WavAugment is available, and their filters cannot be pinned to anything.  `pitch_wsola` is NOT one of
@@ -12,6 +13,9 @@ stands in for the reference's `pitch_dropout`.  `freeverb` likewise: it draws wh
 size per window) and reverberates with the public-domain Freeverb network -- the algorithm behind sox's `reverb` -- as written down
 in FreeverbAugment's docstring; `artificial_reverb` and `artificial_reverb_dropout` stay refused, the agreement of `freeverb` with
 sox's output is unmeasured, and `--augment_type freeverb time_dropout` stands in for `artificial_reverb_dropout`.
+`bandreject_sinc` likewise: it draws what the reference's BandrejectAugment draws (one band per window on the mel scale) and
+rejects the band with a Kaiser-windowed sinc FIR -- the textbook filter behind sox's `sinc -a 120 high-low` -- as written down in
+BandrejectSincAugment's docstring; `bandreject` itself stays refused and the agreement with sox's output is unmeasured.
 
 The reference augments one window at a time on the CPU, inside DataLoader workers.  Here a pack of audio lives in HBM as one
 flat vector and so do the noise pack and the impulse responses; a batch's augmentation is a few kernels
@@ -38,6 +42,8 @@ Deviations from the reference, all deliberate:
   * FreeverbAugment: one mono bank of eight combs and four all-passes at 16 kHz instead of sox's `reverb` chain: no pre-delay, no
     tone filters, no stereo spread, no dither, no clipping, no peak normalisation, and the tail beyond the window is cut off (as
     natural_reverb cuts it);
+  * BandrejectSincAugment: a Kaiser-windowed sinc FIR of this package's design instead of sox's `sinc` / `dither` chain: no
+    dither, no clipping, no peak normalisation, zeros outside the window;
   * `--augment_type none` gives None (the reference's factory raises on the one-element list ['none']).
 """
 import collections
@@ -53,6 +59,7 @@ from ._lib import check, ptr, stream_ptr
 
 BUILT_TYPES = ('additive', 'natural_reverb', 'time_dropout', 'pitch_wsola')
 OWN_TYPES = ('freeverb',)              # built as well; a tuple of its own, listed after BUILT_TYPES wherever the types are named
+FILTER_TYPES = ('bandreject_sinc',)   # built as well; a third tuple, named before BUILT_TYPES wherever the types are listed
 UNBUILT_TYPES = ('bandreject', 'pitch', 'pitch_quick', 'pitch_dropout', 'pitch_deropout', 'artificial_reverb',
                  'artificial_reverb_dropout', 'random_noise')
 
@@ -65,10 +72,10 @@ FlatWindows = collections.namedtuple("FlatWindows", "data offsets")     # window
 def unbuilt_message(augment_type):
     """The refusal of a request that names a type without a kernel path (train.refuseUnsupported, augmentation_factory)."""
     asked = [augment_type] if isinstance(augment_type, str) else list(augment_type)
-    missing = [t for t in asked if t not in BUILT_TYPES + OWN_TYPES and t != 'none']
+    missing = [t for t in asked if t not in BUILT_TYPES + OWN_TYPES + FILTER_TYPES and t != 'none']
     return (f"--augment_past / --augment_future with --augment_type {' '.join(asked)}: {', '.join(missing)} "
             f"{'is' if len(missing) == 1 else 'are'} not built (sox / WavAugment effects); the augmentation types on the MI355X "
-            f"feeder path are {', '.join(BUILT_TYPES)}, {', '.join(OWN_TYPES)} and none, alone or combined")
+            f"feeder path are {', '.join(FILTER_TYPES + BUILT_TYPES)}, {', '.join(OWN_TYPES)} and none, alone or combined")
 
 
 # --------------------------------------------------------------------------- device helpers
@@ -612,6 +619,127 @@ class FreeverbAugment(_Transform):
         return out
 
 
+# --------------------------------------------------------------------------- band reject
+BANDREJECT_SR = 16000                                                # the transform is defined at 16 kHz only
+BANDREJECT_MEL_STEPS, BANDREJECT_WIDTH = 256, 27                     # the reference's n_mels and F (data_augmentation.py:40-49)
+BANDREJECT_MAX_HALF = 1024                                           # cpc_bandreject_max_half()
+
+
+def bandreject_tables(low, high, attenuation_dB=120.0, transition_hz=400.0, sr=BANDREJECT_SR):
+    """The host tables of a batch of bands (BandrejectSincAugment's docstring), in f64: band [n, 2] (low, high in Hz), beta, half
+    (H) and taps (2 H + 1).  Refuses, by the argument's name, a band that is not finite or outside 0 <= low <= high <= sr / 2, an
+    attenuation outside (50, 140] and a transition width whose half length falls outside [1, 1024]."""
+    low = np.asarray(low, dtype=np.float64).reshape(-1)
+    high = np.asarray(high, dtype=np.float64).reshape(-1)
+    if not np.isfinite(sr) or sr <= 0:
+        raise ValueError(f"sr {sr}: bandreject_sinc needs a positive sample rate")
+    if not np.isfinite(low).all() or (low < 0).any():
+        raise ValueError(f"low {low[~(np.isfinite(low) & (low >= 0))][0]}: bandreject_sinc takes a band 0 <= low <= high <= sr / 2")
+    if not np.isfinite(high).all() or (high > sr / 2).any():
+        raise ValueError(f"high {high[~(np.isfinite(high) & (high <= sr / 2))][0]}: bandreject_sinc takes a band "
+                         f"0 <= low <= high <= sr / 2 = {sr / 2}")
+    if low.size != high.size:
+        raise ValueError(f"high: {high.size} upper edges for {low.size} lower edges")
+    if (low > high).any():
+        raise ValueError(f"low {low[low > high][0]} above high {high[low > high][0]}: bandreject_sinc takes a band "
+                         "0 <= low <= high <= sr / 2")
+    if not 50 < attenuation_dB <= 140:
+        raise ValueError(f"attenuation_dB {attenuation_dB}: bandreject_sinc takes more than 50 and at most 140 dB")
+    if not transition_hz > 0 or not np.isfinite(transition_hz):
+        raise ValueError(f"transition_hz {transition_hz}: bandreject_sinc needs a positive finite transition width")
+    beta = 0.1102 * (attenuation_dB - 8.7)
+    dw = 2 * np.pi * transition_hz / sr
+    order = np.ceil((attenuation_dB - 7.95) / (2.285 * dw))
+    if not order < 2 ** 31:
+        raise ValueError(f"transition_hz {transition_hz}: a filter of {order:.3g} taps; at most {2 * BANDREJECT_MAX_HALF + 1} are built")
+    half = (int(order) + 1) // 2
+    if not 1 <= half <= BANDREJECT_MAX_HALF:
+        raise ValueError(f"transition_hz {transition_hz}: {attenuation_dB} dB over {transition_hz} Hz at {sr} Hz needs a half length of "
+                         f"{half} taps; 1 to {BANDREJECT_MAX_HALF} are built")
+    return {"band": np.stack([low, high], axis=1), "half": half, "beta": float(beta), "taps": 2 * half + 1}
+
+
+def _bandreject_launch(src, band, lo, hi, tables, window, out, what="augment_bandreject"):
+    """cpc_augment_bandreject on rows [lo, hi) of the device table band [n, 2] (float64)."""
+    dev = _device_of(src)
+    p, total, off = _operand(src)
+    check(_lib.load().cpc_augment_bandreject(p, total, off, ptr(band[lo:hi]), int(tables["half"]), float(tables["beta"]),
+                                             float(BANDREJECT_SR), ptr(out), hi - lo, window, stream_ptr(dev)), what)
+    return out
+
+
+class BandrejectSincAugment(_Transform):
+    """`bandreject_sinc`: one frequency band of every window rejected, with the band drawn as the reference's BandrejectAugment
+    (data_augmentation.py:40-49, `generate_freq_mask`) draws it -- TWO np.random.uniform calls per window from numpy's global
+    generator, on the mel scale; the output has the input's length and is not peak-normalised.  The reference hands the band to a
+    sox effect chain (`sinc -a 120 high-low`, then `dither`) that is not available.  The textbook filter behind that chain is a
+    Kaiser-windowed sinc band-reject FIR, and what happens to the window here is THIS PACKAGE'S statement of one, written down
+    below.  Its agreement with sox's output is unmeasured, and there is no dither.  The transform is defined at sr = 16000 only.
+
+    The draw, per window and in this order:
+      F = 27 scaler    melfmax = 2595 log10(1 + 8000 / 700)
+      meldf = uniform(0, melfmax F / 256)    melf0 = uniform(0, melfmax - meldf)
+      low = mel2freq(melf0)    high = mel2freq(melf0 + meldf)    mel2freq(m) = (10 ** (m / 2595) - 1) 700
+    `scaler` (--bandreject_scaler) must be finite with 0 <= 27 scaler <= 256, or the draw would leave [0, 8000].
+
+    The filter, from the attenuation A in dB (120) and the transition width tbw in Hz (400, 5 % of the 8 kHz band), on the host
+    in f64 (`bandreject_tables`):
+      beta = 0.1102 (A - 8.7)    dw = 2 pi tbw / sr    M = ceil((A - 7.95) / (2.285 dw))    H = (M + 1) // 2    T = 2 H + 1 taps
+    The defaults give beta = 12.26526, M = 313, H = 157, T = 315.  For j = -H .. H:
+      w[j]    = I0(beta sqrt(1 - (j / H) ** 2)) / I0(beta)
+      lp_f[j] = (2 f / sr) sinc(2 f j / sr)        sinc(u) = sin(pi u) / (pi u), sinc(0) = 1
+      h[j]    = [j == 0] - w[j] (lp_high[j] - lp_low[j])                  (no renormalisation)
+      y[t]    = round_f32( sum_{j = -H .. H} h[j] x[t - j] ),  t = 0 .. W - 1
+    Every product and sum is in f64 in one fixed order; x is f32 and reads as zero outside the window's own [0, W), whatever lies
+    beside it in a pack.  No dither, no clipping, no peak normalisation.  A window with low == high is the identity and is COPIED
+    with no arithmetic; so is a window whose pair is no band (the table lives on the device and is not read back).
+
+    On the device (csrc/bandreject.hip) every workgroup designs its window's H + 1 taps in f64 -- I0 from its power series, the
+    sine from an argument reduced exactly, each tap within 2 ** -40 of its value -- and sums h[0] x[t], then
+    fma(h[j], x[t - j] + x[t + j], .) for j = 1 .. H, rounding once at the store, so a window's bits depend on nothing else in the
+    batch or the pack and a plan costs two doubles per window.
+
+    Entry: (low, high).  Plan: low [n] f64, high [n] f64, band [n, 2] f64, half, beta, taps.  Out of place."""
+
+    def __init__(self, scaler=1.0, attenuation_dB=120.0, transition_hz=400.0):
+        if not np.isfinite(scaler) or not 0 <= BANDREJECT_WIDTH * scaler <= BANDREJECT_MEL_STEPS:
+            raise ValueError(f"scaler {scaler}: bandreject_sinc draws a band of at most 27 scaler of 256 mel steps, scaler from 0 to "
+                             f"{BANDREJECT_MEL_STEPS / BANDREJECT_WIDTH:.4f}")
+        bandreject_tables([], [], attenuation_dB, transition_hz)        # (refuses the other two by name)
+        self.scaler = float(scaler)
+        self.attenuation_dB = float(attenuation_dB)
+        self.transition_hz = float(transition_hz)
+
+    @staticmethod
+    def mel2freq(mel):
+        return (10 ** (mel / 2595) - 1) * 700
+
+    def draw_one(self, window):
+        width = BANDREJECT_WIDTH * self.scaler
+        melfmax = 2595 * np.log10(1 + (BANDREJECT_SR / 2) / 700)
+        meldf = np.random.uniform(0, melfmax * width / BANDREJECT_MEL_STEPS)
+        melf0 = np.random.uniform(0, melfmax - meldf)
+        return float(self.mel2freq(melf0)), float(self.mel2freq(melf0 + meldf))
+
+    def seal(self, entries, device):
+        arr = np.array(entries, dtype=np.float64).reshape(-1, 2)
+        plan = {"kind": "bandreject_sinc", "n": len(arr)}
+        high = np.minimum(arr[:, 1], BANDREJECT_SR / 2)                # (a draw at the very top of the scale may round a hair past 8000 Hz)
+        plan.update(bandreject_tables(arr[:, 0], high, self.attenuation_dB, self.transition_hz))
+        plan["low"], plan["high"] = plan["band"][:, 0].copy(), plan["band"][:, 1].copy()
+        plan["_dev"] = {"band": _upload(plan["band"], device)}
+        return plan
+
+    def apply(self, plan, lo, hi, src, dst=None, window=None):
+        _check_src(src)
+        window = _window(src, dst, window)
+        if not isinstance(src, FlatWindows) and dst is not None and src.data_ptr() == dst.data_ptr():
+            src = src.clone()                                          # (out of place: every output reads many input samples)
+        out = dst if dst is not None else torch.empty(hi - lo, window, dtype=torch.float32, device=_device_of(src))
+        _bandreject_launch(src, plan["_dev"]["band"], lo, hi, plan, window, out)
+        return out
+
+
 # --------------------------------------------------------------------------- combinations
 class CombinedTransforms(_Transform):
     """data_augmentation.py:331-344: the transforms of `augment_cfgs`, applied in the order given ('none' entries skipped).
@@ -669,6 +797,8 @@ def get_augment(augment_type, **kwargs):
         return PitchShiftAugment(kwargs['shift_max'])
     if augment_type == 'freeverb':
         return FreeverbAugment()
+    if augment_type == 'bandreject_sinc':
+        return BandrejectSincAugment(kwargs.get('bandreject_scaler', 1.0))
     if augment_type in UNBUILT_TYPES:
         raise NotImplementedError(unbuilt_message(augment_type))
     raise RuntimeError(f'Unknown augment_type = {augment_type}')
@@ -699,6 +829,7 @@ def augmentation_factory(args, noise_dataset=None, applied_on_noise=False):
     batchSize = args.nGPU * args.batchSizeGPU
     additive_noise_sampling = "temporalsamespeaker" if args.temporal_additive_noise else "uniform"
     aug_args = {"t_ms": args.t_ms,
+                "bandreject_scaler": args.bandreject_scaler,
                 "shift_max": args.shift_max,
                 "noise_dataset": noise_dataset,
                 "additive_noise_snr_min": args.min_snr_in_db,

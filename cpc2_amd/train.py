@@ -964,9 +964,9 @@ def refuseUnsupported(args):
         raise SystemExit(f"--nGPU {args.nGPU}: this package runs one GPU per process (there is no DataParallel wrapper); run "
                          f"with --nGPU 1, or one process per GPU: python -m torch.distributed.run --nproc_per_node {args.nGPU} "
                          "-m cpc2_amd.train --distributed ...")
-    from .data_augmentation import BUILT_TYPES, OWN_TYPES, unbuilt_message
+    from .data_augmentation import BUILT_TYPES, FILTER_TYPES, OWN_TYPES, unbuilt_message
     asked = list(args.augment_type) if args.augment_type is not None else []
-    if (args.augment_past or args.augment_future) and any(t not in BUILT_TYPES + OWN_TYPES and t != 'none' for t in asked):
+    if (args.augment_past or args.augment_future) and any(t not in BUILT_TYPES + OWN_TYPES + FILTER_TYPES and t != 'none' for t in asked):
         raise NotImplementedError(unbuilt_message(asked))
     if args.encoder_type in ("mfcc", "lfb"):
         raise NotImplementedError(f"--encoder_type {args.encoder_type}: only the raw-waveform encoder (--encoder_type cpc) is built")

@@ -63,7 +63,9 @@ int cpc_version(void);          /* 100 x major + minor; 105 = the entry points o
                                   * 124 = cpc_seg_dissimilarity / cpc_seg_boundaries / cpc_seg_lds_entries;
                                   * 125 = cpc_augment_freeverb;
                                   * 126 = cpc_unit_counts / cpc_unit_boundaries (+ scratch queries) / cpc_unit_counts_lds_cells /
-                                  * cpc_unit_counts_chunk */
+                                  * cpc_unit_counts_chunk;
+                                  * 127 = cpc_bandreject_tile / cpc_bandreject_max_half / cpc_bandreject_taps /
+                                  * cpc_augment_bandreject */
 const char *cpc_last_error(void);
 
 /* In-situ kernel timing for bench.py: when enabled, the launchers bracket each launch of the named
@@ -772,6 +774,43 @@ int cpc_augment_pitch(const float *src, long src_total, const long *src_off, con
 int cpc_augment_freeverb(const float *src, long src_total, const long *src_off, const int *comb_len, int len_bound,
                          const int *allpass_len, float feedback, float damping, float gain, float *out, int batch, int window,
                          cpc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Band-reject filtering of windows (the `bandreject_sinc` augmentation; cpc2_amd/data_augmentation.py BandrejectSincAugment,
+ * csrc/bandreject.hip).  version 127.  The reference's BandrejectAugment is a sox effect chain (`sinc -a 120 high-low`, then
+ * `dither`) that is not available; the textbook filter behind it is a Kaiser-windowed sinc band-reject FIR, and this is THIS
+ * LIBRARY'S statement of one.  Its agreement with sox's output is unmeasured, and there is no dither.  The caller's scalars
+ * (data_augmentation.bandreject_tables, in double), from an attenuation A in dB and a transition width tbw in Hz:
+ *   beta = 0.1102 (A - 8.7);  dw = 2 pi tbw / sr;  M = ceil((A - 7.95) / (2.285 dw));  half = H = (M + 1) / 2 (integer division)
+ *   (A = 120, tbw = 400, sr = 16000: beta = 12.26526, M = 313, H = 157, 2 H + 1 = 315 taps)
+ * band is a DEVICE table [batch][2] of doubles, (low, high) in Hz per window, 0 <= low <= high <= sr / 2.  For j = -H .. H, in f64:
+ *   w[j]    = I0(beta sqrt(1 - (j / H)^2)) / I0(beta)
+ *   lp_f[j] = (2 f / sr) sinc(2 f j / sr)          sinc(u) = sin(pi u) / (pi u), sinc(0) = 1
+ *   h[j]    = [j == 0] - w[j] (lp_high[j] - lp_low[j])                          (no renormalisation)
+ *   out[i][t] = round_f32( sum_{j = -H .. H} h[j] x[t - j] ),  t = 0 .. window - 1
+ * Window i is x[0 .. W) of the source (f32) and reads as ZERO outside its own [0, W), whatever lies beside it in the vector.
+ * Every product and sum is in f64 in one fixed order -- h[0] x[t], then fma(h[j], x[t - j] + x[t + j], .) for j = 1 .. H, the sum
+ * of two f32 values being exact in f64 -- and the result is rounded once, at the store.  On the device I0 is its power series, summed
+ * until a term falls below 2^-60 of the sum, and the sine takes the argument reduced exactly (u - 2 rint(u / 2)): a tap is within
+ * 2^-40 of its value.  No dither, no clipping, no peak normalisation; the output has the input's length.  A row with low == high
+ * is the identity and is COPIED with no arithmetic, and so is a row whose pair is no band (low < 0, low > high, high > sr / 2, a
+ * NaN): the table lives on the device and is not read back.  A row's bits depend on nothing else in the batch, the vector or the
+ * launch.
+ *   cpc_bandreject_tile      outputs per workgroup (the seams of the filter kernel, for tests)
+ *   cpc_bandreject_max_half  the largest half length, 1024
+ *   cpc_bandreject_taps      taps [batch][half + 1] (DEVICE, doubles) receives h[0 .. half] of every row, from the same device
+ *                            function the filter kernel designs its taps with; a copied row reads 1, 0, 0, ...
+ * Both entries refuse with CPC_ERR_INVALID, nothing launched and nothing written: window <= 0, batch < 0 or > 65535, half outside
+ * [1, 1024], beta not finite or outside [0, 50], sample_rate not finite or <= 0, a null pointer with batch > 0, out == src, offsets
+ * without the vector's length.  batch == 0 is a no-op.  The source is given as the other augment entries take it: (vector, total,
+ * offsets) with zeros outside [0, total), or a [batch][window] buffer with offsets == NULL.
+ * ------------------------------------------------------------------------------------------ */
+int cpc_bandreject_tile(void);
+int cpc_bandreject_max_half(void);
+int cpc_bandreject_taps(const double *band, int batch, int half, double beta, double sample_rate, double *taps,
+                        cpc_stream_t stream);
+int cpc_augment_bandreject(const float *src, long src_total, const long *src_off, const double *band, int half, double beta,
+                           double sample_rate, float *out, int batch, int window, cpc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Sample-rate conversion (torchaudio's sinc_interp_hann resampler, the transform of the reference's

@@ -116,7 +116,8 @@ def kernel_case(b, warmup, iters, rounds, host_rows):
     return res
 
 
-def feeder_arms(batch, steps, rounds, quick):
+def feeder_arms(batch, steps, rounds, quick, arms=None):
+    """`arms`: {name: transform or None} with a "none" arm, for another augmentation's tool (tools/bandreject_bench.py)."""
     import bench
     from cpc2_amd.dataset import AudioBatchData, findAllSeqs
     from cpc2_amd.train import DataParallelContext, trainStep
@@ -127,10 +128,11 @@ def feeder_arms(batch, steps, rounds, quick):
         random.seed(11)
         np.random.seed(11)
         seqs, speakers = findAllSeqs(os.path.join(tmp, "speech"), extension=".wav")
-        arms = {"none": None, "freeverb": da.FreeverbAugment(),
-                "freeverb+time_dropout": da.CombinedTransforms(["freeverb", "time_dropout"], t_ms=100)}
-        if quick:
-            arms = {k: arms[k] for k in ("none", "freeverb")}
+        if arms is None:
+            arms = {"none": None, "freeverb": da.FreeverbAugment(),
+                    "freeverb+time_dropout": da.CombinedTransforms(["freeverb", "time_dropout"], t_ms=100)}
+            if quick:
+                arms = {k: arms[k] for k in ("none", "freeverb")}
         with contextlib.redirect_stdout(io.StringIO()):
             base = AudioBatchData(os.path.join(tmp, "speech"), W, seqs, None, len(speakers), device=DEV)
         data = {}
