@@ -1032,6 +1032,7 @@ struct EncLayout {
     unsigned short *dUp;    long dUplane, dUrows;         // scratch: dU of the current layer (largest: layer 1)
 };
 
+// The backward pass takes 400 samples on (two frames), at every window count: see encoder_backward.
 constexpr int kEncBackwardMinLength = 400;
 constexpr int NORM_BWD_BLOCKS = 2048;   // 8 per CU: the row loop is a load -> use chain, only occupancy hides its latency
 constexpr int CONV0_BWD_BLOCKS = 768;
@@ -1040,6 +1041,13 @@ static bool supported_hidden(int H) { return H == 32 || H == 64 || H == 128 || H
 static int log2i(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 // the encoder's GEMMs run on pre-split planes when the hidden size is made of 256-column tiles
 static bool use_planes(int H) { return H % 256 == 0; }
+// Reduction rows of layer i's plane-fed weight-gradient product: the N (L_out + 2) virtual rows of the layer, and never fewer than the
+// 64 the product takes (gemm_tn_planes_ok).  The rows in between are zero rows of dU against finite (zero) rows of Y_{i-1}, which is
+// what the product's contract asks of the rows behind R anyway; at 64 rows it runs as one slab of four stages (tn_planes_splits),
+// the form of (512, 2, 4800).  Few windows of a short input -- one window of 400 samples has 4 rows -- so run like any other shape.
+static long tn_rows(int N, int Rv) { return std::max<long>((long)N * Rv, 64); }
+// rows of a phase of the planes that product reads: whole 32-row steps of virtual rows (+ a tap beyond)
+static long tn_plane_rows(int N, int Rv) { return (cdiv(tn_rows(N, Rv), 32) * 32 + 4 + 15) / 16 * 16; }
 
 static int enc_layout(EncLayout &e, int N, int length, int H, void *saved, void *scratch)
 {
@@ -1068,9 +1076,8 @@ static int enc_layout(EncLayout &e, int N, int length, int H, void *saved, void 
     for (int i = 0; i < 4; ++i) {
         e.Y[i] = nullptr; e.Yp[i] = nullptr;
         if (!e.planes) { e.Y[i] = sv.take<float>(((size_t)N * e.R[i] + kConv[i + 1].k) * H); continue; }   // + slack rows
-        // rows of a phase: the weight-gradient product reads whole 32-row steps of virtual rows (+ a tap beyond)
         const int s = kConv[i + 1].s;
-        e.Yrts[i] = (cdiv((long)N * e.Rv[i + 1], 32) * 32 + 4 + 15) / 16 * 16;
+        e.Yrts[i] = tn_plane_rows(N, e.Rv[i + 1]);
         e.Yplane[i] = (long)(H / 16) * s * e.Yrts[i] * 16;
         e.Yp[i] = sv.take<unsigned short>((size_t)3 * e.Yplane[i]);
     }
@@ -1099,7 +1106,7 @@ static int enc_layout(EncLayout &e, int N, int length, int H, void *saved, void 
     e.dYb = sc.take<float>((size_t)N * e.L[2] * H);
     e.dU = nullptr; e.dUp = nullptr; e.dUrows = 0; e.dUplane = 0;
     if (e.planes) {
-        e.dUrows = (cdiv((long)N * e.Rv[1], 32) * 32 + 4 + 15) / 16 * 16;
+        e.dUrows = tn_plane_rows(N, e.Rv[1]);
         e.dUplane = (long)(H / 16) * e.dUrows * 16;
         e.dUp = sc.take<unsigned short>((size_t)3 * e.dUplane);
     } else {
@@ -1114,7 +1121,7 @@ static int enc_layout(EncLayout &e, int N, int length, int H, void *saved, void 
         e.tn_bytes = std::max(e.tn_bytes, std::max(gemm_tn_scratch_bytes(H, kConv[i].k * H, (long)N * e.Rv[i]),
                                                     gemm_nt_scratch_bytes((long)N * e.Rv[i], H, kConv[i].k * H)));   // + forward K split
         if (e.planes)
-            e.tn_bytes = std::max(e.tn_bytes, std::max(gemm_tn_planes_scratch_bytes(H, kConv[i].k * H, (long)N * e.Rv[i]),
+            e.tn_bytes = std::max(e.tn_bytes, std::max(gemm_tn_planes_scratch_bytes(H, kConv[i].k * H, tn_rows(N, e.Rv[i])),
                                                         gemm_nt_planes_scratch_bytes((long)N * e.L[i + 1], H, kConv[i].k * H, (long)N * e.Rv[i])));
     }
     e.tn = sc.take<float>(e.tn_bytes / sizeof(float));
@@ -1125,7 +1132,7 @@ static int enc_layout(EncLayout &e, int N, int length, int H, void *saved, void 
         if (e.planes) {
             e.part_l[i] = sc.take<float>((size_t)NORM_BWD_BLOCKS * 3 * H);
             e.cs_l[i] = sc.take<float>(colsum_split_scratch_bytes(3 * H) / sizeof(float));
-            e.tn_l_bytes[i] = gemm_tn_planes_scratch_bytes(H, kConv[i].k * H, (long)N * e.Rv[i]);
+            e.tn_l_bytes[i] = gemm_tn_planes_scratch_bytes(H, kConv[i].k * H, tn_rows(N, e.Rv[i]));
             e.tn_l[i] = sc.take<float>(e.tn_l_bytes[i] / sizeof(float));
         }
     }
@@ -1253,9 +1260,10 @@ static int encoder_backward(const float *x, const float *x2, int n_first, const 
                             void *scratch, float *const *grads, int N, int length, int H, float eps, bool defer_small, hipStream_t st)
 {
     CPC_TRY(enc_check_split(x2, n_first, N));
-    // the forward pass takes every length that leaves a frame (feature extraction, under no_grad).  The backward is verified from 400
-    // samples on; below, the plane-fed weight-gradient product (gemm_tn_planes: >= 64 reduction rows, N (L_out + 2) of conv4) would
-    // refuse one- and two-frame inputs half-way through unless 16-22 windows came together -- refused here, by name, before any launch
+    // the forward pass takes every length that leaves a frame (feature extraction, under no_grad).  The backward takes 400 samples
+    // on, at every window count, and is held to fp64 there (tests/test_encoder_abi_gpu.py); shorter inputs are refused here, by
+    // name, before any launch.  (The plane-fed weight-gradient product wants >= 64 reduction rows and a layer has N (L_out + 2):
+    // tn_rows pads the reduction with zero rows where windows are few, so nothing is refused half-way through.)
     CPC_REQUIRE(length >= kEncBackwardMinLength, "encoder_backward: inputs shorter than %d samples are forward-only (got %d)", kEncBackwardMinLength, length);
     EncLayout e;
     CPC_TRY(enc_layout(e, N, length, H, saved, scratch));
@@ -1274,7 +1282,7 @@ static int encoder_backward(const float *x, const float *x2, int n_first, const 
         if (side) na.part = e.part_l[i];
         if (e.planes) {
             // dU of layer i as planes: rows of the layer, + the zero rows the weight-gradient product's last step reads
-            const long durows = (cdiv((long)N * e.Rv[i], 32) * 32 + 4 + 15) / 16 * 16;
+            const long durows = tn_plane_rows(N, e.Rv[i]);
             const PlaneOut o{e.dUp, e.dUplane, 0, e.dUrows};
             CPC_DISPATCH_HP(H, hipLaunchKernelGGL(norm_bwd_pl_kernel<HH>, dim3(NORM_BWD_BLOCKS), dim3(256), 0, st, na, o, durows / 16));
             CPC_CHECK_LAUNCH("norm_bwd_pl_kernel");
@@ -1282,7 +1290,7 @@ static int encoder_backward(const float *x, const float *x2, int n_first, const 
             // weight gradient over the virtual rows (dU is zero on a sample's border rows): dW[co][j*H+ci] = sum_m dU(m+1)[co] Y(m s + j)[ci]
             const PlanesTNOperand TA{e.dUp, e.dUplane, 0, e.dUrows, 1, H};
             const PlanesTNOperand TB{e.Yp[i - 1], e.Yplane[i - 1], log2i(s), e.Yrts[i - 1], 0, H};
-            CPC_TRY(gemm_tn_planes(TA, TB, grads[4 * i], 0, H, k * H, (long)N * e.Rv[i], side ? e.tn_l[i] : e.tn, side ? e.tn_l_bytes[i] : e.tn_bytes,
+            CPC_TRY(gemm_tn_planes(TA, TB, grads[4 * i], 0, H, k * H, tn_rows(N, e.Rv[i]), side ? e.tn_l[i] : e.tn, side ? e.tn_l_bytes[i] : e.tn_bytes,
                                    H, k, st, side ? &left[i] : nullptr));
             if (side && i == 1) {
                 // everything the layers have left behind -- their partial sums and K-split slabs, each in a buffer of its own -- is
@@ -1423,6 +1431,11 @@ extern "C" int cpc_encoder_saved_layout(int n_windows, int length, int hidden, i
         out[5] = e.Yplane[layer];
         out[6] = e.Yrts[layer];
         out[7] = cpc::log2i(cpc::kConv[layer + 1].s);
+        out[8] = e.R[layer];
+        out[9] = cpc::kConv[layer + 1].p;
+    }
+    if (!e.planes && layer < 4) {       // the f32 rows of the layer's output: row n * out[8] + out[9] + t
+        out[5] = (long)(reinterpret_cast<const char *>(e.Y[layer]) - base);
         out[8] = e.R[layer];
         out[9] = cpc::kConv[layer + 1].p;
     }

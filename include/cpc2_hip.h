@@ -203,7 +203,15 @@ int cpc_channelnorm_backward(const float *x, const float *w, const float *dy, co
  *   scratch  temporaries (cpc_encoder_scratch_bytes; same query serves forward and backward)
  *   grads    20 pointers, same order/shapes as params; overwritten (not accumulated)
  * Lengths: the forward pass takes every length that leaves a frame, i.e. 159 samples on (cpc_encoder_frames(158) == 0, and the
- * size queries return 0 below 159); the backward passes take 400 samples on and refuse shorter inputs (CPC_ERR_INVALID).
+ * size queries return 0 below 159); the backward pass takes 400 samples on and refuses shorter inputs (CPC_ERR_INVALID) before
+ * anything is launched.  Both take any n_windows >= 1 at every length they take and hidden 32, 64, 128, 256, 512 (at 256 / 512
+ * few windows of a short input give the weight-gradient products fewer than the 64 reduction rows they want: the driver pads them
+ * with zero rows).
+ * The contents of saved and scratch are unspecified on entry: forward writes all of saved that backward reads, every row a
+ * product reads as padding (halo, slack) included; nothing is kept in scratch between the passes, so the caller may reuse or
+ * overwrite it in between (with deferred != 0: after cpc_side_tail_join); neither pass writes outside the sizes the queries
+ * report, or to x, params or dz.  grads are overwritten, not accumulated.  tests/test_encoder_abi_gpu.py holds the two entry
+ * points to this, and to the fp64 oracle, over the domain stated here.
  * ------------------------------------------------------------------------------------------ */
 int cpc_encoder_frames(int length);
 size_t cpc_encoder_saved_bytes(int n_windows, int length, int hidden);
@@ -224,7 +232,10 @@ int cpc_encoder_backward(const float *x_first, const float *x_rest, int n_first,
  *   [1] byte offset of rstd [n_windows * out[2]] f32 (-1: layer 0), [2] rows per window, [3] frames per window,
  *   [4] byte offset of the three bf16 planes of the layer's output (-1: stored as f32, or layer 4), [5] elements per plane,
  *   [6] rows per phase, [7] log2 of the reading stride s; channel ch of frame t of window n is element
- *   ((((ch / 16) << [7]) + (R & (s - 1))) * [6] + (R >> [7])) * 16 + ch % 16 with R = n * [8] + [9] + t. */
+ *   ((((ch / 16) << [7]) + (R & (s - 1))) * [6] + (R >> [7])) * 16 + ch % 16 with R = n * [8] + [9] + t.
+ * hidden 32 / 64 / 128, layers 0..3 ([4] == -1: the output is kept as f32 rows): [5] byte offset of those rows, [hidden] f32 each,
+ * [8] rows per window, [9] halo rows in front of a window's frames -- channel ch of frame t of window n is element
+ * (n * [8] + [9] + t) * hidden + ch; [6] and [7] are 0. */
 int cpc_encoder_saved_layout(int n_windows, int length, int hidden, int layer, long *out);
 
 /* ------------------------------------------------------------------------------------------
