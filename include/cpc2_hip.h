@@ -65,7 +65,8 @@ int cpc_version(void);          /* 100 x major + minor; 105 = the entry points o
                                   * 126 = cpc_unit_counts / cpc_unit_boundaries (+ scratch queries) / cpc_unit_counts_lds_cells /
                                   * cpc_unit_counts_chunk;
                                   * 127 = cpc_bandreject_tile / cpc_bandreject_max_half / cpc_bandreject_taps /
-                                  * cpc_augment_bandreject */
+                                  * cpc_augment_bandreject;
+                                  * 128 = cpc_sdtw (+ scratch query) */
 const char *cpc_last_error(void);
 
 /* In-situ kernel timing for bench.py: when enabled, the launchers bracket each launch of the named
@@ -530,6 +531,37 @@ int cpc_abx_dtw_units(const int *units, const int *item_off, const int *item_len
                       const int *seg_x, const int *seg_start, const int *pair_y, int n_seg,
                       int max_len_x, int max_len_y, float d_same, float d_diff,
                       float *out, int *path_len, void *scratch, size_t scratch_bytes, cpc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Query-by-example term detection: subsequence DTW of a query inside a document (csrc/sdtw.hip, version 128; DESIGN.md
+ * section 26).  The reference has no such task.  Items and the work list are laid out as for cpc_abx_dtw: segment s compares
+ * QUERY item seg_q[s] with the DOCUMENT items pair_doc[seg_start[s] .. seg_start[s+1]-1]; a query's document list may be split
+ * over several segments.  Pair p's results go to score[p] and span[3p .. 3p+2] = (start, end, length).
+ *
+ * Cells.  For a query of n >= 1 frames and a document of m >= 1 frames, d[i][j] is the frame distance of cpc_abx_dtw
+ * (CPC_ABX_COSINE or CPC_ABX_EUCLIDIAN, f32, k-ordered fma chain, inputs normalised by the caller).  Every cell carries
+ * (cost, length, start).
+ * Recurrence.  Row 0: cost = d[0][j], length = 1, start = j (the start is free: no left predecessor on row 0).
+ *   i > 0, j = 0: the predecessor is up (i-1, 0).  Otherwise the predecessor is the one of smallest cost among diag (i-1, j-1),
+ *   left (i, j-1) and up (i-1, j); ties go to diag, then left, then up.  cost = d[i][j] + pred.cost (one f32 addition),
+ *   length = pred.length + 1, start = pred.start.
+ * Detection.  v[j] = cost[n-1][j] / length[n-1][j] (one f32 division); score = min_j v[j], the first j among equals;
+ *   start = start[n-1][j], end = j, length = length[n-1][j].  m < n is allowed: the path may go straight up.
+ *   No slope or band constraint is applied, and one detection is returned per pair.
+ * Not computable.  A pair whose item index or length is out of range (an index outside [0, n_items), a length < 1, or a query
+ *   longer than 64 frames against a document longer than max_len_doc) gets score NaN and span (-1, -1, -1).
+ *
+ * Any query length >= 1; max_len_q / max_len_doc bound the query / document lengths and size the scratch:
+ * cpc_sdtw_scratch_bytes = 0 when max_len_q <= 64, else 2 * 12 * max_len_doc bytes per workgroup (the boundary row of a 64-row
+ * strip of the query, double-buffered); negative sizes give 0 and a cpc_last_error text.  Frames beyond an item are never read;
+ * the scratch's contents before the launch are never read; no atomics: two launches give the same bits.  A bad argument
+ * returns CPC_ERR_INVALID with a message and launches nothing.
+ * ------------------------------------------------------------------------------------------ */
+size_t cpc_sdtw_scratch_bytes(int n_seg, int max_len_q, int max_len_doc);
+int cpc_sdtw(const float *frames, int dp, const int *item_off, const int *item_len, int n_items, const int *seg_q,
+             const int *seg_start, const int *pair_doc, int n_seg, int max_len_q, int max_len_doc, int distance,
+             float *score, int *span /* [pairs][3] int32: start, end, length */, void *scratch, size_t scratch_bytes,
+             cpc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * k-means on features (cpc/clustering/clustering.py of the reference).  x [n][d] rows, ck [k][d] centroids, all fp32 DEVICE
