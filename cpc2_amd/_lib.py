@@ -179,6 +179,10 @@ SIGNATURES = {
     "cpc_unit_boundaries_scratch_bytes": (c_size_t, [c_int, c_long]),
     "cpc_unit_boundaries": (c_int, [c_ptr, c_long, c_ptr, c_ptr, c_long, c_ptr, c_ptr, c_int, c_long, c_int, c_ptr, c_ptr, c_size_t,
                                     c_ptr]),
+    "cpc_segment_units_wave_k": (c_int, []),
+    "cpc_segment_units_scratch_bytes": (c_size_t, [c_int, c_long, c_int, c_int]),
+    "cpc_segment_units": (c_int, [c_ptr, c_long, c_long, c_int, c_ptr, c_ptr, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size_t,
+                            c_ptr]),
 }
 
 _lib = None

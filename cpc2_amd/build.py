@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcpc2_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-SOURCES = ["gemm_f32.hip", "gemm_planes.hip", "rowops.hip", "encoder.hip", "gru.hip", "lstm.hip", "infonce.hip", "side_stream.hip", "transformer.hip", "abx.hip", "abx_units.hip", "sdtw.hip", "kmeans.hip", "moments.hip", "seqmoments.hip", "mfcc.hip", "probe.hip", "augment.hip", "pitch.hip", "freeverb.hip", "bandreject.hip", "resample.hip", "text.hip", "seqalign.hip", "ctc_head.hip", "ctc_align.hip", "segment.hip", "unit_scores.hip", "negidx.cpp", "flac.cpp"]
+SOURCES = ["gemm_f32.hip", "gemm_planes.hip", "rowops.hip", "encoder.hip", "gru.hip", "lstm.hip", "infonce.hip", "side_stream.hip", "transformer.hip", "abx.hip", "abx_units.hip", "sdtw.hip", "kmeans.hip", "moments.hip", "seqmoments.hip", "mfcc.hip", "probe.hip", "augment.hip", "pitch.hip", "freeverb.hip", "bandreject.hip", "resample.hip", "text.hip", "seqalign.hip", "ctc_head.hip", "ctc_align.hip", "segment.hip", "unit_scores.hip", "unit_dp.hip", "negidx.cpp", "flac.cpp"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-pthread"]
 # Device code is built WITHOUT the packed-f32 VALU instructions (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32).  Round 3 found
 # (profiles/r03_dp_rootcause.md; tools/load_determinism_probe.py reproduces it) that kernels which hipcc
@@ -27,8 +27,10 @@ DEVICE_FLAGS = ["--offload-arch=gfx950", "-Xclang", "-target-feature", "-Xclang"
 # rounding of its own, never fused into what surrounds it.
 # freeverb.hip states every sample as the float32 operations of its definition, in their order (s = o + (s - o) dmp is a
 # difference, a product and a sum): unfused, its output equals a float32 numpy evaluation of the definition.
+# unit_dp.hip states its recurrence as a comparison and ONE f64 addition per state and frame, which a numpy program repeats bit
+# for bit: the flag keeps any later product in that file from being fused into them.
 FILE_FLAGS = {"seqalign.hip": ["-ffp-contract=off"], "ctc_align.hip": ["-ffp-contract=off"], "pitch.hip": ["-ffp-contract=off"],
-              "segment.hip": ["-ffp-contract=off"], "freeverb.hip": ["-ffp-contract=off"]}
+              "segment.hip": ["-ffp-contract=off"], "freeverb.hip": ["-ffp-contract=off"], "unit_dp.hip": ["-ffp-contract=off"]}
 
 
 def _newer(target, deps):

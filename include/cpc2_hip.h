@@ -66,7 +66,8 @@ int cpc_version(void);          /* 100 x major + minor; 105 = the entry points o
                                   * cpc_unit_counts_chunk;
                                   * 127 = cpc_bandreject_tile / cpc_bandreject_max_half / cpc_bandreject_taps /
                                   * cpc_augment_bandreject;
-                                  * 128 = cpc_sdtw (+ scratch query) */
+                                  * 128 = cpc_sdtw (+ scratch query);
+                                  * 129 = cpc_segment_units (+ scratch query) / cpc_segment_units_wave_k */
 const char *cpc_last_error(void);
 
 /* In-situ kernel timing for bench.py: when enabled, the launchers bracket each launch of the named
@@ -1136,6 +1137,58 @@ size_t cpc_unit_boundaries_scratch_bytes(int n_utt, long total_frames);
 int cpc_unit_boundaries(const int *units, long n_unit_words, const int64_t *unit_off, const int *labels /* may be NULL */,
                         long n_label_words, const int64_t *label_off, const int *lengths, int n_utt, long total_frames, int tol,
                         int *out, void *scratch, size_t scratch_bytes, cpc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Duration-penalized unit segmentation (csrc/unit_dp.hip; cpc2_amd/unit_segmentation.py).  version 129.
+ * Every pointer but penalties_host is a DEVICE pointer.  The reference has no counterpart: the definition below is the
+ * specification.  It is the dynamic programme of Kamper & van Niekerk (Interspeech 2021) with their linear penalty
+ * pen(l) = -(l - 1) weighted by lambda, which sums over T frames and S segments to lambda S - lambda T: a constant charge lambda
+ * per segment, so the minimiser is a Viterbi pass over the K codes with a switch cost.
+ *
+ * Inputs for one utterance: costs c[t][k], f32, t in [0, T), k in [0, K); one penalty lambda >= 0, f64.  State values are f64:
+ *
+ *   V[0][k] = (double) c[0][k]
+ *   m[t]    = min_k V[t][k]          a[t] = the LOWEST k with V[t][k] == m[t]
+ *   sw      = m[t-1] + lambda                                  (one f64 add)
+ *   stay[t][k] = (V[t-1][k] <= sw)                             (a tie stays)
+ *   V[t][k] = (double) c[t][k] + (stay[t][k] ? V[t-1][k] : sw) (one f64 add)
+ *
+ * Backtrace:
+ *
+ *   u[T-1] = a[T-1]
+ *   u[t-1] = stay[t][u[t]] ? u[t] : a[t-1]
+ *
+ * (m[t] is carried as V[t][a[t]]: where -0.0 and +0.0 are both minima, the one at the lowest index.)
+ * Outputs per (utterance i, penalty p): u[0..T) (int32) at units[p * n_rows + offsets[i] + t]; energy[p * n_utt + i] = m[T-1]
+ * (f64); n_segments[p * n_utt + i] = 1 + #{t >= 1 : u[t] != u[t-1]}; status[p * n_utt + i]:
+ *   0  done
+ *   1  empty utterance, T <= 0: nothing is written for its frames; energy 0, segments 0
+ *   2  a cost of the utterance is NaN or +/-inf: its units are all -1, its energy is NaN, segments 0
+ *   3  the utterance leaves the pack (offset < 0 or offset + T > n_rows), has more than 2^24 frames, or its back-pointers do not
+ *      fit the scratch (below): it is never read, nothing is written for its frames; energy NaN, segments 0
+ * Every step is a single IEEE operation and a min is exact; the file is built with -ffp-contract=off.  The device output
+ * therefore EQUALS a numpy float64 statement of the lines above on every finite input, ties included, on every launch.
+ *
+ * cost is a pack of n_rows rows with stride ld >= k; utterance i owns rows [offsets[i], offsets[i] + lengths[i]) (int64 offsets,
+ * int32 lengths).  Gaps and any order are allowed; rows outside an utterance and columns >= k are never read; units rows outside
+ * an utterance are never written.  penalties_host: n_pen doubles on the HOST, read before the call returns.
+ * Two forms, chosen from K alone: K <= cpc_segment_units_wave_k() = 256 runs one wave64 per (utterance, penalty) with the states in
+ * registers (several waves per workgroup, no barrier); larger K one workgroup of 512 threads with one barrier per frame.  The
+ * back-pointers are one bit per (frame, state) in 32-bit words plus a[t] as one int32 per frame, in scratch; the backtrace runs in
+ * the same launch.  The scan for non-finite costs rides on the row reads.  No atomics, no f32 accumulation.
+ * scratch: cpc_segment_units_scratch_bytes(n_utt, total_frames, k, n_pen), total_frames >= the summed lengths of the utterances that run
+ * (0 with a message for sizes outside the limits).  The lengths live on the device, so cpc_segment_units cannot compare them with
+ * scratch_bytes: fewer bytes than cpc_segment_units_scratch_bytes(n_utt, 0, k, n_pen) give CPC_ERR_WORKSPACE, and an utterance whose
+ * back-pointers would leave what the scratch holds beyond that gets status 3.
+ * Limits: 1 <= k <= 16384, 0 <= n_utt <= 2^20 (0: nothing is done, CPC_OK), 1 <= n_pen <= 16, every penalty finite and >= 0,
+ *   n_rows >= 0, ld >= k; those and a NULL pointer where one is required are CPC_ERR_INVALID with a message naming the entry
+ *   point, before any launch, nothing written.
+ * ------------------------------------------------------------------------------------------ */
+int cpc_segment_units_wave_k(void);
+size_t cpc_segment_units_scratch_bytes(int n_utt, long total_frames, int k, int n_pen);
+int cpc_segment_units(const float *cost, long n_rows, long ld, int k, const int64_t *offsets, const int *lengths, int n_utt,
+                const double *penalties_host, int n_pen, int *units /* [n_pen][n_rows] */, double *energy /* [n_pen][n_utt] */,
+                int *n_segments, int *status, void *scratch, size_t scratch_bytes, cpc_stream_t stream);
 
 #ifdef __cplusplus
 }
