@@ -4,37 +4,23 @@
 // row is kept while the columns stream), and the distance tile is register-blocked: a QbE run spends its time there.
 //
 //   sdtw_kernel   one workgroup per segment (a query item and a list of document items).  Per pair the n x m frame-distance
-//                 matrix is formed 64 x 64 tile by tile in LDS: each thread owns a 4 x 4 block of the tile and reads the
-//                 staged frames TRANSPOSED ([k][row]), one 16-byte LDS read per operand and k for 16 FMAs; every entry is
-//                 still its own k-ordered f32 fma chain.  The DP runs over the tile on the anti-diagonal in wave 0 with
-//                 lane = query row (DPP wave_shr:1 hands a cell to the row below).  Queries longer than 64 frames go in
+//                 matrix is formed 64 x 64 tile by tile in LDS by dist_tile.h (shared with lalign.hip): each thread owns a
+//                 4 x 4 block of the tile; every entry is its own k-ordered f32 fma chain.  The DP runs over the tile on
+//                 the anti-diagonal in wave 0 with lane = query row (DPP wave_shr:1 hands a cell to the row below).
+//                 Queries longer than 64 frames go in
 //                 64-row strips whose boundary row (cost, length, start: 12 bytes per document column) lives in
 //                 per-workgroup scratch, double-buffered.  The lane of the last query row keeps the running best
 //                 (v, end, start, length) in registers: no cost matrix, no backtrack, no atomics.
 #include "common.h"
+#include "dist_tile.h"
 
 #include <algorithm>
 
 namespace cpc {
 namespace {
 
-constexpr int SD_T = 64;           // tile edge (rows = lanes of the DP wave)
-constexpr int SD_KC = 32;          // feature chunk staged in LDS per pass
-constexpr int SD_THREADS = 256;
-constexpr int SD_LS = SD_T + 4;    // row stride of the transposed staging tiles: 16-byte aligned rows, 68 k + 4 tc covers 64 banks
-constexpr int SD_DT_STRIDE = SD_T + 2;   // (65 r + t) % 32: the DP wave's column reads hit 32 banks
 constexpr int SD_MAX_BLOCKS = 8192;
 constexpr int SD_CELL_BYTES = 12;  // (cost, length, start) of a boundary-row column
-
-// lane i receives lane i-1's value (DPP wave_shr:1); lane 0 keeps `own`
-__device__ __forceinline__ float sd_shr1(float v, float own)
-{
-    return __builtin_amdgcn_update_dpp(own, v, 0x138, 0xf, 0xf, false);
-}
-__device__ __forceinline__ int sd_shr1(int v, int own)
-{
-    return __builtin_amdgcn_update_dpp(own, v, 0x138, 0xf, 0xf, false);
-}
 
 __global__ void __launch_bounds__(SD_THREADS)
 sdtw_kernel(const float *__restrict__ frames, int dp, const int *__restrict__ item_off, const int *__restrict__ item_len,
@@ -48,7 +34,6 @@ sdtw_kernel(const float *__restrict__ frames, int dp, const int *__restrict__ it
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const bool dp_wave = tid < 64;
-    const int r4 = (tid >> 4) * 4, c4 = (tid & 15) * 4;                  // this thread's 4 x 4 block of the distance tile
     // boundary rows of this workgroup: two (cost, length, start) rows of max_len_doc, swapped per strip
     float *bc[2];
     int *bl[2], *bs[2];
@@ -93,88 +78,8 @@ sdtw_kernel(const float *__restrict__ frames, int dp, const int *__restrict__ it
                 int best_j = 0, best_l = 0, best_s = 0;
                 for (int cb = 0; cb < ld; cb += SD_T) {
                     const int C = min(SD_T, ld - cb);
-                    // ---- distance tile: a 4 x 4 block per thread, k-ordered fma chain per entry ----
-                    float acc[4][4];
-#pragma unroll
-                    for (int a = 0; a < 4; ++a)
-#pragma unroll
-                        for (int b = 0; b < 4; ++b) acc[a][b] = 0.f;
-                    const bool block_live = r4 < R && c4 < C;
-#ifndef CPC_SDTW_SKIP_DISTANCES
-                    // the next chunk's frames travel from global memory while this chunk is multiplied: two float4 of the
-                    // strip and two of the tile per thread (64 rows x 8 float4 over 256 threads), kept in registers
-                    float4 qv[2], yv[2];
-                    auto fetch = [&](int k0) {
-                        const int kc4 = min(SD_KC, dp - k0) >> 2;       // dp is a multiple of 4
-#pragma unroll
-                        for (int s = 0; s < 2; ++s) {
-                            const int e = tid + s * SD_THREADS;
-                            const int r = e / kc4, k = (e - r * kc4) * 4;
-                            if (e < R * kc4) qv[s] = *reinterpret_cast<const float4 *>(frames + (qo + rs + r) * dp + k0 + k);
-                            if (e < C * kc4) yv[s] = *reinterpret_cast<const float4 *>(frames + (dof + cb + r) * dp + k0 + k);
-                        }
-                    };
-                    fetch(0);
-                    for (int k0 = 0; k0 < dp; k0 += SD_KC) {
-                        const int kc4 = min(SD_KC, dp - k0) >> 2;
-                        __syncthreads();                                 // previous users of xs / ys / dt are done
-#pragma unroll
-                        for (int s = 0; s < 2; ++s) {
-                            const int e = tid + s * SD_THREADS;
-                            const int r = e / kc4, k = (e - r * kc4) * 4;
-                            if (e < R * kc4) {
-                                xs[k][r] = qv[s].x; xs[k + 1][r] = qv[s].y; xs[k + 2][r] = qv[s].z; xs[k + 3][r] = qv[s].w;
-                            }
-                            if (e < C * kc4) {
-                                ys[k][r] = yv[s].x; ys[k + 1][r] = yv[s].y; ys[k + 2][r] = yv[s].z; ys[k + 3][r] = yv[s].w;
-                            }
-                        }
-                        __syncthreads();
-                        if (k0 + SD_KC < dp) fetch(k0 + SD_KC);
-                        if (block_live) {                                // rows >= R / columns >= C of the block hold stale
-                            const int kc = kc4 * 4;                      // LDS: computed, never stored
-#pragma unroll 4
-                            for (int k = 0; k < kc; ++k) {
-                                const float4 xv = *reinterpret_cast<const float4 *>(&xs[k][r4]);
-                                const float4 yv = *reinterpret_cast<const float4 *>(&ys[k][c4]);
-                                const float xa[4] = {xv.x, xv.y, xv.z, xv.w};
-                                const float ya[4] = {yv.x, yv.y, yv.z, yv.w};
-#pragma unroll
-                                for (int a = 0; a < 4; ++a)
-#pragma unroll
-                                    for (int b = 0; b < 4; ++b) {
-                                        if (euclid) {
-                                            const float df = xa[a] - ya[b];
-                                            acc[a][b] = fmaf(df, df, acc[a][b]);
-                                        } else {
-                                            acc[a][b] = fmaf(xa[a], ya[b], acc[a][b]);
-                                        }
-                                    }
-                            }
-                        }
-                    }
-                    if (block_live) {
-#pragma unroll
-                        for (int a = 0; a < 4; ++a)
-#pragma unroll
-                            for (int b = 0; b < 4; ++b)
-                                if (r4 + a < R && c4 + b < C)
-                                    dt[r4 + a][c4 + b] = euclid ? sqrtf(acc[a][b])
-                                                                : acosf(fminf(fmaxf(acc[a][b], -1.f), 1.f)) / 3.14159265358979323846f;
-                    }
-#else
-                    // probe build of tools/term_detection_bench.py: the DP alone, on stand-in distances that are not frame
-                    // distances but vary from cell to cell, so that the three predecessors all get chosen
-                    __syncthreads();
-                    if (block_live) {
-#pragma unroll
-                        for (int a = 0; a < 4; ++a)
-#pragma unroll
-                            for (int b = 0; b < 4; ++b)
-                                if (r4 + a < R && c4 + b < C) dt[r4 + a][c4 + b] = (float)(((rs + r4 + a) * 7 + (cb + c4 + b) * 13) & 15);
-                    }
-#endif
-                    __syncthreads();
+                    // ---- distance tile (dist_tile.h): a 4 x 4 block per thread, k-ordered fma chain per entry ----
+                    sd_distance_tile(frames, dp, qo + rs, R, dof + cb, C, euclid, xs, ys, dt, rs, cb);
                     // ---- DP over the tile: wave 0, lane = query row, step t = anti-diagonal ----
                     if (dp_wave) {
                         const int r = lane;

@@ -67,7 +67,8 @@ int cpc_version(void);          /* 100 x major + minor; 105 = the entry points o
                                   * 127 = cpc_bandreject_tile / cpc_bandreject_max_half / cpc_bandreject_taps /
                                   * cpc_augment_bandreject;
                                   * 128 = cpc_sdtw (+ scratch query);
-                                  * 129 = cpc_segment_units (+ scratch query) / cpc_segment_units_wave_k */
+                                  * 129 = cpc_segment_units (+ scratch query) / cpc_segment_units_wave_k;
+                                  * 130 = cpc_local_align (+ scratch query) */
 const char *cpc_last_error(void);
 
 /* In-situ kernel timing for bench.py: when enabled, the launchers bracket each launch of the named
@@ -563,6 +564,43 @@ int cpc_sdtw(const float *frames, int dp, const int *item_off, const int *item_l
              const int *seg_start, const int *pair_doc, int n_seg, int max_len_q, int max_len_doc, int distance,
              float *score, int *span /* [pairs][3] int32: start, end, length */, void *scratch, size_t scratch_bytes,
              cpc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Spoken term discovery: LOCAL alignment of two items, both ends free on both sides (csrc/lalign.hip, version 130; DESIGN.md
+ * section 28).  The reference has no such task.  Items and the work list are laid out as for cpc_sdtw: segment s compares ROW
+ * item seg_a[s] (n frames) with the COLUMN items pair_b[seg_start[s] .. seg_start[s+1]-1] (m frames each); a row item's list may
+ * be split over several segments.  Pair p's results go to score[p] and span[5p .. 5p+4].
+ *
+ * Cells.  d[i][j] is the frame distance of cpc_abx_dtw, bit for bit (CPC_ABX_COSINE or CPC_ABX_EUCLIDIAN, f32, k-ordered fma
+ *   chain, inputs normalised by the caller).  Two f32 parameters: a threshold theta > 0 and a step penalty gamma >= 0.
+ * Gain.  g = theta - d[i][j] (one f32 subtraction).
+ * Candidates of cell (i, j).  diag: H[i-1][j-1], when i > 0 and j > 0; left: H[i][j-1] - gamma, when j > 0; up: H[i-1][j] - gamma,
+ *   when i > 0 (each of left and up is one f32 subtraction).  The best candidate is the largest; ties go to diag, then left,
+ *   then up.
+ * Open or continue.  No candidate exists, or the best is <= 0: the cell opens a path, h = g, length = 1, start = (i, j).
+ *   Otherwise h = g + best (one f32 addition), length = pred.length + 1, start = pred.start.
+ * Clamp.  h > 0: the cell holds (H = h, length, start).  Otherwise H = 0 and the cell carries nothing.  A NaN distance closes
+ *   the cell.
+ * Result of a pair.  The cell of largest H; among equals the smallest i, then the smallest j, whatever the order in which the
+ *   matrix is walked.  score[p] = H, span[5p .. 5p+4] = (start_i, end_i, start_j, end_j, length).  No positive cell: score 0.0f,
+ *   span all -1.
+ * Not computable.  A pair with an item index outside [0, n_items), a length < 1, a row item longer than max_len_a or a column
+ *   item longer than max_len_b gets score NaN and span all -1.
+ * Limits.  Items have at most 32767 frames (the two start indices of a cell share one word): max_len_a, max_len_b <= 32767.  One
+ *   match is returned per pair, and no band or slope constraint is applied other than gamma.
+ *
+ * cpc_local_align_scratch_bytes = 0 when max_len_a <= 64, else 2 * 12 * max_len_b bytes per workgroup (the boundary row of a
+ * 64-row strip of the row item, one cell per column, double-buffered); negative sizes give 0 and a cpc_last_error text.  Frames
+ * beyond an item are never read; the scratch's contents before the launch are never read; no atomics: two launches give the same
+ * bytes.  Bad arguments (a null buffer, dp not a positive multiple of 4, an unknown distance, theta not finite or <= 0, gamma not
+ * finite or < 0, negative or zero sizes, a maximum above 32767) return CPC_ERR_INVALID, a scratch that is too small
+ * CPC_ERR_WORKSPACE, each with a cpc_last_error text; nothing is launched.
+ * ------------------------------------------------------------------------------------------ */
+size_t cpc_local_align_scratch_bytes(int n_seg, int max_len_a, int max_len_b);
+int cpc_local_align(const float *frames, int dp, const int *item_off, const int *item_len, int n_items, const int *seg_a,
+                    const int *seg_start, const int *pair_b, int n_seg, int max_len_a, int max_len_b, int distance, float theta,
+                    float gamma, float *score, int *span /* [pairs][5] int32: start_i, end_i, start_j, end_j, length */,
+                    void *scratch, size_t scratch_bytes, cpc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * k-means on features (cpc/clustering/clustering.py of the reference).  x [n][d] rows, ck [k][d] centroids, all fp32 DEVICE
