@@ -13,8 +13,7 @@
 //                          The previous strip's boundary row reaches lane 0 the same way.  Each cell carries (cost, path
 //                          length) with abx_dtw_kernel's addition order (d + predecessor) and tie rule (diag, left, up).
 #include "common.h"
-
-#include <algorithm>
+#include "dtw_strip.h"
 
 namespace cpc {
 namespace {
@@ -22,17 +21,7 @@ namespace {
 constexpr int ABXU_T = 64;          // strip height (rows = lanes)
 constexpr int ABXU_THREADS = 256;
 constexpr int ABXU_WAVES = ABXU_THREADS / 64;
-constexpr int ABXU_MAX_BLOCKS = 8192;
 
-// lane i receives lane i-1's value (DPP wave_shr:1); lane 0 keeps `own`
-__device__ __forceinline__ float shr1(float v, float own)
-{
-    return __builtin_amdgcn_update_dpp(own, v, 0x138, 0xf, 0xf, false);
-}
-__device__ __forceinline__ int shr1(int v, int own)
-{
-    return __builtin_amdgcn_update_dpp(own, v, 0x138, 0xf, 0xf, false);
-}
 __device__ __forceinline__ float lane_value(float v, int l)
 {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
@@ -159,8 +148,6 @@ abx_dtw_units_kernel(const int *__restrict__ units, const int *__restrict__ item
     }
 }
 
-int abxu_grid(int n) { return std::min(n, ABXU_MAX_BLOCKS); }
-
 }  // namespace
 }  // namespace cpc
 
@@ -168,7 +155,7 @@ extern "C" size_t cpc_abx_dtw_units_scratch_bytes(int n_seg, int max_len_x, int 
 {
     if (n_seg <= 0 || max_len_x <= 0 || max_len_y <= 0) return 0;
     if (max_len_x <= cpc::ABXU_T) return 0;                      // one strip per item: no boundary row is stored
-    return (size_t)cpc::abxu_grid(n_seg) * cpc::ABXU_WAVES * 2 * (size_t)max_len_y * 8;
+    return (size_t)cpc::dtw_grid(n_seg) * cpc::ABXU_WAVES * 2 * (size_t)max_len_y * 8;
 }
 
 extern "C" int cpc_abx_dtw_units(const int *units, const int *item_off, const int *item_len, int n_items, const int *seg_x,
@@ -188,7 +175,7 @@ extern "C" int cpc_abx_dtw_units(const int *units, const int *item_off, const in
     CPC_REQUIRE(scratch_bytes >= need && (need == 0 || scratch != nullptr), "abx_dtw_units: scratch of %zu bytes, %zu needed",
                 scratch_bytes, need);
     if (n_seg == 0) return CPC_OK;
-    hipLaunchKernelGGL(cpc::abx_dtw_units_kernel, dim3((unsigned)cpc::abxu_grid(n_seg)), dim3(cpc::ABXU_THREADS), 0,
+    hipLaunchKernelGGL(cpc::abx_dtw_units_kernel, dim3((unsigned)cpc::dtw_grid(n_seg)), dim3(cpc::ABXU_THREADS), 0,
                        static_cast<hipStream_t>(stream), units, item_off, item_len, n_items, seg_x, seg_start, pair_y, n_seg,
                        max_len_y, d_same, d_diff, out, path_len, need ? static_cast<char *>(scratch) : nullptr);
     CPC_CHECK_LAUNCH("abx_dtw_units_kernel");

@@ -1,37 +1,24 @@
 // The 64 x 64 frame-distance tile of the DTW kernels that stream a row item against column items (sdtw.hip, lalign.hip): staging,
-// the register-blocked products and the acos / sqrt finish, in one copy.  A workgroup of SD_THREADS threads forms the tile in LDS:
+// the register-blocked products and the acos / sqrt finish, in one copy.  A workgroup of DTW_THREADS threads forms the tile in LDS:
 // each thread owns a 4 x 4 block of it and reads the staged frames TRANSPOSED ([k][row]), one 16-byte LDS read per operand and k
 // for 16 FMAs; every entry is still its own k-ordered f32 fma chain, bit for bit the frame distance of cpc_abx_dtw.  The next
 // chunk's frames travel from global memory while this chunk is multiplied.  (abx.hip keeps its own tile: one thread per entry of
 // a 64 x 64 tile whose rows are not transposed, a different shape.)
 #pragma once
 
-#include <hip/hip_runtime.h>
+#include "dtw_strip.h"
 
 namespace cpc {
 
-constexpr int SD_T = 64;           // tile edge (rows = lanes of the DP wave)
 constexpr int SD_KC = 32;          // feature chunk staged in LDS per pass
-constexpr int SD_THREADS = 256;
-constexpr int SD_LS = SD_T + 4;    // row stride of the transposed staging tiles: 16-byte aligned rows, 68 k + 4 tc covers 64 banks
-constexpr int SD_DT_STRIDE = SD_T + 2;   // (65 r + t) % 32: the DP wave's column reads hit 32 banks
-
-// lane i receives lane i-1's value (DPP wave_shr:1); lane 0 keeps `own`
-__device__ __forceinline__ float sd_shr1(float v, float own)
-{
-    return __builtin_amdgcn_update_dpp(own, v, 0x138, 0xf, 0xf, false);
-}
-__device__ __forceinline__ int sd_shr1(int v, int own)
-{
-    return __builtin_amdgcn_update_dpp(own, v, 0x138, 0xf, 0xf, false);
-}
+constexpr int SD_LS = DTW_T + 4;   // row stride of the transposed staging tiles: 16-byte aligned rows, 68 k + 4 tc covers 64 banks
 
 // dt[r][c] = distance of frame row0 + r to frame col0 + c for r < R <= 64, c < C <= 64 (rows of `frames`, dp floats each, dp a
-// multiple of 4); other entries of dt are left as they were.  Called by all SD_THREADS threads of the workgroup with the same
+// multiple of 4); other entries of dt are left as they were.  Called by all DTW_THREADS threads of the workgroup with the same
 // arguments; it opens with a barrier behind which xs / ys / dt are rewritten, and ends with one behind which dt may be read.
 // Frames outside the R rows and C columns are never read.  gi0 / gj0: the tile's place in the pair (probe build only).
 __device__ __forceinline__ void sd_distance_tile(const float *__restrict__ frames, int dp, long row0, int R, long col0, int C, int euclid,
-                                                 float (*xs)[SD_LS], float (*ys)[SD_LS], float (*dt)[SD_DT_STRIDE], int gi0, int gj0)
+                                                 float (*xs)[SD_LS], float (*ys)[SD_LS], float (*dt)[DTW_DT_STRIDE], int gi0, int gj0)
 {
     const int tid = threadIdx.x;
     const int r4 = (tid >> 4) * 4, c4 = (tid & 15) * 4;                  // this thread's 4 x 4 block of the distance tile
@@ -49,7 +36,7 @@ __device__ __forceinline__ void sd_distance_tile(const float *__restrict__ frame
         const int kc4 = min(SD_KC, dp - k0) >> 2;       // dp is a multiple of 4
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            const int e = tid + s * SD_THREADS;
+            const int e = tid + s * DTW_THREADS;
             const int r = e / kc4, k = (e - r * kc4) * 4;
             if (e < R * kc4) qv[s] = *reinterpret_cast<const float4 *>(frames + (row0 + r) * dp + k0 + k);
             if (e < C * kc4) yv[s] = *reinterpret_cast<const float4 *>(frames + (col0 + r) * dp + k0 + k);
@@ -61,7 +48,7 @@ __device__ __forceinline__ void sd_distance_tile(const float *__restrict__ frame
         __syncthreads();                                 // previous users of xs / ys / dt are done
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            const int e = tid + s * SD_THREADS;
+            const int e = tid + s * DTW_THREADS;
             const int r = e / kc4, k = (e - r * kc4) * 4;
             if (e < R * kc4) {
                 xs[k][r] = qv[s].x; xs[k + 1][r] = qv[s].y; xs[k + 2][r] = qv[s].z; xs[k + 3][r] = qv[s].w;

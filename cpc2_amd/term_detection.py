@@ -89,27 +89,42 @@ def plan_segments(queries, docs, lens, exclude=None, cell_budget=None, target_se
 
 
 # --------------------------------------------------------------------------- kernel call
+def check_work_list(what, frames, item_off, item_len, seg_row, seg_start, pair_col, names):
+    """The checks of a run_segments (here and in term_discovery; `what` labels the messages, names = what the caller calls
+    seg_row and pair_col): frames as contiguous f32 [total_frames, dp], the work list as contiguous int32 device tensors, one more
+    seg_start than segments.  Returns (frames, n_seg, n_pairs)."""
+    _lib.require_gpu(frames, item_off, item_len, seg_row, seg_start, pair_col)
+    frames = _lib.f32c(frames)
+    if frames.dim() != 2:
+        raise ValueError(f"{what}: frames must be [total_frames, dp], got {tuple(frames.shape)}")
+    for name, t in (("item_off", item_off), ("item_len", item_len), (names[0], seg_row), ("seg_start", seg_start),
+                    (names[1], pair_col)):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise TypeError(f"{what}: {name} must be a contiguous int32 tensor")
+    n_seg, n_pairs = int(seg_row.numel()), int(pair_col.numel())
+    if seg_start.numel() != n_seg + 1:
+        raise ValueError(f"{what}: seg_start has {seg_start.numel()} entries for {n_seg} segments")
+    return frames, n_seg, n_pairs
+
+
+def fetch_scratch(what, scratch, nbytes, dev, tag):
+    """The boundary-row buffer of a run_segments: the caller's when it holds nbytes, else the package's arena (None for 0 bytes)."""
+    if scratch is None:
+        return _lib.scratch(nbytes, dev, tag=tag) if nbytes else None
+    if scratch.numel() * scratch.element_size() < nbytes:
+        raise ValueError(f"{what}: scratch of {scratch.numel() * scratch.element_size()} bytes, {nbytes} needed")
+    return scratch
+
+
 def run_segments(frames, item_off, item_len, seg_q, seg_start, pair_doc, max_len_q, max_len_doc, distance, scratch=None):
     """cpc_sdtw on a given work list (device int32 tensors): (score [P] f32, span [P, 3] int32: start, end, length).  scratch:
     a device buffer of at least cpc_sdtw_scratch_bytes (default: the package's arena)."""
-    _lib.require_gpu(frames, item_off, item_len, seg_q, seg_start, pair_doc)
-    frames = _lib.f32c(frames)
-    if frames.dim() != 2:
-        raise ValueError(f"term detection: frames must be [total_frames, dp], got {tuple(frames.shape)}")
-    for name, t in (("item_off", item_off), ("item_len", item_len), ("seg_q", seg_q), ("seg_start", seg_start),
-                    ("pair_doc", pair_doc)):
-        if t.dtype != torch.int32 or not t.is_contiguous():
-            raise TypeError(f"term detection: {name} must be a contiguous int32 tensor")
+    frames, n_seg, n_pairs = check_work_list("term detection", frames, item_off, item_len, seg_q, seg_start, pair_doc,
+                                             ("seg_q", "pair_doc"))
     dev = frames.device
-    n_seg, n_pairs = int(seg_q.numel()), int(pair_doc.numel())
-    if seg_start.numel() != n_seg + 1:
-        raise ValueError(f"term detection: seg_start has {seg_start.numel()} entries for {n_seg} segments")
     lib = _lib.load()
     nbytes = lib.cpc_sdtw_scratch_bytes(n_seg, int(max_len_q), int(max_len_doc))
-    if scratch is None:
-        scratch = _lib.scratch(nbytes, dev, tag="sdtw") if nbytes else None
-    elif scratch.numel() * scratch.element_size() < nbytes:
-        raise ValueError(f"term detection: scratch of {scratch.numel() * scratch.element_size()} bytes, {nbytes} needed")
+    scratch = fetch_scratch("term detection", scratch, nbytes, dev, "sdtw")
     score = torch.empty(n_pairs, dtype=torch.float32, device=dev)
     span = torch.empty(n_pairs, 3, dtype=torch.int32, device=dev)
     _lib.check(lib.cpc_sdtw(_lib.ptr(frames), frames.size(1), _lib.ptr(item_off), _lib.ptr(item_len), int(item_len.numel()),

@@ -57,23 +57,12 @@ def plan_pairs(items, lens, exclude=None, cell_budget=None):
 def run_segments(frames, item_off, item_len, seg_a, seg_start, pair_b, max_len_a, max_len_b, distance, theta, gamma, scratch=None):
     """cpc_local_align on a given work list (device int32 tensors): (score [P] f32, span [P, 5] int32: start_i, end_i, start_j,
     end_j, length).  scratch: a device buffer of at least cpc_local_align_scratch_bytes (default: the package's arena)."""
-    _lib.require_gpu(frames, item_off, item_len, seg_a, seg_start, pair_b)
-    frames = _lib.f32c(frames)
-    if frames.dim() != 2:
-        raise ValueError(f"term discovery: frames must be [total_frames, dp], got {tuple(frames.shape)}")
-    for name, t in (("item_off", item_off), ("item_len", item_len), ("seg_a", seg_a), ("seg_start", seg_start), ("pair_b", pair_b)):
-        if t.dtype != torch.int32 or not t.is_contiguous():
-            raise TypeError(f"term discovery: {name} must be a contiguous int32 tensor")
+    frames, n_seg, n_pairs = td.check_work_list("term discovery", frames, item_off, item_len, seg_a, seg_start, pair_b,
+                                                ("seg_a", "pair_b"))
     dev = frames.device
-    n_seg, n_pairs = int(seg_a.numel()), int(pair_b.numel())
-    if seg_start.numel() != n_seg + 1:
-        raise ValueError(f"term discovery: seg_start has {seg_start.numel()} entries for {n_seg} segments")
     lib = _lib.load()
     nbytes = lib.cpc_local_align_scratch_bytes(n_seg, int(max_len_a), int(max_len_b))
-    if scratch is None:
-        scratch = _lib.scratch(nbytes, dev, tag="lalign") if nbytes else None
-    elif scratch.numel() * scratch.element_size() < nbytes:
-        raise ValueError(f"term discovery: scratch of {scratch.numel() * scratch.element_size()} bytes, {nbytes} needed")
+    scratch = td.fetch_scratch("term discovery", scratch, nbytes, dev, "lalign")
     score = torch.empty(n_pairs, dtype=torch.float32, device=dev)
     span = torch.empty(n_pairs, SPAN, dtype=torch.int32, device=dev)
     _lib.check(lib.cpc_local_align(_lib.ptr(frames), frames.size(1), _lib.ptr(item_off), _lib.ptr(item_len), int(item_len.numel()),

@@ -66,6 +66,20 @@ def test_recurrent_size_queries(kind):
             assert lib.cpc_last_error().startswith(kind.encode() + b":"), lib.cpc_last_error()
 
 
+@pytest.mark.parametrize("query,bytes_per_cell", [("cpc_abx_dtw_scratch_bytes", 8), ("cpc_sdtw_scratch_bytes", 12),
+                                                  ("cpc_local_align_scratch_bytes", 12)])
+def test_dense_dtw_scratch_sizes(query, bytes_per_cell):
+    """The boundary rows of the dense DTW entry points (csrc/dtw_strip.h): per workgroup of the launch (at most 8192) two rows of
+    max_len_col cells, of (cost, length) for abx and three words for sdtw and local_align; nothing when one strip holds every row
+    item (max_len_row <= 64)."""
+    size = getattr(_lib.load(), query)
+    for n_seg in (1, 100, 8192, 20000):
+        for max_len_row in (64, 65):
+            for max_len_col in (1, 500):
+                want = 0 if max_len_row <= 64 else min(n_seg, 8192) * 2 * max_len_col * bytes_per_cell
+                assert size(n_seg, max_len_row, max_len_col) == want, (n_seg, max_len_row, max_len_col)
+
+
 @pytest.mark.parametrize("tag", ["tiny", "mid"])
 def test_sampler_bit_exact_vs_reference(golden, tag):
     g = golden("g1_negidx.npz")

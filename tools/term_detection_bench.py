@@ -218,8 +218,8 @@ def main():
     ap.add_argument("--build_probe_only", action="store_true")
     ap.add_argument("--out", type=str, default=os.path.join(ROOT, "profiles", "term_detection_bench.json"))
     a = ap.parse_args()
-    src = os.path.join(lib_build.CSRC, "sdtw.hip")
-    if not os.path.exists(a.probe_lib) or os.path.getmtime(a.probe_lib) < os.path.getmtime(src):
+    deps = [os.path.join(lib_build.CSRC, name) for name in ("sdtw.hip", "dist_tile.h", "dtw_strip.h")]
+    if not os.path.exists(a.probe_lib) or os.path.getmtime(a.probe_lib) < max(os.path.getmtime(p) for p in deps):
         build_probe(a.probe_lib)
     if a.build_probe_only:
         print(a.probe_lib)
