@@ -112,6 +112,12 @@ SIGNATURES = {
     "cpc_local_align_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
     "cpc_local_align": (c_int, [c_ptr, c_int, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_float, c_float,
                                 c_ptr, c_ptr, c_ptr, c_size_t, c_ptr]),
+    "cpc_sdtw_units_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "cpc_sdtw_units": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_float, c_float, c_ptr, c_ptr,
+                               c_ptr, c_size_t, c_ptr]),
+    "cpc_local_align_units_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "cpc_local_align_units": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_float, c_float, c_float,
+                                      c_float, c_ptr, c_ptr, c_ptr, c_size_t, c_ptr]),
     "cpc_kmeans_scratch_bytes": (c_size_t, [c_long, c_int, c_int]),
     "cpc_kmeans_assign": (c_int, [c_ptr, c_long, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr]),
     "cpc_kmeans_distances": (c_int, [c_ptr, c_long, c_int, c_ptr, c_int, c_ptr, c_ptr]),

@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcpc2_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-SOURCES = ["gemm_f32.hip", "gemm_planes.hip", "rowops.hip", "encoder.hip", "gru.hip", "lstm.hip", "infonce.hip", "side_stream.hip", "transformer.hip", "abx.hip", "abx_units.hip", "sdtw.hip", "lalign.hip", "kmeans.hip", "moments.hip", "seqmoments.hip", "mfcc.hip", "probe.hip", "augment.hip", "pitch.hip", "freeverb.hip", "bandreject.hip", "resample.hip", "text.hip", "seqalign.hip", "ctc_head.hip", "ctc_align.hip", "segment.hip", "unit_scores.hip", "unit_dp.hip", "negidx.cpp", "flac.cpp"]
+SOURCES = ["gemm_f32.hip", "gemm_planes.hip", "rowops.hip", "encoder.hip", "gru.hip", "lstm.hip", "infonce.hip", "side_stream.hip", "transformer.hip", "abx.hip", "abx_units.hip", "sdtw.hip", "lalign.hip", "sdtw_units.hip", "lalign_units.hip", "kmeans.hip", "moments.hip", "seqmoments.hip", "mfcc.hip", "probe.hip", "augment.hip", "pitch.hip", "freeverb.hip", "bandreject.hip", "resample.hip", "text.hip", "seqalign.hip", "ctc_head.hip", "ctc_align.hip", "segment.hip", "unit_scores.hip", "unit_dp.hip", "negidx.cpp", "flac.cpp"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-pthread"]
 # Device code is built WITHOUT the packed-f32 VALU instructions (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32).  Round 3 found
 # (profiles/r03_dp_rootcause.md; tools/load_determinism_probe.py reproduces it) that kernels which hipcc
@@ -31,10 +31,11 @@ DEVICE_FLAGS = ["--offload-arch=gfx950", "-Xclang", "-target-feature", "-Xclang"
 # for bit: the flag keeps any later product in that file from being fused into them.
 # lalign.hip states a cell as one f32 subtraction per candidate and one f32 addition, and its scores and spans must EQUAL those of a
 # float32 numpy program: the flag keeps any later product in that file from being fused into them (the distance tile of
-# dist_tile.h spells its fma chain out, so it is the same under either setting).
+# dist_tile.h spells its fma chain out, so it is the same under either setting).  lalign_units.hip runs the same recurrence
+# (lalign_rule.h) on unit ids under the same flag.
 FILE_FLAGS = {"seqalign.hip": ["-ffp-contract=off"], "ctc_align.hip": ["-ffp-contract=off"], "pitch.hip": ["-ffp-contract=off"],
               "segment.hip": ["-ffp-contract=off"], "freeverb.hip": ["-ffp-contract=off"], "unit_dp.hip": ["-ffp-contract=off"],
-              "lalign.hip": ["-ffp-contract=off"]}
+              "lalign.hip": ["-ffp-contract=off"], "lalign_units.hip": ["-ffp-contract=off"]}
 
 
 def _newer(target, deps):
@@ -47,7 +48,7 @@ def _newer(target, deps):
 def build(force=False, verbose=True):
     objdir = os.path.join(HERE, "..", "build")
     os.makedirs(objdir, exist_ok=True)
-    headers = [os.path.abspath(__file__), os.path.join(CSRC, "common.h"), os.path.join(CSRC, "rowcfg.h"), os.path.join(CSRC, "coop.h"), os.path.join(CSRC, "recurrent.h"), os.path.join(CSRC, "ldsdma.h"), os.path.join(CSRC, "text_digits.h"), os.path.join(CSRC, "ctc_lattice.h"), os.path.join(CSRC, "moment_tiles.h"), os.path.join(CSRC, "dist_tile.h"), os.path.join(CSRC, "dtw_strip.h"), os.path.join(HERE, "..", "include", "cpc2_hip.h")]
+    headers = [os.path.abspath(__file__), os.path.join(CSRC, "common.h"), os.path.join(CSRC, "rowcfg.h"), os.path.join(CSRC, "coop.h"), os.path.join(CSRC, "recurrent.h"), os.path.join(CSRC, "ldsdma.h"), os.path.join(CSRC, "text_digits.h"), os.path.join(CSRC, "ctc_lattice.h"), os.path.join(CSRC, "moment_tiles.h"), os.path.join(CSRC, "dist_tile.h"), os.path.join(CSRC, "dtw_strip.h"), os.path.join(CSRC, "dtw_units_walk.h"), os.path.join(CSRC, "sdtw_rule.h"), os.path.join(CSRC, "lalign_rule.h"), os.path.join(HERE, "..", "include", "cpc2_hip.h")]
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
     if not force and _newer(LIB, srcs + headers):
         return LIB

@@ -556,7 +556,7 @@ extern "C" int cpc_stream_spin(cpc_stream_t stream, long ticks)
 
 extern "C" long cpc_stream_apart_failures(void) { return cpc::g_apart_fail.load(std::memory_order_relaxed); }
 
-extern "C" int cpc_version(void) { return 130; }     // 130: spoken term discovery (cpc_local_align_scratch_bytes, cpc_local_align; lalign.hip); 129: duration-penalized unit segmentation (cpc_segment_units, cpc_segment_units_scratch_bytes, cpc_segment_units_wave_k; unit_dp.hip); 128: query-by-example term detection (cpc_sdtw_scratch_bytes, cpc_sdtw; sdtw.hip); 127: band-reject filtering (cpc_bandreject_tile, cpc_bandreject_max_half, cpc_bandreject_taps, cpc_augment_bandreject; bandreject.hip); 126: units against phone labels (cpc_unit_counts, cpc_unit_boundaries, their scratch queries, cpc_unit_counts_lds_cells, cpc_unit_counts_chunk; unit_scores.hip); 125: artificial reverberation (cpc_augment_freeverb; freeverb.hip); 122: cpc_probe_ctc runs on cpc_ctc_loss's kernels (its scratch query returns cpc_ctc_loss_scratch_bytes, b <= 65535); 120: CTC forced alignment (cpc_ctc_align_scratch_bytes, cpc_ctc_align, cpc_ctc_align_segments; ctc_align.hip); 119: log-mel / MFCC baseline features in f64 (cpc_mfcc_tables_doubles, cpc_mfcc_tables_host, cpc_mfcc_frame_tile, cpc_melspec_scratch_bytes, cpc_melspec_db, cpc_mfcc_finish, cpc_deltas; mfcc.hip); 118: streaming f64 second moments (cpc_moments_scratch_bytes, cpc_moments_accumulate; moments.hip); 117: the whole-utterance CTC head (cpc_ctc_loss, cpc_seqnorm_len_forward, cpc_seqnorm_len_backward, cpc_conv_head_forward, cpc_conv_head_backward_data, cpc_gather_utterances; ctc_head.hip); 116: cpc_ctc_beam_search (+ scratch query) and cpc_align_score (seqalign.hip); 115: the library owns the sampler's draw ahead (cpc_negidx_draw_ahead, cpc_negidx_take; the cpc_mt_*_async forms are gone); 114: one forward and one backward entry point per op (x_rest / n_first, c_frames and `deferred` as arguments; the *2, *_cw and *_backward_deferred symbols are gone); 113: decimal text (cpc_text_format_f32, cpc_text_format_i64, cpc_text_row_bytes, cpc_text_pack); 112: sample-rate conversion (cpc_resample_plan, cpc_resample_table_host, cpc_resample, cpc_resample_to_pcm16); 111: audio augmentation (cpc_augment_additive, cpc_augment_peak_norm, cpc_augment_fir, cpc_augment_time_dropout); 110: ABX on quantized units (cpc_abx_dtw_units); 109: linear-separability probe heads (cpc_probe_xent, cpc_probe_head_backward, cpc_probe_ctc, cpc_probe_collapse); 108: k-means (cpc_kmeans_assign, cpc_kmeans_distances, cpc_kmeans_accumulate); 107: ABX (cpc_abx_dtw, cpc_abx_counts); 106: round 6 (cpc_stream_create_apart, the sampler's hand-over through an event, ...); 105: round 5 (cpc_coop_set_policy, cpc_side_tail_wait, ...)
+extern "C" int cpc_version(void) { return 131; }     // 131: term detection and discovery on quantized units (cpc_sdtw_units, cpc_local_align_units, their scratch queries; sdtw_units.hip, lalign_units.hip); 130: spoken term discovery (cpc_local_align_scratch_bytes, cpc_local_align; lalign.hip); 129: duration-penalized unit segmentation (cpc_segment_units, cpc_segment_units_scratch_bytes, cpc_segment_units_wave_k; unit_dp.hip); 128: query-by-example term detection (cpc_sdtw_scratch_bytes, cpc_sdtw; sdtw.hip); 127: band-reject filtering (cpc_bandreject_tile, cpc_bandreject_max_half, cpc_bandreject_taps, cpc_augment_bandreject; bandreject.hip); 126: units against phone labels (cpc_unit_counts, cpc_unit_boundaries, their scratch queries, cpc_unit_counts_lds_cells, cpc_unit_counts_chunk; unit_scores.hip); 125: artificial reverberation (cpc_augment_freeverb; freeverb.hip); 122: cpc_probe_ctc runs on cpc_ctc_loss's kernels (its scratch query returns cpc_ctc_loss_scratch_bytes, b <= 65535); 120: CTC forced alignment (cpc_ctc_align_scratch_bytes, cpc_ctc_align, cpc_ctc_align_segments; ctc_align.hip); 119: log-mel / MFCC baseline features in f64 (cpc_mfcc_tables_doubles, cpc_mfcc_tables_host, cpc_mfcc_frame_tile, cpc_melspec_scratch_bytes, cpc_melspec_db, cpc_mfcc_finish, cpc_deltas; mfcc.hip); 118: streaming f64 second moments (cpc_moments_scratch_bytes, cpc_moments_accumulate; moments.hip); 117: the whole-utterance CTC head (cpc_ctc_loss, cpc_seqnorm_len_forward, cpc_seqnorm_len_backward, cpc_conv_head_forward, cpc_conv_head_backward_data, cpc_gather_utterances; ctc_head.hip); 116: cpc_ctc_beam_search (+ scratch query) and cpc_align_score (seqalign.hip); 115: the library owns the sampler's draw ahead (cpc_negidx_draw_ahead, cpc_negidx_take; the cpc_mt_*_async forms are gone); 114: one forward and one backward entry point per op (x_rest / n_first, c_frames and `deferred` as arguments; the *2, *_cw and *_backward_deferred symbols are gone); 113: decimal text (cpc_text_format_f32, cpc_text_format_i64, cpc_text_row_bytes, cpc_text_pack); 112: sample-rate conversion (cpc_resample_plan, cpc_resample_table_host, cpc_resample, cpc_resample_to_pcm16); 111: audio augmentation (cpc_augment_additive, cpc_augment_peak_norm, cpc_augment_fir, cpc_augment_time_dropout); 110: ABX on quantized units (cpc_abx_dtw_units); 109: linear-separability probe heads (cpc_probe_xent, cpc_probe_head_backward, cpc_probe_ctc, cpc_probe_collapse); 108: k-means (cpc_kmeans_assign, cpc_kmeans_distances, cpc_kmeans_accumulate); 107: ABX (cpc_abx_dtw, cpc_abx_counts); 106: round 6 (cpc_stream_create_apart, the sampler's hand-over through an event, ...); 105: round 5 (cpc_coop_set_policy, cpc_side_tail_wait, ...)
 
 extern "C" int cpc_prof_enable(int on)
 {

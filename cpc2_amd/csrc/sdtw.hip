@@ -1,42 +1,15 @@
 // Query-by-example term detection: batched SUBSEQUENCE DTW of a query item inside document items (cpc2_hip.h, DESIGN.md
 // section 26).  The walk is that of dtw_strip.h and the distance tile that of dist_tile.h (a QbE run spends its time there); what
-// is this file's: the recurrence (free start on row 0, every cell carries (cost, length, start)) and the best end column of the
-// last query row, kept in that row's lane while the columns stream: no cost matrix, no backtrack, no atomics.
+// is sdtw_rule.h's, shared with sdtw_units.hip: the recurrence (free start on row 0, every cell carries (cost, length, start)) and the
+// best end column of the last query row, kept in that row's lane while the columns stream: no cost matrix, no backtrack, no atomics.
 //
 //   sdtw_kernel   one workgroup per segment (a query item and a list of document items).
 #include "common.h"
 #include "dist_tile.h"
+#include "sdtw_rule.h"
 
 namespace cpc {
 namespace {
-
-constexpr int SD_W = 3;            // (cost, length, start): 12 bytes per boundary-row column
-using SdCell = DtwCell<SD_W>;
-
-struct SdRule {
-    int lq;                        // query frames
-    float best_v = 0.f;            // lane of the last query row: the best end column so far
-    int best_j = 0, best_l = 0, best_s = 0;
-
-    __device__ __forceinline__ SdCell cell(int gi, int gj, float d, const SdCell &diag, const SdCell &left, const SdCell &up) const
-    {
-        if (gi == 0) return {d, {1, gj}};                // free start: no predecessor on the first query row
-        const SdCell pred = dtw_pick(gj == 0, up, dtw_cheapest(diag, left, up));
-        return {d + pred.v, {pred.n[DTW_LEN] + 1, pred.n[DTW_START]}};
-    }
-    __device__ __forceinline__ void visit(int gi, int gj, const SdCell &c)
-    {
-        if (gi != lq - 1) return;
-        const float v = c.v / (float)c.n[DTW_LEN];       // the last query row: v[j], the first smallest wins
-        if (gj == 0 || v < best_v) {
-            best_v = v;
-            best_j = gj;
-            best_l = c.n[DTW_LEN];
-            best_s = c.n[DTW_START];
-        }
-    }
-    __device__ __forceinline__ void strip_done(int, int, bool) {}
-};
 
 __global__ void __launch_bounds__(DTW_THREADS)
 sdtw_kernel(const float *__restrict__ frames, int dp, const int *__restrict__ item_off, const int *__restrict__ item_len,

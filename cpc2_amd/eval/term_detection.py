@@ -3,6 +3,9 @@ csrc/sdtw.hip).  The reference has no such tool; the comma
 
     python -m cpc2_amd.eval.term_detection from_checkpoint CKPT DOC_DIR --queries Q.txt --relevance R.txt --out DIR [flags]
     python -m cpc2_amd.eval.term_detection from_pre_computed FEATURE_DIR --queries Q.txt --relevance R.txt --out DIR [flags]
+    python -m cpc2_amd.eval.term_detection from_units QUANTIZED.txt --queries Q.txt --relevance R.txt --out DIR
+           [--query_units QUANTIZED_Q.txt] [--doc_list L] [--distance_mode cosine|euclidian] [--top 100] [--feature_size 0.01]
+           [--max_doc_frames N]
 
     flags: [--query_dir D] [--doc_list L] [--file_extension .flac|.wav|.npy|.pt] [--distance_mode cosine|euclidian]
            [--feature_size 0.01] [--top 100] [--seqNorm] [--max_doc_frames N]
@@ -24,6 +27,14 @@ scratch for, MAX_DOC_FRAMES = 16384) are left out and listed by name.  Three fil
     detections.txt               the top --top documents per query: `query doc rank score start_s end_s relevant`
     term_detection_log.json      the wall time of decode, model, copy, kernels, rank and write, the device synchronised between them
 
+from_units searches QUANTIZED units (csrc/sdtw_units.hip): QUANTIZED.txt is the quantized_outputs.txt that
+clustering_quantization and segment_quantization write (or the directory that holds one), read by unit_quality.read_quantized: a
+document is a line of it, a query a line (of --query_units when given) or a span of one.  The frame distance is then one of two
+numbers, those the chosen --distance_mode gives on one-hot rows (abx_group_computation.unit_frame_distances: 0 and 0.5 for
+cosine, 0 and sqrt 2 for euclidian), and cpc_sdtw_units runs the same recurrence on the unit ids.  Ranks, scores and files are
+made by the same code; the log also names the source, the number of distinct units and the two distances.  --seqNorm and
+--query_dir are refused with from_units (there is no feature to normalise and no file to look up).
+
 Refused by name before any audio or feature file is opened: --file_extension .mp3, a non-empty --out, a Q.txt or R.txt that is
 missing or has malformed lines, a query_id in R.txt that Q.txt lacks, a non-positive --feature_size, --top < 1.
 """
@@ -42,7 +53,9 @@ from .. import audio
 from .. import term_detection as td
 from ..dataset import filterSeqs, findAllSeqs
 from ..feature_loader import FeatureModule, buildFeature_device, loadModel, seqNormalization
+from .ABX import abx_group_computation as abx_g
 from .ABX.abx_iterators import normalize_with_singularity
+from .unit_quality import read_quantized
 
 STAGES = ("decode", "model", "copy", "kernels", "rank", "write")
 MAX_DOC_FRAMES = 16384             # documents the scratch is sized for by default: 24 bytes x frames per workgroup
@@ -76,10 +89,24 @@ def parse_args(argv):
     pre.add_argument('path_dataset', type=str, help="Path to pre-computed [frames, dim] features")
     pre.add_argument('--file_extension', type=str, default='.pt', help=".pt or .npy")
     _common(pre)
+    units = subparsers.add_parser('from_units')
+    units.add_argument('path_units', type=str, help="quantized_outputs.txt of clustering_quantization / segment_quantization")
+    units.add_argument('--query_units', type=str, default=None, help="The queries' quantized_outputs.txt (default: the documents)")
+    _common(units)
     args = base_parser.parse_args(argv)
     if args.load is None:
-        base_parser.error("choose from_checkpoint or from_pre_computed")
+        base_parser.error("choose from_checkpoint, from_pre_computed or from_units")
     return args
+
+
+def units_file(path, flag="from_units"):
+    """The unit file behind `path`: the file itself, or the quantized_outputs.txt of a directory (the per-penalty layout of
+    segment_quantization)."""
+    if os.path.isdir(path):
+        path = os.path.join(path, "quantized_outputs.txt")
+    if not os.path.isfile(path):
+        raise ValueError(f"{flag} {path}: no such unit file")
+    return path
 
 
 def _read_spans(path, flag, what):
@@ -109,12 +136,18 @@ def _read_spans(path, flag, what):
 def check_args(args):
     """The refusals, each naming its flag; no audio or feature file has been opened.  Leaves the parsed Q.txt / R.txt in
     args.query_rows / args.relevance_rows."""
-    ext = args.file_extension.lower()
-    if ext == ".mp3":
-        raise NotImplementedError("--file_extension .mp3: there is no mp3 decoder in this package; convert the files to .wav or .flac")
-    allowed = (".wav", ".flac") if args.load == 'from_checkpoint' else (".pt", ".npy")
-    if ext not in allowed:
-        raise ValueError(f"--file_extension {args.file_extension}: {args.load} reads {' or '.join(allowed)}")
+    if args.load == 'from_units':
+        if args.seqNorm:
+            raise ValueError("--seqNorm with from_units: units are not features, there is nothing to normalise")
+        if args.query_dir is not None:
+            raise ValueError("--query_dir with from_units: the queries' units come from --query_units")
+    else:
+        ext = args.file_extension.lower()
+        if ext == ".mp3":
+            raise NotImplementedError("--file_extension .mp3: there is no mp3 decoder in this package; convert the files to .wav or .flac")
+        allowed = (".wav", ".flac") if args.load == 'from_checkpoint' else (".pt", ".npy")
+        if ext not in allowed:
+            raise ValueError(f"--file_extension {args.file_extension}: {args.load} reads {' or '.join(allowed)}")
     if not args.feature_size > 0 or not math.isfinite(args.feature_size):
         raise ValueError(f"--feature_size {args.feature_size} must be positive")
     if args.top < 1:
@@ -136,6 +169,10 @@ def check_args(args):
     if unknown:
         raise ValueError(f"--relevance {args.relevance}: query_id not in --queries: {' '.join(unknown)}")
     args.query_rows, args.relevance_rows = queries, relevance
+    if args.load == 'from_units':
+        args.path_units = units_file(args.path_units)
+        if args.query_units is not None:
+            args.query_units = units_file(args.query_units, "--query_units")
     return args
 
 
@@ -201,6 +238,42 @@ def feature_loader(args, timings):
     return load
 
 
+def unit_distances(distance_mode):
+    """(d_same, d_diff) of --distance_mode on one-hot rows: what the feature sources would compute on the one-hot expansion of the
+    units (cosine mode normalises the rows, euclidian does not)."""
+    cosine = distance_mode == 'cosine'
+    return abx_g.unit_frame_distances(2, cosine, abx_g.get_cosine_distance_batch if cosine else abx_g.get_euclidian_distance_batch)
+
+
+def read_units(path, flag):
+    """unit_quality.read_quantized, with a unit id that does not fit the kernels' int32 refused by the file's name."""
+    try:
+        return read_quantized(path)
+    except OverflowError as err:
+        raise ValueError(f"{flag} {path}: a unit id does not fit int32 ({err})") from None
+
+
+def unit_listing(args, timings):
+    """from_units: (doc_paths, query_paths, load) in the shapes main uses for files.  A "path" is (file, name), so that a query
+    taken from the documents' own file is the document it is excluded from, and load(path) gives the line's units."""
+    t0 = time.perf_counter()
+    store = {("doc", name): units for name, units in read_units(args.path_units, "from_units")}
+    doc_names = sorted(name for _, name in store)
+    if args.doc_list is not None:
+        with open(args.doc_list, 'r') as f:
+            wanted = {p.strip() for p in f.readlines() if p.strip()}
+        doc_names = [name for name in doc_names if name in wanted]
+    doc_paths = {name: ("doc", name) for name in doc_names}
+    if args.query_units is not None:
+        queries = {("query", name): units for name, units in read_units(args.query_units, "--query_units")}
+        query_paths = {key[1]: key for key in queries}
+        store.update(queries)
+    else:
+        query_paths = doc_paths
+    timings["decode"] += time.perf_counter() - t0
+    return doc_paths, query_paths, store.__getitem__
+
+
 def iou(a0, a1, b0, b1):
     inter = max(0.0, min(a1, b1) - max(a0, b0))
     union = max(a1, b1) - min(a0, b0)
@@ -218,12 +291,19 @@ def main(argv):
         raise RuntimeError("cpc2_amd runs only on a GPU (HIP) device and none is available: term_detection makes the frame "
                            "distances and the subsequence DTW on the device. There is no CPU fallback.")
     timings = {stage: 0.0 for stage in STAGES}
-    doc_paths = _listing(args.path_dataset, args.file_extension, args.doc_list)
-    if not doc_paths:
-        raise ValueError(f"no {args.file_extension} document found under {args.path_dataset}")
-    query_paths = _listing(args.query_dir, args.file_extension) if args.query_dir is not None else doc_paths
+    from_units = args.load == 'from_units'
+    if from_units:
+        # a "path" is (which file, name) and its "features" are the line's unit ids (int32 numpy)
+        doc_paths, query_paths, load = unit_listing(args, timings)
+        if not doc_paths:
+            raise ValueError(f"from_units {args.path_units}: no document" + (" named in --doc_list" if args.doc_list else ""))
+    else:
+        doc_paths = _listing(args.path_dataset, args.file_extension, args.doc_list)
+        if not doc_paths:
+            raise ValueError(f"no {args.file_extension} document found under {args.path_dataset}")
+        query_paths = _listing(args.query_dir, args.file_extension) if args.query_dir is not None else doc_paths
+        load = feature_loader(args, timings)
     missing_queries = [q[0] for q in args.query_rows if q[1] not in query_paths]
-    load = feature_loader(args, timings)
     cosine = args.distance_mode == 'cosine'
 
     # ---- features: every file once; items are spans of one frames buffer ----
@@ -236,19 +316,20 @@ def main(argv):
         if path in file_span:
             return file_span[path]
         feats = load(path)
-        if dim is None:
-            dim = feats.size(1)
-        if feats.size(1) != dim:
-            raise ValueError(f"{path}: {feats.size(1)} feature columns, the files before it have {dim}")
-        if not bool(torch.isfinite(feats).all()):
-            non_finite.append(_name(path))
-            file_span[path] = None
-            return None
-        if cosine and feats.size(0):
-            feats = normalize_with_singularity(feats)
-        file_span[path] = (n_rows, feats.size(0))
+        if not from_units:
+            if dim is None:
+                dim = feats.size(1)
+            if feats.size(1) != dim:
+                raise ValueError(f"{path}: {feats.size(1)} feature columns, the files before it have {dim}")
+            if not bool(torch.isfinite(feats).all()):
+                non_finite.append(_name(path))
+                file_span[path] = None
+                return None
+            if cosine and feats.size(0):
+                feats = normalize_with_singularity(feats)
+        file_span[path] = (n_rows, len(feats))
         pieces.append(feats)
-        n_rows += feats.size(0)
+        n_rows += len(feats)
         return file_span[path]
 
     offs, lens, doc_names = [], [], []
@@ -289,10 +370,18 @@ def main(argv):
 
     t0 = time.perf_counter()
     device = torch.device("cuda")
-    width = pieces[0].size(1)
-    dp = -(-width // 4) * 4
-    frames = torch.zeros(n_rows, dp, dtype=torch.float32, device=device)
-    frames[:, :width] = torch.cat(pieces, 0)
+    if from_units:
+        all_units = np.concatenate(pieces).astype(np.int32)
+        source_log = dict(zip(("d_same", "d_diff"), unit_distances(args.distance_mode)))
+        source_log.update(source="from_units", distinct_units=int(np.unique(all_units).size))
+        frames = torch.from_numpy(all_units).to(device)
+        dp = 0
+    else:
+        source_log = {"source": args.load}
+        width = pieces[0].size(1)
+        dp = -(-width // 4) * 4
+        frames = torch.zeros(n_rows, dp, dtype=torch.float32, device=device)
+        frames[:, :width] = torch.cat(pieces, 0)
     del pieces
     item_off = torch.tensor(offs, dtype=torch.int32, device=device)
     item_len = torch.tensor(lens, dtype=torch.int32, device=device)
@@ -300,8 +389,13 @@ def main(argv):
     timings["copy"] += time.perf_counter() - t0
 
     t0 = time.perf_counter()
-    score, span, pair_q, pair_doc = td.subsequence_dtw(frames, item_off, item_len, query_items, np.arange(n_docs), args.distance_mode,
-                                                       exclude=exclude, lens_host=lens)
+    if from_units:
+        score, span, pair_q, pair_doc = td.subsequence_dtw_units(frames, item_off, item_len, query_items, np.arange(n_docs),
+                                                                 source_log["d_same"], source_log["d_diff"], exclude=exclude,
+                                                                 lens_host=lens)
+    else:
+        score, span, pair_q, pair_doc = td.subsequence_dtw(frames, item_off, item_len, query_items, np.arange(n_docs),
+                                                           args.distance_mode, exclude=exclude, lens_host=lens)
     torch.cuda.synchronize()
     timings["kernels"] += time.perf_counter() - t0
     t0 = time.perf_counter()
@@ -361,7 +455,7 @@ def main(argv):
     cells = int((np.asarray(lens, dtype=np.int64)[np.asarray(query_items)[pair_q]] * np.asarray(lens, dtype=np.int64)[pair_doc]).sum())
     with open(out_dir / "term_detection_log.json", "w") as f:
         json.dump({"documents": n_docs, "queries": len(query_ids), "pairs": int(len(pair_q)), "cells": cells, "frames": int(n_rows),
-                   "feature_columns": int(dp), "seconds": timings}, f, indent=2)
+                   "feature_columns": int(dp), **source_log, "seconds": timings}, f, indent=2)
     print(f"MAP {scores['map']:.4f} P@10 {scores['p_at_10']:.4f} P@N {scores['p_at_n']:.4f} MRR {scores['mrr']:.4f} over "
           f"{result['n_scored']} of {len(query_ids)} queries, {n_docs} documents")
     print(f"{len(pair_q)} pairs: " + ", ".join(f"{stage} {timings[stage]:.3f} s" for stage in STAGES))

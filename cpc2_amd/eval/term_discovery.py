@@ -3,6 +3,9 @@ csrc/lalign.hip).  The reference has no such tool; the com
 
     python -m cpc2_amd.eval.term_discovery from_checkpoint CKPT.pt AUDIO_DIR --threshold T --out DIR [flags]
     python -m cpc2_amd.eval.term_discovery from_pre_computed FEATURE_DIR --file_extension .npy|.pt --threshold T --out DIR [flags]
+    python -m cpc2_amd.eval.term_discovery from_units QUANTIZED.txt --threshold T --out DIR [--seq_list L]
+           [--distance_mode cosine|euclidian] [--gap_penalty G] [--min_frames 25] [--min_score 0] [--max_frames N]
+           [--pathPhone LABELS.txt] [--top K]
 
     flags: [--file_extension .flac] [--seq_list L] [--distance_mode cosine|euclidian] [--gap_penalty G] [--min_frames 25]
            [--min_score 0] [--max_frames N] [--seqNorm] [--pathPhone LABELS.txt] [--top K] [--seed 0]
@@ -29,6 +32,16 @@ is 32767) are left out and listed by name.  Written into --out:
     discovery_log.json      the arguments, the theta and gamma used, the distance percentiles, the utterances left out by name, the
                             pair and cell counts and the wall time by stage
 
+from_units searches QUANTIZED units (csrc/lalign_units.hip): QUANTIZED.txt is the quantized_outputs.txt
+that clustering_quantization and segment_quantization write (or the directory that holds one), read by
+unit_quality.read_quantized: an utterance is a line of it.  The frame distance is then one of two numbers, those the chosen
+--distance_mode gives on one-hot rows (d_same = 0 and d_diff = 0.5 for cosine, 0 and sqrt 2 for euclidian), and
+cpc_local_align_units runs the same recurrence on the unit ids.  Matches, scores and files are made by the same code; the log also
+names the source, the number of distinct units and the two distances, and has no distance percentiles: there is no sample.
+Refused with from_units, by flag: --seqNorm; --threshold qP (a percentile of a distance that takes two values says nothing); a
+--threshold outside (d_same, d_diff]: at or below d_same no cell can gain, above d_diff every cell gains and the match is the whole
+matrix.
+
 Refused by name before any audio or feature file is opened: a non-empty --out, --file_extension .mp3, a malformed --threshold, a
 negative --gap_penalty, --min_frames or --min_score, a --max_frames above the kernel's limit, --top < 1.
 """
@@ -46,7 +59,7 @@ import torch
 from .. import term_discovery as tdisc
 from ..dataset import parseSeqLabels
 from .ABX.abx_iterators import normalize_with_singularity
-from .term_detection import _listing, feature_loader, format_time
+from .term_detection import _listing, feature_loader, format_time, read_units, unit_distances, units_file
 
 STAGES = ("decode", "model", "copy", "threshold", "kernels", "select", "score", "write")
 MAX_FRAMES_DEFAULT = 16384         # utterances the scratch is sized for by default: 24 bytes x frames per workgroup
@@ -84,9 +97,12 @@ def parse_args(argv):
     pre.add_argument('path_dataset', type=str, help="Path to pre-computed [frames, dim] features")
     pre.add_argument('--file_extension', type=str, default='.pt', help=".pt or .npy")
     _common(pre)
+    units = subparsers.add_parser('from_units')
+    units.add_argument('path_units', type=str, help="quantized_outputs.txt of clustering_quantization / segment_quantization")
+    _common(units)
     args = base_parser.parse_args(argv)
     if args.load is None:
-        base_parser.error("choose from_checkpoint or from_pre_computed")
+        base_parser.error("choose from_checkpoint, from_pre_computed or from_units")
     return args
 
 
@@ -110,13 +126,26 @@ def parse_threshold(text):
 def check_args(args):
     """The refusals, each naming its flag; no audio or feature file has been opened.  Leaves the parsed threshold in
     args.threshold_kind / args.threshold_value."""
-    ext = args.file_extension.lower()
-    if ext == ".mp3":
-        raise NotImplementedError("--file_extension .mp3: there is no mp3 decoder in this package; convert the files to .wav or .flac")
-    allowed = (".wav", ".flac") if args.load == 'from_checkpoint' else (".pt", ".npy")
-    if ext not in allowed:
-        raise ValueError(f"--file_extension {args.file_extension}: {args.load} reads {' or '.join(allowed)}")
+    if args.load == 'from_units':
+        if args.seqNorm:
+            raise ValueError("--seqNorm with from_units: units are not features, there is nothing to normalise")
+    else:
+        ext = args.file_extension.lower()
+        if ext == ".mp3":
+            raise NotImplementedError("--file_extension .mp3: there is no mp3 decoder in this package; convert the files to .wav or .flac")
+        allowed = (".wav", ".flac") if args.load == 'from_checkpoint' else (".pt", ".npy")
+        if ext not in allowed:
+            raise ValueError(f"--file_extension {args.file_extension}: {args.load} reads {' or '.join(allowed)}")
     args.threshold_kind, args.threshold_value = parse_threshold(args.threshold)
+    if args.load == 'from_units':
+        if args.threshold_kind == "percentile":
+            raise ValueError(f"--threshold {args.threshold} with from_units: the frame distance of two units takes two values, a "
+                             "percentile of it says nothing; give a number")
+        d_same, d_diff = unit_distances(args.distance_mode)
+        if not d_same < float(np.float32(args.threshold_value)) <= d_diff:
+            raise ValueError(f"--threshold {args.threshold} with from_units: must lie in (d_same, d_diff] = ({d_same:.6g}, {d_diff:.6g}] of "
+                             f"--distance_mode {args.distance_mode}: at or below d_same no cell can gain, above d_diff every cell gains "
+                             "and the match is the whole matrix")
     if args.gap_penalty is not None and not (math.isfinite(args.gap_penalty) and args.gap_penalty >= 0):
         raise ValueError(f"--gap_penalty {args.gap_penalty} must be finite and >= 0")
     if args.min_frames < 0:
@@ -130,6 +159,8 @@ def check_args(args):
     if os.path.exists(args.out) and (not os.path.isdir(args.out) or os.listdir(args.out)):
         raise ValueError(f"--out {args.out} exists and is not an empty directory: the tool writes its files there and overwrites "
                          "nothing")
+    if args.load == 'from_units':
+        args.path_units = units_file(args.path_units)
     return args
 
 
@@ -158,10 +189,27 @@ def main(argv):
         raise RuntimeError("cpc2_amd runs only on a GPU (HIP) device and none is available: term_discovery makes the frame "
                            "distances and the local alignment on the device. There is no CPU fallback.")
     timings = {stage: 0.0 for stage in STAGES}
-    paths = _listing(args.path_dataset, args.file_extension, args.seq_list)
-    if not paths:
-        raise ValueError(f"no {args.file_extension} file found under {args.path_dataset}")
-    load = feature_loader(args, timings)
+    from_units = args.load == 'from_units'
+    if from_units:
+        # a "path" is the utterance's name and its "features" are the line's unit ids (int32 numpy)
+        t0 = time.perf_counter()
+        paths = dict(read_units(args.path_units, "from_units"))
+        if args.seq_list is not None:
+            with open(args.seq_list, 'r') as f:
+                wanted = {p.strip() for p in f.readlines() if p.strip()}
+            paths = {name: units for name, units in paths.items() if name in wanted}
+        paths = {name: paths[name] for name in sorted(paths)}
+        timings["decode"] += time.perf_counter() - t0
+        if not paths:
+            raise ValueError(f"from_units {args.path_units}: no utterance" + (" named in --seq_list" if args.seq_list else ""))
+
+        def load(units):
+            return units
+    else:
+        paths = _listing(args.path_dataset, args.file_extension, args.seq_list)
+        if not paths:
+            raise ValueError(f"no {args.file_extension} file found under {args.path_dataset}")
+        load = feature_loader(args, timings)
     cosine = args.distance_mode == 'cosine'
 
     # ---- features: every file once; items are spans of one frames buffer ----
@@ -169,33 +217,42 @@ def main(argv):
     non_finite, too_long, empty = [], [], []
     for name, path in paths.items():
         feats = load(path)
-        if dim is None:
-            dim = feats.size(1)
-        if feats.size(1) != dim:
-            raise ValueError(f"{path}: {feats.size(1)} feature columns, the files before it have {dim}")
-        if feats.size(0) < 1:
+        if not from_units:
+            if dim is None:
+                dim = feats.size(1)
+            if feats.size(1) != dim:
+                raise ValueError(f"{path}: {feats.size(1)} feature columns, the files before it have {dim}")
+        if len(feats) < 1:
             empty.append(name)
-        elif feats.size(0) > args.max_frames:
+        elif len(feats) > args.max_frames:
             too_long.append(name)
-        elif not bool(torch.isfinite(feats).all()):
+        elif not from_units and not bool(torch.isfinite(feats).all()):
             non_finite.append(name)
         else:
-            if cosine:
+            if cosine and not from_units:
                 feats = normalize_with_singularity(feats)
             names.append(name)
             offs.append(n_rows)
-            lens.append(feats.size(0))
+            lens.append(len(feats))
             pieces.append(feats)
-            n_rows += feats.size(0)
+            n_rows += len(feats)
     if len(names) < 2:
         raise ValueError("fewer than two utterances left to compare: the others were empty, non-finite or longer than --max_frames")
 
     t0 = time.perf_counter()
     device = torch.device("cuda")
-    width = pieces[0].size(1)
-    dp = -(-width // 4) * 4
-    frames = torch.zeros(n_rows, dp, dtype=torch.float32, device=device)
-    frames[:, :width] = torch.cat(pieces, 0)
+    if from_units:
+        all_units = np.concatenate(pieces).astype(np.int32)
+        source_log = dict(zip(("d_same", "d_diff"), unit_distances(args.distance_mode)))
+        source_log.update(source="from_units", distinct_units=int(np.unique(all_units).size))
+        frames = torch.from_numpy(all_units).to(device)
+        dp = 0
+    else:
+        source_log = {"source": args.load}
+        width = pieces[0].size(1)
+        dp = -(-width // 4) * 4
+        frames = torch.zeros(n_rows, dp, dtype=torch.float32, device=device)
+        frames[:, :width] = torch.cat(pieces, 0)
     del pieces
     item_off = torch.tensor(offs, dtype=torch.int32, device=device)
     item_len = torch.tensor(lens, dtype=torch.int32, device=device)
@@ -204,21 +261,27 @@ def main(argv):
 
     # ---- theta and gamma ----
     t0 = time.perf_counter()
-    sample = sample_distances(frames, offs, lens, args.distance_mode, args.seed)
-    percentiles = {str(p): float(np.percentile(sample, p)) for p in PERCENTILES}
+    sample = np.zeros(0) if from_units else sample_distances(frames, offs, lens, args.distance_mode, args.seed)
+    percentiles = {} if from_units else {str(p): float(np.percentile(sample, p)) for p in PERCENTILES}
     theta = args.threshold_value if args.threshold_kind == "value" else float(np.percentile(sample, args.threshold_value))
     theta = float(np.float32(theta))
     if not (math.isfinite(theta) and theta > 0):
         raise ValueError(f"--threshold {args.threshold}: the percentile is {theta}, not a positive distance")
     gamma = float(np.float32(theta / 2 if args.gap_penalty is None else args.gap_penalty))
     timings["threshold"] += time.perf_counter() - t0
-    print("frame distance percentiles of the sample: " + ", ".join(f"{p} %: {v:.4f}" for p, v in percentiles.items()))
+    if not from_units:
+        print("frame distance percentiles of the sample: " + ", ".join(f"{p} %: {v:.4f}" for p, v in percentiles.items()))
     print(f"theta {theta:.6g} gamma {gamma:.6g}")
 
     # ---- every pair ----
     t0 = time.perf_counter()
-    score, span, pair_a, pair_b = tdisc.local_alignment(frames, item_off, item_len, np.arange(len(names)), args.distance_mode, theta,
-                                                        gamma, lens_host=lens)
+    if from_units:
+        score, span, pair_a, pair_b = tdisc.local_alignment_units(frames, item_off, item_len, np.arange(len(names)),
+                                                                  source_log["d_same"], source_log["d_diff"], theta, gamma,
+                                                                  lens_host=lens)
+    else:
+        score, span, pair_a, pair_b = tdisc.local_alignment(frames, item_off, item_len, np.arange(len(names)), args.distance_mode,
+                                                            theta, gamma, lens_host=lens)
     torch.cuda.synchronize()
     timings["kernels"] += time.perf_counter() - t0
     t0 = time.perf_counter()
@@ -261,7 +324,7 @@ def main(argv):
     lens64 = np.asarray(lens, dtype=np.int64)
     log = {"args": {k: v for k, v in vars(args).items()}, "theta": theta, "gamma": gamma, "distance_percentiles": percentiles,
            "sampled_frame_pairs": int(len(sample)), "utterances": len(names), "pairs": int(len(pair_a)),
-           "cells": int((lens64[pair_a] * lens64[pair_b]).sum()), "frames": int(n_rows), "feature_columns": int(dp),
+           "cells": int((lens64[pair_a] * lens64[pair_b]).sum()), "frames": int(n_rows), "feature_columns": int(dp), **source_log,
            "pairs_with_a_match": int((score_h > 0).sum()), "matches_selected": int(n_selected), "matches_written": len(matches),
            "empty": empty, "too_long": too_long, "non_finite": non_finite, "seconds": timings}
     with open(out_dir / "discovery_log.json", "w") as f:

@@ -157,6 +157,64 @@ def subsequence_dtw(frames, item_off, item_len, queries, docs, distance, exclude
     return score, span, pair_q, pair_doc
 
 
+# --------------------------------------------------------------------------- quantized units (csrc/sdtw_units.hip)
+def check_unit_work_list(what, units, item_off, item_len, seg_row, seg_start, pair_col, names):
+    """check_work_list for items of unit ids (here and in term_discovery): units as a contiguous int32 device tensor
+    [total_frames]; anything else is a TypeError that names the argument.  Returns (n_seg, n_pairs)."""
+    for name, t in (("units", units), ("item_off", item_off), ("item_len", item_len), (names[0], seg_row), ("seg_start", seg_start),
+                    (names[1], pair_col)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_contiguous():
+            raise TypeError(f"{what}: {name} must be a contiguous int32 tensor")
+    if units.dim() != 1:
+        raise TypeError(f"{what}: units must be [total_frames], got {tuple(units.shape)}")
+    _lib.require_gpu(units, item_off, item_len, seg_row, seg_start, pair_col)
+    n_seg, n_pairs = int(seg_row.numel()), int(pair_col.numel())
+    if seg_start.numel() != n_seg + 1:
+        raise ValueError(f"{what}: seg_start has {seg_start.numel()} entries for {n_seg} segments")
+    return n_seg, n_pairs
+
+
+def run_segments_units(units, item_off, item_len, seg_q, seg_start, pair_doc, max_len_q, max_len_doc, d_same, d_diff, scratch=None):
+    """cpc_sdtw_units on a given work list (device int32 tensors): run_segments with the frames replaced by unit ids
+    [total_frames] int32 and the distance by its two values (d_same between equal units, d_diff between different ones;
+    abx_group_computation.unit_frame_distances makes them).  scratch: at least cpc_sdtw_units_scratch_bytes."""
+    n_seg, n_pairs = check_unit_work_list("term detection on units", units, item_off, item_len, seg_q, seg_start, pair_doc,
+                                          ("seg_q", "pair_doc"))
+    dev = units.device
+    lib = _lib.load()
+    nbytes = lib.cpc_sdtw_units_scratch_bytes(n_seg, int(max_len_q), int(max_len_doc))
+    scratch = fetch_scratch("term detection on units", scratch, nbytes, dev, "sdtw_units")
+    score = torch.empty(n_pairs, dtype=torch.float32, device=dev)
+    span = torch.empty(n_pairs, 3, dtype=torch.int32, device=dev)
+    _lib.check(lib.cpc_sdtw_units(_lib.ptr(units), _lib.ptr(item_off), _lib.ptr(item_len), int(item_len.numel()), _lib.ptr(seg_q),
+                                  _lib.ptr(seg_start), _lib.ptr(pair_doc), n_seg, int(max_len_q), int(max_len_doc), float(d_same),
+                                  float(d_diff), _lib.ptr(score), _lib.ptr(span), _lib.ptr(scratch), nbytes, _lib.stream_ptr(dev)),
+               "cpc_sdtw_units")
+    return score, span
+
+
+def subsequence_dtw_units(units, item_off, item_len, queries, docs, d_same, d_diff, exclude=None, lens_host=None, cell_budget=None,
+                          target_segments=TARGET_SEGMENTS):
+    """subsequence_dtw on items of unit ids: units [total_frames] int32 on the device, d_same / d_diff the frame distance between
+    equal / different units.  The same plan and the same returns.  target_segments keeps the dense default of 4096: a workgroup
+    serves four pairs at once here, but a segment is still what a workgroup takes, and tools/term_units_bench.py does not vary
+    it, so there is no measured reason for another value."""
+    if not isinstance(units, torch.Tensor) or units.dtype != torch.int32 or not units.is_contiguous() or units.dim() != 1:
+        raise TypeError("term detection on units: units must be a contiguous int32 tensor [total_frames]")
+    _lib.require_gpu(units, item_off, item_len)
+    lens = np.asarray(item_len.cpu().numpy() if lens_host is None else lens_host, dtype=np.int64)
+    seg_q, seg_start, pair_doc, pair_q = plan_segments(queries, docs, lens, exclude, cell_budget, target_segments)
+    dev = units.device
+    if pair_doc.size == 0:
+        return (torch.empty(0, dtype=torch.float32, device=dev), torch.empty(0, 3, dtype=torch.int32, device=dev), pair_q,
+                pair_doc)
+    max_len_q = max(1, int(lens[seg_q].max()))
+    max_len_doc = max(1, int(lens[pair_doc].max()))
+    score, span = run_segments_units(units, item_off, item_len, torch.from_numpy(seg_q).to(dev), torch.from_numpy(seg_start).to(dev),
+                                     torch.from_numpy(pair_doc).to(dev), max_len_q, max_len_doc, d_same, d_diff)
+    return score, span, pair_q, pair_doc
+
+
 # --------------------------------------------------------------------------- ranking and scores
 def rank(score, pair_q, pair_doc):
     """Ranks per query: ascending score, ties by ascending document index, NaN last.  score [P] (any device), pair_q and

@@ -93,6 +93,46 @@ def local_alignment(frames, item_off, item_len, items, distance, theta, gamma, e
     return score, span, pair_a, pair_b
 
 
+# --------------------------------------------------------------------------- quantized units (csrc/lalign_units.hip)
+def run_segments_units(units, item_off, item_len, seg_a, seg_start, pair_b, max_len_a, max_len_b, d_same, d_diff, theta, gamma,
+                       scratch=None):
+    """cpc_local_align_units on a given work list (device int32 tensors): run_segments with the frames replaced by unit ids
+    [total_frames] int32 and the distance by its two values (d_same between equal units, d_diff between different ones;
+    abx_group_computation.unit_frame_distances makes them).  scratch: at least cpc_local_align_units_scratch_bytes."""
+    n_seg, n_pairs = td.check_unit_work_list("term discovery on units", units, item_off, item_len, seg_a, seg_start, pair_b,
+                                             ("seg_a", "pair_b"))
+    dev = units.device
+    lib = _lib.load()
+    nbytes = lib.cpc_local_align_units_scratch_bytes(n_seg, int(max_len_a), int(max_len_b))
+    scratch = td.fetch_scratch("term discovery on units", scratch, nbytes, dev, "lalign_units")
+    score = torch.empty(n_pairs, dtype=torch.float32, device=dev)
+    span = torch.empty(n_pairs, SPAN, dtype=torch.int32, device=dev)
+    _lib.check(lib.cpc_local_align_units(_lib.ptr(units), _lib.ptr(item_off), _lib.ptr(item_len), int(item_len.numel()),
+                                         _lib.ptr(seg_a), _lib.ptr(seg_start), _lib.ptr(pair_b), n_seg, int(max_len_a), int(max_len_b),
+                                         float(d_same), float(d_diff), float(theta), float(gamma), _lib.ptr(score), _lib.ptr(span),
+                                         _lib.ptr(scratch), nbytes, _lib.stream_ptr(dev)), "cpc_local_align_units")
+    return score, span
+
+
+def local_alignment_units(units, item_off, item_len, items, d_same, d_diff, theta, gamma, exclude=None, lens_host=None,
+                          cell_budget=None):
+    """local_alignment on items of unit ids: units [total_frames] int32 on the device, d_same / d_diff the frame distance between
+    equal / different units.  The same plan and the same returns."""
+    if not isinstance(units, torch.Tensor) or units.dtype != torch.int32 or not units.is_contiguous() or units.dim() != 1:
+        raise TypeError("term discovery on units: units must be a contiguous int32 tensor [total_frames]")
+    _lib.require_gpu(units, item_off, item_len)
+    lens = np.asarray(item_len.cpu().numpy() if lens_host is None else lens_host, dtype=np.int64)
+    seg_a, seg_start, pair_b, pair_a = plan_pairs(items, lens, exclude, cell_budget)
+    dev = units.device
+    if pair_b.size == 0:
+        return (torch.empty(0, dtype=torch.float32, device=dev), torch.empty(0, SPAN, dtype=torch.int32, device=dev), pair_a, pair_b)
+    max_len_a = max(1, int(lens[seg_a].max()))
+    max_len_b = max(1, int(lens[pair_b].max()))
+    score, span = run_segments_units(units, item_off, item_len, torch.from_numpy(seg_a).to(dev), torch.from_numpy(seg_start).to(dev),
+                                     torch.from_numpy(pair_b).to(dev), max_len_a, max_len_b, d_same, d_diff, theta, gamma)
+    return score, span, pair_a, pair_b
+
+
 # --------------------------------------------------------------------------- matches
 def select(score, span, min_frames, min_score):
     """The pairs kept as matches: both sides span at least min_frames frames (end - start + 1) and the score is at least

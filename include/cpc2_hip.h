@@ -68,7 +68,8 @@ int cpc_version(void);          /* 100 x major + minor; 105 = the entry points o
                                   * cpc_augment_bandreject;
                                   * 128 = cpc_sdtw (+ scratch query);
                                   * 129 = cpc_segment_units (+ scratch query) / cpc_segment_units_wave_k;
-                                  * 130 = cpc_local_align (+ scratch query) */
+                                  * 130 = cpc_local_align (+ scratch query);
+                                  * 131 = cpc_sdtw_units / cpc_local_align_units (+ scratch queries) */
 const char *cpc_last_error(void);
 
 /* In-situ kernel timing for bench.py: when enabled, the launchers bracket each launch of the named
@@ -601,6 +602,42 @@ int cpc_local_align(const float *frames, int dp, const int *item_off, const int 
                     const int *seg_start, const int *pair_b, int n_seg, int max_len_a, int max_len_b, int distance, float theta,
                     float gamma, float *score, int *span /* [pairs][5] int32: start_i, end_i, start_j, end_j, length */,
                     void *scratch, size_t scratch_bytes, cpc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Term detection and term discovery on quantized units (csrc/sdtw_units.hip, csrc/lalign_units.hip, version 131; DESIGN.md
+ * section 29).  `units` [total_frames] int32 as for cpc_abx_dtw_units: item i is units item_off[i] .. item_off[i] + item_len[i] - 1.
+ * Any int32 is a unit id: only equality is looked at.  The frame distance takes two values, given by the caller:
+ *     d[i][j] = d_same where the two units are equal, d_diff where they differ.
+ * With that d[i][j], cpc_sdtw_units is cpc_sdtw and cpc_local_align_units is cpc_local_align, word for word: the work list, the
+ * cell contents, the tie order diag, left, up, the free start on row 0, one f32 addition per cell and one f32 division per end
+ * column (subsequence); one f32 subtraction per gain and per candidate, open / continue / clamp, the best cell by (largest H,
+ * smallest i, smallest j) (alignment); the outputs, and NaN and -1 for a pair that is not computable.  The kernels run the same
+ * copy of each recurrence as the dense ones (csrc/sdtw_rule.h, csrc/lalign_rule.h).
+ *
+ * Not computable, both entry points: an item index outside [0, n_items), a length < 1, a row item (query) longer than
+ * max_len_q / max_len_a or a column item (document) longer than max_len_doc / max_len_b.
+ * Limits.  Alignment items have at most 32767 frames (max_len_a, max_len_b <= 32767); otherwise those of the dense entry points.
+ *
+ * Scratch, both queries: 0 when the row maximum is <= 64, else min(n_seg, 2048) workgroups x 4 waves x 2 buffers x 12 bytes x
+ * the column maximum (one wave serves one pair, so every wave keeps the boundary row of a 64-row strip, double-buffered; the
+ * launch has at most 2048 workgroups); negative sizes give 0 and a cpc_last_error text.  Units beyond an item are never read; the
+ * scratch's contents before the launch are never read; no atomics and no LDS: two launches give the same bytes.
+ * Bad arguments (a null buffer, a NaN d_same or d_diff, negative or zero sizes; for the alignment theta not finite or <= 0, gamma
+ * not finite or < 0, a maximum above 32767) return CPC_ERR_INVALID; a scratch that is too small returns CPC_ERR_INVALID from
+ * cpc_sdtw_units and CPC_ERR_WORKSPACE from cpc_local_align_units, as their dense siblings do; each with a cpc_last_error text
+ * that names the entry point (sdtw_units / local_align_units); nothing is launched and no output is written.
+ * ------------------------------------------------------------------------------------------ */
+size_t cpc_sdtw_units_scratch_bytes(int n_seg, int max_len_q, int max_len_doc);
+int cpc_sdtw_units(const int *units, const int *item_off, const int *item_len, int n_items, const int *seg_q,
+                   const int *seg_start, const int *pair_doc, int n_seg, int max_len_q, int max_len_doc, float d_same,
+                   float d_diff, float *score, int *span /* [pairs][3] int32: start, end, length */, void *scratch,
+                   size_t scratch_bytes, cpc_stream_t stream);
+size_t cpc_local_align_units_scratch_bytes(int n_seg, int max_len_a, int max_len_b);
+int cpc_local_align_units(const int *units, const int *item_off, const int *item_len, int n_items, const int *seg_a,
+                          const int *seg_start, const int *pair_b, int n_seg, int max_len_a, int max_len_b, float d_same,
+                          float d_diff, float theta, float gamma, float *score,
+                          int *span /* [pairs][5] int32: start_i, end_i, start_j, end_j, length */, void *scratch,
+                          size_t scratch_bytes, cpc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * k-means on features (cpc/clustering/clustering.py of the reference).  x [n][d] rows, ck [k][d] centroids, all fp32 DEVICE
