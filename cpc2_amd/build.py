@@ -48,7 +48,7 @@ def _newer(target, deps):
 def build(force=False, verbose=True):
     objdir = os.path.join(HERE, "..", "build")
     os.makedirs(objdir, exist_ok=True)
-    headers = [os.path.abspath(__file__), os.path.join(CSRC, "common.h"), os.path.join(CSRC, "rowcfg.h"), os.path.join(CSRC, "coop.h"), os.path.join(CSRC, "recurrent.h"), os.path.join(CSRC, "ldsdma.h"), os.path.join(CSRC, "text_digits.h"), os.path.join(CSRC, "ctc_lattice.h"), os.path.join(CSRC, "moment_tiles.h"), os.path.join(CSRC, "dist_tile.h"), os.path.join(CSRC, "dtw_strip.h"), os.path.join(CSRC, "dtw_units_walk.h"), os.path.join(CSRC, "sdtw_rule.h"), os.path.join(CSRC, "lalign_rule.h"), os.path.join(HERE, "..", "include", "cpc2_hip.h")]
+    headers = [os.path.abspath(__file__), os.path.join(CSRC, "common.h"), os.path.join(CSRC, "rowcfg.h"), os.path.join(CSRC, "coop.h"), os.path.join(CSRC, "recurrent.h"), os.path.join(CSRC, "ldsdma.h"), os.path.join(CSRC, "text_digits.h"), os.path.join(CSRC, "ctc_lattice.h"), os.path.join(CSRC, "moment_tiles.h"), os.path.join(CSRC, "dist_tile.h"), os.path.join(CSRC, "dtw_strip.h"), os.path.join(CSRC, "dtw_units_walk.h"), os.path.join(CSRC, "abx_rule.h"), os.path.join(CSRC, "sdtw_rule.h"), os.path.join(CSRC, "lalign_rule.h"), os.path.join(HERE, "..", "include", "cpc2_hip.h")]
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
     if not force and _newer(LIB, srcs + headers):
         return LIB

@@ -4,11 +4,12 @@
 //
 //   abx_dtw_kernel     one workgroup per x item (a "segment") and its list of y items, walked as dtw_strip.h says.  What is
 //                      this file's: the distance tile (one entry per thread, true f32 FMAs, k-ordered: ABX items have 3 to 25
-//                      frames) and the recurrence.  Each cell carries (cost, path length); the length follows the reference's
-//                      backtrack tie rule, so no cost matrix and no backtrack are needed.
+//                      frames).  The recurrence is abx_rule.h's, shared with abx_units.hip; AbxDenseRule adds the write of the
+//                      result, from `visit` of the last cell.
 //   abx_counts_kernel  one workgroup per triplet: counts dxa < dxb and dxa == dxb over its Nx x Na x Nb comparisons,
 //                      reading the pair results through index lists (-1 = excluded diagonal).  Integer counts: deterministic.
 #include "common.h"
+#include "abx_rule.h"
 #include "dtw_strip.h"
 
 namespace cpc {
@@ -16,8 +17,6 @@ namespace {
 
 constexpr int ABX_KC = 32;         // feature chunk staged in LDS per pass
 constexpr int ABX_ACC = DTW_T * DTW_T / DTW_THREADS;   // distance entries per thread
-constexpr int ABX_W = 2;           // (cost, length): 8 bytes per boundary-row column
-using AbxCell = DtwCell<ABX_W>;
 
 // dt[r][c] = distance of frame row0 + r to frame col0 + c for r < R, c < C: acc over the feature dim, a k-ordered fma chain per
 // entry.  Called by all threads of the workgroup; opens with a barrier before xs / ys / dt are rewritten, ends with one.
@@ -73,16 +72,16 @@ __device__ __forceinline__ void abx_distance_tile(const float *__restrict__ fram
     __syncthreads();
 }
 
-struct AbxRule {
+// The shared recurrence and, for this walk, which returns nothing, the result written when the last cell is visited.  (A walk
+// that returned the last cell instead left abx_dtw_kernel faster and sdtw_kernel 1 to 2 % slower: profiles/dtw_units_refactor.md.)
+struct AbxDenseRule : AbxRule {
     int lx, ly, p;
     float *__restrict__ out;
     int *__restrict__ path_len;
 
-    __device__ __forceinline__ AbxCell cell(int gi, int gj, float d, const AbxCell &diag, const AbxCell &left, const AbxCell &up) const
+    __device__ __forceinline__ AbxDenseRule(int lx, int ly, int p, float *out, int *path_len)
+        : lx(lx), ly(ly), p(p), out(out), path_len(path_len)
     {
-        if (gi == 0 && gj == 0) return {d, {1}};
-        const AbxCell pred = dtw_pick(gi == 0, left, dtw_pick(gj == 0, up, dtw_cheapest(diag, left, up)));
-        return {d + pred.v, {pred.n[DTW_LEN] + 1}};
     }
     __device__ __forceinline__ void visit(int gi, int gj, const AbxCell &c) const
     {
@@ -91,7 +90,6 @@ struct AbxRule {
             if (path_len) path_len[p] = c.n[DTW_LEN];
         }
     }
-    __device__ __forceinline__ void strip_done(int, int, bool) const {}
 };
 
 __global__ void __launch_bounds__(DTW_THREADS)
@@ -115,7 +113,7 @@ abx_dtw_kernel(const float *__restrict__ frames, int dp, const int *__restrict__
                 }
                 continue;
             }
-            AbxRule rule{x.len, y.len, p, out, path_len};
+            AbxDenseRule rule(x.len, y.len, p, out, path_len);
             dtw_walk_pair(bnd, x.len, y.len, dt, rule, [&](int rs, int R, int cb, int C) {
                 abx_distance_tile(frames, dp, x.off + rs, R, y.off + cb, C, euclid, xs, ys, dt);
             });

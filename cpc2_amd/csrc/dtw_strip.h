@@ -2,8 +2,9 @@
 // 64 x 64 tiles of frame distances, the DP of a tile on wave 0 with lane = row and step = anti-diagonal, row items longer than 64
 // frames in 64-row strips whose last row waits for the next strip in per-workgroup scratch.  DESIGN.md section 7 has the scheme.
 // A kernel brings a Rule: its cell (how many words), its recurrence, what it notes of a finished cell and of a finished strip.
-// Everything here inlines: a cell and a rule's state live in registers.  abx_units.hip walks differently (one wave per pair, no
-// tiles) and takes only shr1 and the grid cap from here.
+// Everything here inlines: a cell and a rule's state live in registers.  The kernels on unit ids (abx_units.hip, sdtw_units.hip,
+// lalign_units.hip) walk differently (one wave per pair, no tiles): dtw_units_walk.h, which takes the cell, shr1, dtw_pick and
+// dtw_item from here.
 #pragma once
 
 #include "common.h"
@@ -109,7 +110,8 @@ __device__ __forceinline__ DtwItem dtw_item(const int *__restrict__ item_off, co
 // with the same arguments.  fill_tile(rs, R, cb, C) is called by all of them and leaves the distances of rows rs .. rs + R - 1
 // against columns cb .. cb + C - 1 in dt[r][c] behind a workgroup barrier (and opens with one, before it rewrites dt).
 // Wave 0 then runs the tile's cells, and for each cell (gi, gj), in an order in which diag, left and up are finished:
-//     cell = rule.cell(gi, gj, d, diag, left, up)     the new cell; a neighbour outside the matrix is not a cell: the rule ignores it
+//     cell = rule.cell(gi, gj, d, diag, left, up)     the new cell; a neighbour outside the matrix is not a cell: the rule ignores
+//                                                     it, but may count on `left` being the zero cell at column 0
 //     rule.visit(gi, gj, cell)                        by the lane of row gi % 64
 // and after the last tile of a strip, in all 64 lanes, rule.strip_done(rs, R, more_strips).
 template <int W, class Rule, class FillTile>

@@ -1,7 +1,6 @@
-// The walk of the DTW kernels on UNIT IDS (sdtw_units.hip, lalign_units.hip), in one copy.  On units the frame distance takes two
+// The walk of the DTW kernels on UNIT IDS (abx_units.hip, sdtw_units.hip, lalign_units.hip), in one copy.  On units the frame distance takes two
 // values, d_same (equal units) and d_diff, so there is no distance tile, no LDS and no workgroup barrier: a kernel is its
-// recurrence alone, and every wave runs it.  DESIGN.md section 29 has the scheme, which is that of abx_dtw_units_kernel
-// (abx_units.hip, section 7.1):
+// recurrence alone, and every wave runs it.  DESIGN.md section 29 has the scheme:
 //   - one workgroup of 256 threads per segment, ONE WAVE PER (row item, column item) PAIR: the four waves take the segment's
 //     pairs round robin and never synchronise;
 //   - lane = row of the row item (strips of 64 rows), step t = one anti-diagonal over ALL columns of the column item;
@@ -12,8 +11,7 @@
 //   - lanes outside the matrix are masked by selects, not branches; the caller takes its wave index through readfirstlane, so
 //     lengths and loop bounds are scalars.
 // A kernel brings a Rule with the interface of dtw_walk_pair (dtw_strip.h): cell, visit, strip_done; the dense and the unit
-// kernels share their Rules (sdtw_rule.h, lalign_rule.h).  abx_units.hip keeps its own copy of this walk in this version: moving
-// it here is a follow-up, once this walk has measured numbers beside it.
+// kernels share their Rules (abx_rule.h, sdtw_rule.h, lalign_rule.h).
 #pragma once
 
 #include "dtw_strip.h"
@@ -23,8 +21,10 @@ namespace cpc {
 constexpr int DTWU_T = 64;                       // strip height (rows = lanes)
 constexpr int DTWU_THREADS = 256;
 constexpr int DTWU_WAVES = DTWU_THREADS / 64;
-// 2048 workgroups = 8192 waves: every wave slot of 256 CUs x 4 SIMDs at 8 waves per SIMD.  The kernels loop over segments with a
-// grid stride, so a larger grid would buy nothing and multiply the per-wave boundary rows.
+// The grid cap is the entry point's (the kernels loop over segments with a grid stride, and the scratch grows with the grid).
+// 2048 workgroups = 8192 waves: every wave slot of 256 CUs x 4 SIMDs at 8 waves per SIMD; the two term kernels take it.
+// cpc_abx_dtw_units keeps the 8192 of the dense kernels (DTW_MAX_BLOCKS), with which it was written and measured.  The two caps
+// have not been measured against each other on that kernel.
 constexpr int DTWU_MAX_BLOCKS = 2048;
 
 // The boundary rows of one wave: two buffers, swapped per strip, of W planes of max_len_col words each.  Word w of column j of
@@ -85,21 +85,25 @@ __device__ __forceinline__ DtwCell<W> shr1(const DtwCell<W> &c, const DtwCell<W>
 // (1 <= len_col <= the max_len_col of bnd; len_row > 64 only with scratch).  The row item is units[row_off ..], the column item
 // units[col_off ..]; nothing outside them is read.  For each cell (gi, gj), in an order in which diag, left and up are finished:
 //     cell = rule.cell(gi, gj, d, diag, left, up)     d = d_same where the two units are equal, else d_diff; a neighbour outside
-//                                                     the matrix is not a cell: the rule ignores it
+//                                                     the matrix is not a cell: the rule ignores it, but may count on
+//                                                     `left` being the zero cell at column 0
 //     rule.visit(gi, gj, cell)                        by the lane of row gi % 64
 // and after the last step of a strip, in all 64 lanes, rule.strip_done(rs, R, more_strips).
+// Returns the calling lane's newest cell of the last strip: in lane (len_row - 1) % 64 the cell (len_row - 1, len_col - 1).
 template <int W, class Rule>
-__device__ __forceinline__ void dtw_units_walk_pair(const DtwWaveBoundary<W> &bnd, const int *__restrict__ units, long row_off,
-                                                    int len_row, long col_off, int len_col, float d_same, float d_diff, Rule &rule)
+__device__ __forceinline__ DtwCell<W> dtw_units_walk_pair(const DtwWaveBoundary<W> &bnd, const int *__restrict__ units, long row_off,
+                                                          int len_row, long col_off, int len_col, float d_same, float d_diff,
+                                                          Rule &rule)
 {
     const int r = threadIdx.x & 63;
     int cur = 0;                                             // boundary buffer read by this strip
+    DtwCell<W> cell = {};                                    // this lane's newest cell in its row
     for (int rs = 0; rs < len_row; rs += DTWU_T) {
         const int R = min(DTWU_T, len_row - rs);
         const bool more_strips = rs + DTWU_T < len_row;
         const int gi = rs + r;
         const int xu = r < R ? units[row_off + gi] : 0;      // (a lane without a row is never active: its unit is not looked at)
-        DtwCell<W> cell = {};                                // this lane's newest cell in its row
+        cell = {};
         DtwCell<W> pup = {};                                 // the up cell of the previous step (= this step's diag)
         int yu = 0;                                          // y[t - r]
         const int steps = R + len_col - 1;
@@ -139,22 +143,23 @@ __device__ __forceinline__ void dtw_units_walk_pair(const DtwWaveBoundary<W> &bn
         cur ^= 1;
         __threadfence_block();                               // boundary row visible to the next strip's reads
     }
+    return cell;
 }
 
 // ---- host side ----
-inline int dtw_units_grid(int n) { return std::min(n, DTWU_MAX_BLOCKS); }
+inline int dtw_units_grid(int n, int max_blocks) { return std::min(n, max_blocks); }
 
-// Bytes of the boundary rows of a launch over n_seg segments: per wave two buffers of max_len_col cells of W words; nothing when
-// one strip holds every row item.  Negative sizes give 0 with a message that names `what`.
+// Bytes of the boundary rows of a launch over n_seg segments on at most max_blocks workgroups: per wave two buffers of
+// max_len_col cells of W words; nothing when one strip holds every row item.  Negative sizes give 0 with a message that names `what`.
 inline size_t dtw_units_scratch_bytes(const char *what, int n_seg, const char *row, int max_len_row, const char *col, int max_len_col,
-                                      int W)
+                                      int W, int max_blocks)
 {
     if (n_seg < 0 || max_len_row < 0 || max_len_col < 0) {
         set_error("%s: negative size (n_seg=%d %s=%d %s=%d)", what, n_seg, row, max_len_row, col, max_len_col);
         return 0;
     }
     if (n_seg == 0 || max_len_col == 0 || max_len_row <= DTWU_T) return 0;
-    return (size_t)dtw_units_grid(n_seg) * DTWU_WAVES * 2 * (size_t)max_len_col * 4 * (size_t)W;
+    return (size_t)dtw_units_grid(n_seg, max_blocks) * DTWU_WAVES * 2 * (size_t)max_len_col * 4 * (size_t)W;
 }
 
 // The checks that the unit entry points repeat.  `what` is the entry point's label and row / col its names of the two size

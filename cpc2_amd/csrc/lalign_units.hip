@@ -57,7 +57,8 @@ lalign_units_kernel(const int *__restrict__ units, const int *__restrict__ item_
 
 extern "C" size_t cpc_local_align_units_scratch_bytes(int n_seg, int max_len_a, int max_len_b)
 {
-    return cpc::dtw_units_scratch_bytes("local_align_units", n_seg, "max_len_a", max_len_a, "max_len_b", max_len_b, cpc::LA_W);
+    return cpc::dtw_units_scratch_bytes("local_align_units", n_seg, "max_len_a", max_len_a, "max_len_b", max_len_b, cpc::LA_W,
+                                        cpc::DTWU_MAX_BLOCKS);
 }
 
 extern "C" int cpc_local_align_units(const int *units, const int *item_off, const int *item_len, int n_items, const int *seg_a,
@@ -82,9 +83,9 @@ extern "C" int cpc_local_align_units(const int *units, const int *item_off, cons
         return CPC_ERR_WORKSPACE;
     }
     if (n_seg == 0) return CPC_OK;
-    hipLaunchKernelGGL(cpc::lalign_units_kernel, dim3((unsigned)cpc::dtw_units_grid(n_seg)), dim3(cpc::DTWU_THREADS), 0,
-                       static_cast<hipStream_t>(stream), units, item_off, item_len, n_items, seg_a, seg_start, pair_b, n_seg,
-                       max_len_a, max_len_b, d_same, d_diff, theta, gamma, score, span,
+    hipLaunchKernelGGL(cpc::lalign_units_kernel, dim3((unsigned)cpc::dtw_units_grid(n_seg, cpc::DTWU_MAX_BLOCKS)),
+                       dim3(cpc::DTWU_THREADS), 0, static_cast<hipStream_t>(stream), units, item_off, item_len, n_items, seg_a,
+                       seg_start, pair_b, n_seg, max_len_a, max_len_b, d_same, d_diff, theta, gamma, score, span,
                        need ? static_cast<char *>(scratch) : nullptr);
     CPC_CHECK_LAUNCH("lalign_units_kernel");
     return CPC_OK;

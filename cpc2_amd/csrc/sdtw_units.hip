@@ -53,7 +53,8 @@ sdtw_units_kernel(const int *__restrict__ units, const int *__restrict__ item_of
 
 extern "C" size_t cpc_sdtw_units_scratch_bytes(int n_seg, int max_len_q, int max_len_doc)
 {
-    return cpc::dtw_units_scratch_bytes("sdtw_units", n_seg, "max_len_q", max_len_q, "max_len_doc", max_len_doc, cpc::SD_W);
+    return cpc::dtw_units_scratch_bytes("sdtw_units", n_seg, "max_len_q", max_len_q, "max_len_doc", max_len_doc, cpc::SD_W,
+                                        cpc::DTWU_MAX_BLOCKS);
 }
 
 extern "C" int cpc_sdtw_units(const int *units, const int *item_off, const int *item_len, int n_items, const int *seg_q,
@@ -68,9 +69,10 @@ extern "C" int cpc_sdtw_units(const int *units, const int *item_off, const int *
     CPC_REQUIRE(scratch_bytes >= need && (need == 0 || scratch != nullptr), "sdtw_units: scratch of %zu bytes, %zu needed",
                 scratch_bytes, need);
     if (n_seg == 0) return CPC_OK;
-    hipLaunchKernelGGL(cpc::sdtw_units_kernel, dim3((unsigned)cpc::dtw_units_grid(n_seg)), dim3(cpc::DTWU_THREADS), 0,
-                       static_cast<hipStream_t>(stream), units, item_off, item_len, n_items, seg_q, seg_start, pair_doc, n_seg,
-                       max_len_q, max_len_doc, d_same, d_diff, score, span, need ? static_cast<char *>(scratch) : nullptr);
+    hipLaunchKernelGGL(cpc::sdtw_units_kernel, dim3((unsigned)cpc::dtw_units_grid(n_seg, cpc::DTWU_MAX_BLOCKS)),
+                       dim3(cpc::DTWU_THREADS), 0, static_cast<hipStream_t>(stream), units, item_off, item_len, n_items, seg_q,
+                       seg_start, pair_doc, n_seg, max_len_q, max_len_doc, d_same, d_diff, score, span,
+                       need ? static_cast<char *>(scratch) : nullptr);
     CPC_CHECK_LAUNCH("sdtw_units_kernel");
     return CPC_OK;
 }

@@ -156,40 +156,26 @@ def _segment_lists(items, px, py):
             torch.from_numpy(np.ascontiguousarray(py, dtype=np.int32)).to(dev), len(seg_x), max_lx, max_ly)
 
 
-def _dtw_pairs_units(items, px, py, code):
-    """_dtw_pairs on items of unit ids: cpc_abx_dtw_units with the two frame distances of `code`."""
-    dev = items.device
-    n = int(px.shape[0])
-    d_seg_x, d_seg_start, d_py, n_seg, max_lx, max_ly = _segment_lists(items, px, py)
-    d_same, d_diff = items.distances[code]
-    lib = _lib.load()
-    nbytes = lib.cpc_abx_dtw_units_scratch_bytes(n_seg, max_lx, max_ly)
-    scratch = _lib.scratch(nbytes, dev, tag="abx") if nbytes else None
-    out = torch.empty(n, dtype=torch.float32, device=dev)
-    plen = torch.empty(n, dtype=torch.int32, device=dev)
-    _lib.check(lib.cpc_abx_dtw_units(_lib.ptr(items.units), _lib.ptr(items.off), _lib.ptr(items.lens), items.n,
-                                     _lib.ptr(d_seg_x), _lib.ptr(d_seg_start), _lib.ptr(d_py), n_seg, max_lx, max_ly,
-                                     d_same, d_diff, _lib.ptr(out), _lib.ptr(plen), _lib.ptr(scratch), nbytes,
-                                     _lib.stream_ptr(dev)), "cpc_abx_dtw_units")
-    return out, plen
-
-
 def _dtw_pairs(items, px, py, code):
-    """DTW of the pairs (px[p], py[p]) (item indices, sorted by px) on the device: (values [n] fp32, path lengths)."""
+    """DTW of the pairs (px[p], py[p]) (item indices, sorted by px) on the device: (values [n] fp32, path lengths).  Items of
+    unit ids go through cpc_abx_dtw_units with the two frame distances of `code`, frames through cpc_abx_dtw."""
+    lib = _lib.load()
     if isinstance(items, _UnitItems):
-        return _dtw_pairs_units(items, px, py, code)
+        name, query, call = "cpc_abx_dtw_units", lib.cpc_abx_dtw_units_scratch_bytes, lib.cpc_abx_dtw_units
+        head, params = (_lib.ptr(items.units),), items.distances[code]
+    else:
+        name, query, call = "cpc_abx_dtw", lib.cpc_abx_dtw_scratch_bytes, lib.cpc_abx_dtw
+        head, params = (_lib.ptr(items.frames), items.frames.size(1)), (code,)
     dev = items.device
     n = int(px.shape[0])
     d_seg_x, d_seg_start, d_py, n_seg, max_lx, max_ly = _segment_lists(items, px, py)
-    lib = _lib.load()
-    nbytes = lib.cpc_abx_dtw_scratch_bytes(n_seg, max_lx, max_ly)
+    nbytes = query(n_seg, max_lx, max_ly)
     scratch = _lib.scratch(nbytes, dev, tag="abx") if nbytes else None
     out = torch.empty(n, dtype=torch.float32, device=dev)
     plen = torch.empty(n, dtype=torch.int32, device=dev)
-    _lib.check(lib.cpc_abx_dtw(_lib.ptr(items.frames), items.frames.size(1), _lib.ptr(items.off), _lib.ptr(items.lens),
-                               items.n, _lib.ptr(d_seg_x), _lib.ptr(d_seg_start), _lib.ptr(d_py), n_seg, max_lx,
-                               max_ly, code, _lib.ptr(out), _lib.ptr(plen), _lib.ptr(scratch), nbytes,
-                               _lib.stream_ptr(dev)), "cpc_abx_dtw")
+    _lib.check(call(*head, _lib.ptr(items.off), _lib.ptr(items.lens), items.n, _lib.ptr(d_seg_x), _lib.ptr(d_seg_start),
+                    _lib.ptr(d_py), n_seg, max_lx, max_ly, *params, _lib.ptr(out), _lib.ptr(plen), _lib.ptr(scratch), nbytes,
+                    _lib.stream_ptr(dev)), name)
     return out, plen
 
 

@@ -107,13 +107,26 @@ def check_work_list(what, frames, item_off, item_len, seg_row, seg_start, pair_c
     return frames, n_seg, n_pairs
 
 
-def fetch_scratch(what, scratch, nbytes, dev, tag):
-    """The boundary-row buffer of a run_segments: the caller's when it holds nbytes, else the package's arena (None for 0 bytes)."""
+def _call_segments(what, name, query, call, tag, head, work, sizes, params, span_width, scratch):
+    """The library call of a run_segments (here and in term_discovery): `call` (the entry point `name`) on a checked work list.
+    head: the arguments before item_off, the device tensor of frames or units first; work: item_off, item_len, seg_row, seg_start,
+    pair_col; sizes: n_seg, n_pairs, max_len_row, max_len_col; params: the arguments between max_len_col and score.  The
+    boundary-row buffer is the caller's `scratch` when it holds query(...) bytes, else the package's arena under `tag` (None for 0
+    bytes).  Returns (score [P] f32, span [P, span_width] int32)."""
+    dev = head[0].device
+    item_off, item_len, seg_row, seg_start, pair_col = work
+    n_seg, n_pairs, max_len_row, max_len_col = (int(v) for v in sizes)
+    nbytes = query(n_seg, max_len_row, max_len_col)
     if scratch is None:
-        return _lib.scratch(nbytes, dev, tag=tag) if nbytes else None
-    if scratch.numel() * scratch.element_size() < nbytes:
+        scratch = _lib.scratch(nbytes, dev, tag=tag) if nbytes else None
+    elif scratch.numel() * scratch.element_size() < nbytes:
         raise ValueError(f"{what}: scratch of {scratch.numel() * scratch.element_size()} bytes, {nbytes} needed")
-    return scratch
+    score = torch.empty(n_pairs, dtype=torch.float32, device=dev)
+    span = torch.empty(n_pairs, span_width, dtype=torch.int32, device=dev)
+    _lib.check(call(_lib.ptr(head[0]), *head[1:], _lib.ptr(item_off), _lib.ptr(item_len), int(item_len.numel()), _lib.ptr(seg_row),
+                    _lib.ptr(seg_start), _lib.ptr(pair_col), n_seg, max_len_row, max_len_col, *params, _lib.ptr(score),
+                    _lib.ptr(span), _lib.ptr(scratch), nbytes, _lib.stream_ptr(dev)), name)
+    return score, span
 
 
 def run_segments(frames, item_off, item_len, seg_q, seg_start, pair_doc, max_len_q, max_len_doc, distance, scratch=None):
@@ -121,17 +134,26 @@ def run_segments(frames, item_off, item_len, seg_q, seg_start, pair_doc, max_len
     a device buffer of at least cpc_sdtw_scratch_bytes (default: the package's arena)."""
     frames, n_seg, n_pairs = check_work_list("term detection", frames, item_off, item_len, seg_q, seg_start, pair_doc,
                                              ("seg_q", "pair_doc"))
-    dev = frames.device
     lib = _lib.load()
-    nbytes = lib.cpc_sdtw_scratch_bytes(n_seg, int(max_len_q), int(max_len_doc))
-    scratch = fetch_scratch("term detection", scratch, nbytes, dev, "sdtw")
-    score = torch.empty(n_pairs, dtype=torch.float32, device=dev)
-    span = torch.empty(n_pairs, 3, dtype=torch.int32, device=dev)
-    _lib.check(lib.cpc_sdtw(_lib.ptr(frames), frames.size(1), _lib.ptr(item_off), _lib.ptr(item_len), int(item_len.numel()),
-                            _lib.ptr(seg_q), _lib.ptr(seg_start), _lib.ptr(pair_doc), n_seg, int(max_len_q), int(max_len_doc),
-                            int(distance), _lib.ptr(score), _lib.ptr(span), _lib.ptr(scratch), nbytes, _lib.stream_ptr(dev)),
-               "cpc_sdtw")
-    return score, span
+    return _call_segments("term detection", "cpc_sdtw", lib.cpc_sdtw_scratch_bytes, lib.cpc_sdtw, "sdtw", (frames, frames.size(1)),
+                          (item_off, item_len, seg_q, seg_start, pair_doc), (n_seg, n_pairs, max_len_q, max_len_doc),
+                          (int(distance),), 3, scratch)
+
+
+def _subsequence(run, data, item_len, queries, docs, exclude, lens_host, cell_budget, target_segments):
+    """What subsequence_dtw and subsequence_dtw_units do once `data` (frames or units) is checked: the plan on the host, its upload,
+    and run(seg_q, seg_start, pair_doc, max_len_q, max_len_doc), the run_segments of the kind."""
+    lens = np.asarray(item_len.cpu().numpy() if lens_host is None else lens_host, dtype=np.int64)
+    seg_q, seg_start, pair_doc, pair_q = plan_segments(queries, docs, lens, exclude, cell_budget, target_segments)
+    dev = data.device
+    if pair_doc.size == 0:
+        return (torch.empty(0, dtype=torch.float32, device=dev), torch.empty(0, 3, dtype=torch.int32, device=dev), pair_q,
+                pair_doc)
+    max_len_q = max(1, int(lens[seg_q].max()))
+    max_len_doc = max(1, int(lens[pair_doc].max()))
+    score, span = run(torch.from_numpy(seg_q).to(dev), torch.from_numpy(seg_start).to(dev), torch.from_numpy(pair_doc).to(dev),
+                      max_len_q, max_len_doc)
+    return score, span, pair_q, pair_doc
 
 
 def subsequence_dtw(frames, item_off, item_len, queries, docs, distance, exclude=None, lens_host=None, cell_budget=None,
@@ -144,17 +166,8 @@ def subsequence_dtw(frames, item_off, item_len, queries, docs, distance, exclude
     _lib.require_gpu(frames, item_off, item_len)
     if isinstance(distance, str):
         distance = distance_code(distance)
-    lens = np.asarray(item_len.cpu().numpy() if lens_host is None else lens_host, dtype=np.int64)
-    seg_q, seg_start, pair_doc, pair_q = plan_segments(queries, docs, lens, exclude, cell_budget, target_segments)
-    dev = frames.device
-    if pair_doc.size == 0:
-        return (torch.empty(0, dtype=torch.float32, device=dev), torch.empty(0, 3, dtype=torch.int32, device=dev), pair_q,
-                pair_doc)
-    max_len_q = max(1, int(lens[seg_q].max()))
-    max_len_doc = max(1, int(lens[pair_doc].max()))
-    score, span = run_segments(frames, item_off, item_len, torch.from_numpy(seg_q).to(dev), torch.from_numpy(seg_start).to(dev),
-                               torch.from_numpy(pair_doc).to(dev), max_len_q, max_len_doc, distance)
-    return score, span, pair_q, pair_doc
+    return _subsequence(lambda *work: run_segments(frames, item_off, item_len, *work, distance), frames, item_len, queries,
+                        docs, exclude, lens_host, cell_budget, target_segments)
 
 
 # --------------------------------------------------------------------------- quantized units (csrc/sdtw_units.hip)
@@ -174,23 +187,23 @@ def check_unit_work_list(what, units, item_off, item_len, seg_row, seg_start, pa
     return n_seg, n_pairs
 
 
+def _check_units(what, units, item_off, item_len):
+    """The input check of subsequence_dtw_units and term_discovery.local_alignment_units."""
+    if not isinstance(units, torch.Tensor) or units.dtype != torch.int32 or not units.is_contiguous() or units.dim() != 1:
+        raise TypeError(f"{what}: units must be a contiguous int32 tensor [total_frames]")
+    _lib.require_gpu(units, item_off, item_len)
+
+
 def run_segments_units(units, item_off, item_len, seg_q, seg_start, pair_doc, max_len_q, max_len_doc, d_same, d_diff, scratch=None):
     """cpc_sdtw_units on a given work list (device int32 tensors): run_segments with the frames replaced by unit ids
     [total_frames] int32 and the distance by its two values (d_same between equal units, d_diff between different ones;
     abx_group_computation.unit_frame_distances makes them).  scratch: at least cpc_sdtw_units_scratch_bytes."""
     n_seg, n_pairs = check_unit_work_list("term detection on units", units, item_off, item_len, seg_q, seg_start, pair_doc,
                                           ("seg_q", "pair_doc"))
-    dev = units.device
     lib = _lib.load()
-    nbytes = lib.cpc_sdtw_units_scratch_bytes(n_seg, int(max_len_q), int(max_len_doc))
-    scratch = fetch_scratch("term detection on units", scratch, nbytes, dev, "sdtw_units")
-    score = torch.empty(n_pairs, dtype=torch.float32, device=dev)
-    span = torch.empty(n_pairs, 3, dtype=torch.int32, device=dev)
-    _lib.check(lib.cpc_sdtw_units(_lib.ptr(units), _lib.ptr(item_off), _lib.ptr(item_len), int(item_len.numel()), _lib.ptr(seg_q),
-                                  _lib.ptr(seg_start), _lib.ptr(pair_doc), n_seg, int(max_len_q), int(max_len_doc), float(d_same),
-                                  float(d_diff), _lib.ptr(score), _lib.ptr(span), _lib.ptr(scratch), nbytes, _lib.stream_ptr(dev)),
-               "cpc_sdtw_units")
-    return score, span
+    return _call_segments("term detection on units", "cpc_sdtw_units", lib.cpc_sdtw_units_scratch_bytes, lib.cpc_sdtw_units,
+                          "sdtw_units", (units,), (item_off, item_len, seg_q, seg_start, pair_doc),
+                          (n_seg, n_pairs, max_len_q, max_len_doc), (float(d_same), float(d_diff)), 3, scratch)
 
 
 def subsequence_dtw_units(units, item_off, item_len, queries, docs, d_same, d_diff, exclude=None, lens_host=None, cell_budget=None,
@@ -199,20 +212,9 @@ def subsequence_dtw_units(units, item_off, item_len, queries, docs, d_same, d_di
     equal / different units.  The same plan and the same returns.  target_segments keeps the dense default of 4096: a workgroup
     serves four pairs at once here, but a segment is still what a workgroup takes, and tools/term_units_bench.py does not vary
     it, so there is no measured reason for another value."""
-    if not isinstance(units, torch.Tensor) or units.dtype != torch.int32 or not units.is_contiguous() or units.dim() != 1:
-        raise TypeError("term detection on units: units must be a contiguous int32 tensor [total_frames]")
-    _lib.require_gpu(units, item_off, item_len)
-    lens = np.asarray(item_len.cpu().numpy() if lens_host is None else lens_host, dtype=np.int64)
-    seg_q, seg_start, pair_doc, pair_q = plan_segments(queries, docs, lens, exclude, cell_budget, target_segments)
-    dev = units.device
-    if pair_doc.size == 0:
-        return (torch.empty(0, dtype=torch.float32, device=dev), torch.empty(0, 3, dtype=torch.int32, device=dev), pair_q,
-                pair_doc)
-    max_len_q = max(1, int(lens[seg_q].max()))
-    max_len_doc = max(1, int(lens[pair_doc].max()))
-    score, span = run_segments_units(units, item_off, item_len, torch.from_numpy(seg_q).to(dev), torch.from_numpy(seg_start).to(dev),
-                                     torch.from_numpy(pair_doc).to(dev), max_len_q, max_len_doc, d_same, d_diff)
-    return score, span, pair_q, pair_doc
+    _check_units("term detection on units", units, item_off, item_len)
+    return _subsequence(lambda *work: run_segments_units(units, item_off, item_len, *work, d_same, d_diff), units, item_len,
+                        queries, docs, exclude, lens_host, cell_budget, target_segments)
 
 
 # --------------------------------------------------------------------------- ranking and scores

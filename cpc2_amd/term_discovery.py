@@ -59,17 +59,25 @@ def run_segments(frames, item_off, item_len, seg_a, seg_start, pair_b, max_len_a
     end_j, length).  scratch: a device buffer of at least cpc_local_align_scratch_bytes (default: the package's arena)."""
     frames, n_seg, n_pairs = td.check_work_list("term discovery", frames, item_off, item_len, seg_a, seg_start, pair_b,
                                                 ("seg_a", "pair_b"))
-    dev = frames.device
     lib = _lib.load()
-    nbytes = lib.cpc_local_align_scratch_bytes(n_seg, int(max_len_a), int(max_len_b))
-    scratch = td.fetch_scratch("term discovery", scratch, nbytes, dev, "lalign")
-    score = torch.empty(n_pairs, dtype=torch.float32, device=dev)
-    span = torch.empty(n_pairs, SPAN, dtype=torch.int32, device=dev)
-    _lib.check(lib.cpc_local_align(_lib.ptr(frames), frames.size(1), _lib.ptr(item_off), _lib.ptr(item_len), int(item_len.numel()),
-                                   _lib.ptr(seg_a), _lib.ptr(seg_start), _lib.ptr(pair_b), n_seg, int(max_len_a), int(max_len_b),
-                                   int(distance), float(theta), float(gamma), _lib.ptr(score), _lib.ptr(span), _lib.ptr(scratch),
-                                   nbytes, _lib.stream_ptr(dev)), "cpc_local_align")
-    return score, span
+    return td._call_segments("term discovery", "cpc_local_align", lib.cpc_local_align_scratch_bytes, lib.cpc_local_align, "lalign",
+                             (frames, frames.size(1)), (item_off, item_len, seg_a, seg_start, pair_b),
+                             (n_seg, n_pairs, max_len_a, max_len_b), (int(distance), float(theta), float(gamma)), SPAN, scratch)
+
+
+def _local_alignment(run, data, item_len, items, exclude, lens_host, cell_budget):
+    """What local_alignment and local_alignment_units do once `data` (frames or units) is checked: the plan on the host, its
+    upload, and run(seg_a, seg_start, pair_b, max_len_a, max_len_b), the run_segments of the kind."""
+    lens = np.asarray(item_len.cpu().numpy() if lens_host is None else lens_host, dtype=np.int64)
+    seg_a, seg_start, pair_b, pair_a = plan_pairs(items, lens, exclude, cell_budget)
+    dev = data.device
+    if pair_b.size == 0:
+        return (torch.empty(0, dtype=torch.float32, device=dev), torch.empty(0, SPAN, dtype=torch.int32, device=dev), pair_a, pair_b)
+    max_len_a = max(1, int(lens[seg_a].max()))
+    max_len_b = max(1, int(lens[pair_b].max()))
+    score, span = run(torch.from_numpy(seg_a).to(dev), torch.from_numpy(seg_start).to(dev), torch.from_numpy(pair_b).to(dev),
+                      max_len_a, max_len_b)
+    return score, span, pair_a, pair_b
 
 
 def local_alignment(frames, item_off, item_len, items, distance, theta, gamma, exclude=None, lens_host=None, cell_budget=None):
@@ -81,16 +89,8 @@ def local_alignment(frames, item_off, item_len, items, distance, theta, gamma, e
     _lib.require_gpu(frames, item_off, item_len)
     if isinstance(distance, str):
         distance = distance_code(distance)
-    lens = np.asarray(item_len.cpu().numpy() if lens_host is None else lens_host, dtype=np.int64)
-    seg_a, seg_start, pair_b, pair_a = plan_pairs(items, lens, exclude, cell_budget)
-    dev = frames.device
-    if pair_b.size == 0:
-        return (torch.empty(0, dtype=torch.float32, device=dev), torch.empty(0, SPAN, dtype=torch.int32, device=dev), pair_a, pair_b)
-    max_len_a = max(1, int(lens[seg_a].max()))
-    max_len_b = max(1, int(lens[pair_b].max()))
-    score, span = run_segments(frames, item_off, item_len, torch.from_numpy(seg_a).to(dev), torch.from_numpy(seg_start).to(dev),
-                               torch.from_numpy(pair_b).to(dev), max_len_a, max_len_b, distance, theta, gamma)
-    return score, span, pair_a, pair_b
+    return _local_alignment(lambda *work: run_segments(frames, item_off, item_len, *work, distance, theta, gamma), frames, item_len,
+                            items, exclude, lens_host, cell_budget)
 
 
 # --------------------------------------------------------------------------- quantized units (csrc/lalign_units.hip)
@@ -101,36 +101,20 @@ def run_segments_units(units, item_off, item_len, seg_a, seg_start, pair_b, max_
     abx_group_computation.unit_frame_distances makes them).  scratch: at least cpc_local_align_units_scratch_bytes."""
     n_seg, n_pairs = td.check_unit_work_list("term discovery on units", units, item_off, item_len, seg_a, seg_start, pair_b,
                                              ("seg_a", "pair_b"))
-    dev = units.device
     lib = _lib.load()
-    nbytes = lib.cpc_local_align_units_scratch_bytes(n_seg, int(max_len_a), int(max_len_b))
-    scratch = td.fetch_scratch("term discovery on units", scratch, nbytes, dev, "lalign_units")
-    score = torch.empty(n_pairs, dtype=torch.float32, device=dev)
-    span = torch.empty(n_pairs, SPAN, dtype=torch.int32, device=dev)
-    _lib.check(lib.cpc_local_align_units(_lib.ptr(units), _lib.ptr(item_off), _lib.ptr(item_len), int(item_len.numel()),
-                                         _lib.ptr(seg_a), _lib.ptr(seg_start), _lib.ptr(pair_b), n_seg, int(max_len_a), int(max_len_b),
-                                         float(d_same), float(d_diff), float(theta), float(gamma), _lib.ptr(score), _lib.ptr(span),
-                                         _lib.ptr(scratch), nbytes, _lib.stream_ptr(dev)), "cpc_local_align_units")
-    return score, span
+    return td._call_segments("term discovery on units", "cpc_local_align_units", lib.cpc_local_align_units_scratch_bytes,
+                             lib.cpc_local_align_units, "lalign_units", (units,), (item_off, item_len, seg_a, seg_start, pair_b),
+                             (n_seg, n_pairs, max_len_a, max_len_b), (float(d_same), float(d_diff), float(theta), float(gamma)),
+                             SPAN, scratch)
 
 
 def local_alignment_units(units, item_off, item_len, items, d_same, d_diff, theta, gamma, exclude=None, lens_host=None,
                           cell_budget=None):
     """local_alignment on items of unit ids: units [total_frames] int32 on the device, d_same / d_diff the frame distance between
     equal / different units.  The same plan and the same returns."""
-    if not isinstance(units, torch.Tensor) or units.dtype != torch.int32 or not units.is_contiguous() or units.dim() != 1:
-        raise TypeError("term discovery on units: units must be a contiguous int32 tensor [total_frames]")
-    _lib.require_gpu(units, item_off, item_len)
-    lens = np.asarray(item_len.cpu().numpy() if lens_host is None else lens_host, dtype=np.int64)
-    seg_a, seg_start, pair_b, pair_a = plan_pairs(items, lens, exclude, cell_budget)
-    dev = units.device
-    if pair_b.size == 0:
-        return (torch.empty(0, dtype=torch.float32, device=dev), torch.empty(0, SPAN, dtype=torch.int32, device=dev), pair_a, pair_b)
-    max_len_a = max(1, int(lens[seg_a].max()))
-    max_len_b = max(1, int(lens[pair_b].max()))
-    score, span = run_segments_units(units, item_off, item_len, torch.from_numpy(seg_a).to(dev), torch.from_numpy(seg_start).to(dev),
-                                     torch.from_numpy(pair_b).to(dev), max_len_a, max_len_b, d_same, d_diff, theta, gamma)
-    return score, span, pair_a, pair_b
+    td._check_units("term discovery on units", units, item_off, item_len)
+    return _local_alignment(lambda *work: run_segments_units(units, item_off, item_len, *work, d_same, d_diff, theta, gamma), units,
+                            item_len, items, exclude, lens_host, cell_budget)
 
 
 # --------------------------------------------------------------------------- matches

@@ -527,7 +527,8 @@ int cpc_abx_counts(const float *dist, int n_pairs, const int *idx_a, const int *
  * frame distance is d_same where the two units are equal and d_diff where they differ: the two values the reference's
  * distance takes on one-hot rows, computed by the caller.  Segment / pair lists, outputs, path-length rule, limits and the
  * not-computable convention (NaN, path length -1) are those of cpc_abx_dtw; cost = d + predecessor in f32, one f32 division
- * by the path length at the end.  scratch: cpc_abx_dtw_units_scratch_bytes (0 when every x item has <= 64 frames).
+ * by the path length at the end.  scratch: cpc_abx_dtw_units_scratch_bytes (0 when every x item has <= 64 frames; 0 and a
+ * "negative size" message in cpc_last_error for a negative argument, as the other queries on units).
  * ------------------------------------------------------------------------------------------ */
 size_t cpc_abx_dtw_units_scratch_bytes(int n_seg, int max_len_x, int max_len_y);
 int cpc_abx_dtw_units(const int *units, const int *item_off, const int *item_len, int n_items,

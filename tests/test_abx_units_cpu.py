@@ -204,6 +204,23 @@ def test_abi_declares_the_unit_kernel():
     assert "abx_units.hip" in open(os.path.join(ROOT, "cpc2_amd", "build.py")).read()
 
 
+def test_scratch_query_is_pinned():
+    """0 when one strip holds every x item; else min(n_seg, 8192) workgroups x 4 waves x 2 buffers x 8 bytes x max_len_y: the
+    grid cap of the dense kernels, not the 2048 of the two term kernels on units."""
+    lib = _lib.load()
+    size = lib.cpc_abx_dtw_units_scratch_bytes
+    for n_seg in (1, 100, 8192, 20000):
+        for max_len_x in (64, 65):
+            for max_len_y in (1, 500):
+                want = 0 if max_len_x <= 64 else min(n_seg, 8192) * 4 * 2 * 8 * max_len_y
+                assert size(n_seg, max_len_x, max_len_y) == want, (n_seg, max_len_x, max_len_y)
+    assert size(0, 65, 500) == 0
+    for bad in ((-1, 65, 500), (5, -65, 500), (5, 65, -500)):
+        assert size(*bad) == 0
+        message = lib.cpc_last_error()
+        assert message.startswith(b"abx_dtw_units:") and b"negative size" in message, message
+
+
 # --------------------------------------------------------------------------- command line
 def test_command_line(tmp_path, capsys):
     base = ["--path_audio_data", "db", "--path_abx_item", "x.item"]

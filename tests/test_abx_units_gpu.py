@@ -148,6 +148,56 @@ def test_unit_kernel_equals_dense_kernel_2000_units():
     assert np.array_equal(plen, dplen) and np.array_equal(vals, dvals)
 
 
+def test_strip_ends_stale_boundary_columns_and_the_not_computable_rule():
+    """What X_LENS / Y_LENS leave open, against the oracle bit for bit (cosine: 0 / 0.5).  x of 128 (last row in lane 63), 129
+    (last row in lane 0 of a third strip) and 192 frames (three full strips) against y of 1, 64, 65, 129 and 130, the y items
+    ordered so that wave w of the four takes pairs w and w + 4 of a segment: a long y and then a short one under the same
+    x, whose boundary rows then hold stale columns beyond the shorter y.  Then the rule for what is not computable: with
+    max_len_y = 50 and a y of 100 frames in the list, an x of one strip (64) is computed against it (no boundary row is
+    touched), an x of 65 frames is NaN / -1; the scratch is of exactly the queried size and nothing is written behind it."""
+    n_units = 6
+    rng = np.random.default_rng(31)
+    d_same, d_diff = abx_g.unit_frame_distances(n_units, True, COS)
+    assert (d_same, d_diff) == (0.0, 0.5)
+    xs = [_runs(rng, n, n_units) for n in (128, 129, 192)]
+    ys = [_runs(rng, n, n_units) for n in (130, 129, 65, 64, 1)]
+    order = [0, 1, 2, 3, 4, 3, 4, 2]                       # waves: 130 -> 1, 129 -> 64, 65 -> 1, 64 -> 65
+    items, code = _unit_items(xs + ys, COS, n_units=n_units)
+    px = np.repeat(np.arange(len(xs)), len(order))
+    py = np.tile(np.array(order), len(xs)) + len(xs)
+    vals, plen = abx_g._dtw_pairs(items, px, py, code)
+    vals, plen = vals.cpu().numpy(), plen.cpu().numpy()
+    want = {(i, j): _oracle(x, y, d_same, d_diff) for i, x in enumerate(xs) for j, y in enumerate(ys)}
+    for p, (i, j) in enumerate(zip(px, py - len(xs))):
+        v, n = want[i, j]
+        assert vals[p] == np.float32(v) and plen[p] == n, (p, len(xs[i]), len(ys[j]), vals[p], v, plen[p], n)
+
+    seqs = [_runs(rng, n, n_units) for n in (64, 65, 100, 30)]
+    items, code = _unit_items(seqs, COS, n_units=n_units)
+    lib = _lib.load()
+    seg_x = torch.tensor([0, 1], dtype=torch.int32, device=DEV)
+    seg_start = torch.tensor([0, 2, 4], dtype=torch.int32, device=DEV)
+    pair_y = torch.tensor([2, 3, 2, 3], dtype=torch.int32, device=DEV)
+    nbytes = lib.cpc_abx_dtw_units_scratch_bytes(2, 65, 50)
+    assert nbytes == 2 * 4 * 2 * 8 * 50
+    guard = 4096
+    scratch = torch.full((nbytes + guard,), 0xFF, dtype=torch.uint8, device=DEV)
+    vals = torch.zeros(4, dtype=torch.float32, device=DEV)
+    plen = torch.zeros(4, dtype=torch.int32, device=DEV)
+    _lib.check(lib.cpc_abx_dtw_units(_lib.ptr(items.units), _lib.ptr(items.off), _lib.ptr(items.lens), items.n,
+                                     _lib.ptr(seg_x), _lib.ptr(seg_start), _lib.ptr(pair_y), 2, 65, 50, d_same, d_diff,
+                                     _lib.ptr(vals), _lib.ptr(plen), _lib.ptr(scratch), nbytes, _lib.stream_ptr(DEV)),
+               "cpc_abx_dtw_units")
+    vals, plen = vals.cpu().numpy(), plen.cpu().numpy()
+    assert (scratch[nbytes:] == 0xFF).all().item()
+    for p, (i, j) in enumerate(((0, 2), (0, 3), (1, 2), (1, 3))):
+        if (i, j) == (1, 2):                                 # 65 frames against 100 > max_len_y: a boundary row would not hold it
+            assert np.isnan(vals[p]) and plen[p] == -1
+        else:
+            v, n = _oracle(seqs[i], seqs[j], d_same, d_diff)
+            assert vals[p] == np.float32(v) and plen[p] == n, (p, vals[p], v, plen[p], n)
+
+
 def test_reference_dtw_cases(g22):
     for k in range(int(g22["dtw_n"])):
         code, sym, n_units = (int(v) for v in g22[f"dtw{k}_cfg"])

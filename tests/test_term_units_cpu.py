@@ -50,14 +50,24 @@ def test_header_library_and_bindings_name_the_entry_points():
         assert name in _lib.SIGNATURES, name
     assert _lib.load().cpc_version() >= 131
     sources = set(os.listdir(os.path.join(ROOT, "cpc2_amd", "csrc")))
-    assert {"dtw_units_walk.h", "sdtw_rule.h", "lalign_rule.h", "sdtw_units.hip", "lalign_units.hip"} <= sources
-    # the recurrences stay in one copy: the rule headers define them, the four kernels include them
-    for rule, header_name, users in (("struct SdRule", "sdtw_rule.h", ("sdtw.hip", "sdtw_units.hip")),
+    assert {"dtw_units_walk.h", "abx_rule.h", "sdtw_rule.h", "lalign_rule.h", "abx_units.hip", "sdtw_units.hip",
+            "lalign_units.hip"} <= sources
+    read = lambda f: open(os.path.join(ROOT, "cpc2_amd", "csrc", f)).read()  # noqa: E731
+    # the recurrences stay in one copy: the rule headers define them, the six kernels include them
+    for rule, header_name, users in (("struct AbxRule", "abx_rule.h", ("abx.hip", "abx_units.hip")),
+                                     ("struct SdRule", "sdtw_rule.h", ("sdtw.hip", "sdtw_units.hip")),
                                      ("struct LaRule", "lalign_rule.h", ("lalign.hip", "lalign_units.hip"))):
-        holders = [f for f in sorted(sources) if rule in open(os.path.join(ROOT, "cpc2_amd", "csrc", f)).read()]
+        holders = [f for f in sorted(sources) if rule in read(f)]
         assert holders == [header_name], (rule, holders)
         for user in users:
-            assert f'#include "{header_name}"' in open(os.path.join(ROOT, "cpc2_amd", "csrc", user)).read(), user
+            assert f'#include "{header_name}"' in read(user), user
+    # ... and so does the walk on unit ids: the three unit kernels include it, and the ABX one has no walk of its own left
+    for user in ("abx_units.hip", "sdtw_units.hip", "lalign_units.hip"):
+        assert '#include "dtw_units_walk.h"' in read(user), user
+    abx_units = read("abx_units.hip")
+    assert "readlane" not in abx_units and not re.search(r"\bshr1\s*\(", abx_units)
+    assert not re.search(r"for\s*\([^)]*\brs\b", abx_units), "a strip loop"
+    assert len(re.findall(r"\bfor\s*\(", abx_units)) == 2, "the segment loop and the pair loop"
 
 
 # --------------------------------------------------------------------------- the tools' refusals
